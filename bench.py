@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- `deSAMBA classify` hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--reads-per-gpu R] [--read-len L] [--batches B]
+    python bench.py --gpus N --steps K --warmup W [--reads-per-gpu R] [--read-len L] [--batches B] [--dump-outputs DIR]
 
 Headline workload (BASELINE.json configs[1]: "viral RefSeq index (~1 GB), synthetic 50 kbp ONT-15 %-error reads"): the RefSeq
 index is not in the mount and cannot be downloaded, so a viral-RefSeq-sized one is made here -- a >= 300-Mbp synthetic strain
@@ -29,6 +29,10 @@ the stock reference vs the UB-pinned build, and the stock reference with itself 
 residue).  `demo_index` repeats the measurements on the reference's own demo index (463 viral
 genomes, 11.5 Mbp: round 1-2's headline), where the device path is 4.5x faster and the host pipeline is what is tested.
 Indexes and reads are input data; nothing of oracle/ is on a measured GPU path.
+
+--dump-outputs DIR writes what the last timed step returned (rank 0: per-read records and hits, Measure.dump_outputs) as .npy
+files, so that two builds can be compared output for output: the index and the reads are seeded, the same arguments give the
+same inputs (pass --batches as well where the host memory differs: its default depends on it).
 """
 import argparse
 import ctypes as C
@@ -46,13 +50,31 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")   # before the HIP runtime starts (the HIP runtime reads it at its first call)
 
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (6.3 TB/s achievable)
 CLI = os.path.join(ROOT, "desamba_amd", "bin", "deSAMBA")
 REF = os.path.join(ROOT, "oracle", "_ref", "deSAMBA")
 UBF = os.path.join(ROOT, "oracle", "_ref", "deSAMBA_ubfree")
 SHM = "/dev/shm" if os.path.isdir("/dev/shm") else "/tmp"
+
+
+def data_root():
+    """where the indexes of the run go: data/ of the tree, or (a read-only checkout) a directory of this user's under the system's
+    temporary directory; DSB_BENCH_DATA overrides both"""
+    d = os.environ.get("DSB_BENCH_DATA")
+    if not d:
+        d = os.path.join(ROOT, "data")
+        if not os.access(d if os.path.isdir(d) else ROOT, os.W_OK):
+            import tempfile
+            d = os.path.join(tempfile.gettempdir(), "desamba_amd_bench_%d" % os.getuid())
+    os.makedirs(d, exist_ok=True)
+    return d
+
+
+DATA = data_root()
+DUMP_LIMIT = 64 << 20      # --dump-outputs: bytes of .npy files at most
+DUMP_READS = 65536         #   reads whose results are written (a seeded sample of them on larger batches)
+DUMP_SEED = 20240607
 
 
 def self_launch(a):
@@ -354,6 +376,7 @@ class Measure:
         dt = reduce_max(time.perf_counter() - t0)
         self.acc, self.dt, self.n_steps = acc, dt, steps
         res = ctx.fetch(strict=False)
+        self.res = res                              # the last timed step's results (valid until the next batch on ctx)
         R = self.R
         self.n_bad = sum(1 for i in range(R) if res.reads[i].status != 0)
         self.n_mapped = sum(1 for i in range(R) if res.reads[i].n > 0)
@@ -433,6 +456,34 @@ class Measure:
                 "batches": len(order), "hits_fetched": hits[0] + hits[1],
                 "what": "per batch: H2D of the raw FASTQ text (sequence + quality lines, %.1f GB) from pinned memory, all kernels, D2H of per-read results and hits; two contexts on the GPU share the staged index; the kernels of one batch at a time (dsb_batch_run takes a per-device turn), the other context's upload and fetch overlap them" % (bufs[0][1] / 1e9)}
 
+    def dump_outputs(self, out_dir, limit=DUMP_LIMIT):
+        """what the last timed step returned to its caller (dsb_batch_fetch), as float64 .npy files under out_dir: the per-read
+        records of every read (of a fixed, seeded sample of DUMP_READS reads on larger batches) and the hits of those reads, read by
+        read in sample order while the files stay within `limit` bytes.  device_us is a timing, not a result, and is left out."""
+        import numpy as np
+        read_dt = np.dtype([("first", "<u4"), ("n", "<u4"), ("status", "<i4"), ("fast", "<u4"), ("device_us", "<u4"), ("n_anc", "<u4")])
+        hit_dt = np.dtype([(f, "<u4") for f in ("ref_ID", "t_st", "t_ed", "q_st", "q_ed", "sum_score", "indel")] +
+                          [(f, "u1") for f in ("direction", "primary", "pri_index", "pad")])
+        assert read_dt.itemsize == C.sizeof(self.D.DsbReadResult) and hit_dt.itemsize == C.sizeof(self.D.DsbHit)
+        res, R = self.res, self.R
+        reads = np.frombuffer(C.string_at(res.reads, R * read_dt.itemsize), dtype=read_dt)
+        pick = np.arange(R) if R <= DUMP_READS else np.sort(np.random.default_rng(DUMP_SEED).choice(R, DUMP_READS, replace=False))
+        rs = reads[pick]
+        out = {"read_index": pick, "read_n_hits": rs["n"], "read_status": rs["status"], "read_fast": rs["fast"], "read_n_anc": rs["n_anc"]}
+        cols = [f for f in hit_dt.names if f != "pad"]
+        room = (limit - (len(out) + 1) * 128 - 8 * len(pick) * len(out)) // (8 * (1 + len(cols)))    # hit rows that fit (128 = .npy header)
+        counts = rs["n"].astype(np.int64)
+        take = int(np.searchsorted(np.cumsum(counts), room, side="right"))                          # whole reads only
+        counts = counts[:take]; n = int(counts.sum())
+        rows = np.repeat(rs["first"][:take].astype(np.int64) - np.cumsum(counts) + counts, counts) + np.arange(n)
+        allh = np.frombuffer(C.string_at(res.hits, int(res.n_hits) * hit_dt.itemsize), dtype=hit_dt) if n else np.zeros(0, hit_dt)
+        h = allh[rows]
+        out["hits"] = np.stack([np.repeat(pick[:take], counts)] + [h[f] for f in cols], axis=1) if n else np.zeros((0, 1 + len(cols)))
+        os.makedirs(out_dir, exist_ok=True)
+        for name, v in out.items():
+            np.save(os.path.join(out_dir, name + ".npy"), np.asarray(v, dtype=np.float64))
+        return {"dir": out_dir, "reads": len(pick), "reads_with_hits_written": take, "hits": n, "hits_columns": ["read_index"] + cols}
+
     def sample(self, ns):
         """SAM of the first ns reads of batch 0 (library's writer) and the FASTQ text of those reads"""
         D, ctx, bufs, Lr, R = self.D, self.ctx, self.bufs, self.Lr, self.R
@@ -509,7 +560,7 @@ def resident_batch(D, L, idx, index_dir, local, n, length, err, seed, profile, t
 def proxy_index(a, D, local):
     """BASELINE configs[4] stands for a bacterial-scale index that is not in the mount: its proxy is a synthetic collection of
     a.proxy_mbp million bases indexed here by this repo's builder (k = 17 / 18 filter tables, natural 64-bit rank counts from 4.3 G rows on)"""
-    d = os.path.join(ROOT, "data", "bench_proxy"); idxd = os.path.join(d, "index")
+    d = os.path.join(DATA, "bench_proxy"); idxd = os.path.join(d, "index")
     shutil.rmtree(d, ignore_errors=True); os.makedirs(d)
     fa = os.path.join(d, "syn.fa")
     t0 = time.perf_counter()
@@ -524,7 +575,7 @@ def proxy_index(a, D, local):
 
 def strain_index(a, D, rank, local, barrier):
     """the viral-RefSeq-sized index of the headline: made by rank 0 with this repo's builder, opened by every rank"""
-    d = os.path.join(ROOT, "data", "bench_strain"); idxd = os.path.join(d, "index"); info = None
+    d = os.path.join(DATA, "bench_strain"); idxd = os.path.join(d, "index"); info = None
     if rank == 0:
         shutil.rmtree(d, ignore_errors=True); os.makedirs(d)
         fa = os.path.join(d, "syn.fa")
@@ -593,6 +644,7 @@ def main():
     ap.add_argument("--proxy-reads", type=int, default=65536)
     ap.add_argument("--proxy-parity", type=int, default=2048, help="reads of the proxy's parity sample against the reference's UB-pinned build")
     ap.add_argument("--slots", type=int, default=0, help="reads in flight per GPU (0 = library default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the results of the last timed step as DIR/<name>.npy (float64, at most 64 MB)")
     a = ap.parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -621,13 +673,13 @@ def main():
     if rank == 0:
         if not os.path.exists(D.LIB_PATH):
             G.build()
-        G.demo_dir()
+        subprocess.check_call([os.path.join(ROOT, "tools", "make_demo_index.sh"), os.path.join(DATA, "demo")], stdout=sys.stderr)   # (one line on stdout)
 
     def barrier():
         if dist:
             dist.barrier()
     barrier()
-    demo_dir = os.path.join(ROOT, "data", "demo", "index")
+    demo_dir = os.path.join(DATA, "demo", "index")
 
     if not have_gpu:
         if not rehearsal:
@@ -675,6 +727,7 @@ def main():
     m = Measure(D, L, idx, index_dir, local, a, R, Lr, B, 1000 * (rank + 1), gen_threads)
     t_stage = time.perf_counter() - t0
     dt = m.steps(a.warmup, a.steps, sync_all, reduce_max)
+    dumped = m.dump_outputs(a.dump_outputs) if a.dump_outputs and rank == 0 and a.steps > 0 else None
     e2e = None if a.no_end_to_end else m.end_to_end(sync_all, reduce_max, world, min_batches=max(4, B))
     out = None
     if rank == 0:
@@ -699,6 +752,8 @@ def main():
                                  "p99": m.dev_us[int(len(m.dev_us) * 0.99)] if m.dev_us else 0, "max": m.dev_us[-1] if m.dev_us else 0},
             "generation_s": m.t_gen, "stage_s": t_stage,
         }
+        if dumped:
+            out["dump_outputs"] = dumped
         lib_md5 = None; ns = min(a.cpu_sample, R)
         if not a.no_cpu_baseline or not a.no_cli:
             gpu_sam, fq_text = m.sample(ns)
@@ -736,7 +791,7 @@ def main():
         c5["index_build"] = pinfo
         out["config5_proxy"] = c5
         pidx.close()
-        shutil.rmtree(os.path.join(ROOT, "data", "bench_proxy"), ignore_errors=True)
+        shutil.rmtree(os.path.join(DATA, "bench_proxy"), ignore_errors=True)
     barrier()                                   # every rank has given its device memory back: the CLI takes all GPUs
     if rank == 0 and not a.no_cli:
         n_cli = a.cli_reads * world
@@ -808,7 +863,7 @@ def main():
                 ce["fraction_of_end_to_end"] = ce["reads_per_s"] / demo["end_to_end"]["reads_per_s"]
         out["demo_index"] = demo
     if rank == 0:
-        shutil.rmtree(os.path.join(ROOT, "data", "bench_strain"), ignore_errors=True)
+        shutil.rmtree(os.path.join(DATA, "bench_strain"), ignore_errors=True)
         print(json.dumps(out), flush=True)
     if dist:
         dist.barrier(); dist.destroy_process_group()

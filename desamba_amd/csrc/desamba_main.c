@@ -997,9 +997,7 @@ int analysis_main(int argc, char **argv, const char *version);   /* desamba_anal
 #ifndef DSB_CLI_NO_MAIN
 int main(int argc, char **argv)
 {	/* dispatcher, src/main.c:35-53: `classify`, `index` and `analysis ana_meta[_base]` are in scope of this build */
-	/* two contexts per device share eight streams: with HIP's default of 4 hardware queues an upload waits behind the other
-	 * context's persistent kernel (10-15 GB/s instead of 50); read by the HIP runtime at its first call, so set here, first */
-	setenv("GPU_MAX_HW_QUEUES", "16", 0);
+	/* (the number of hardware queues is left to the environment: GPUs shared between users cap it, see dsb_gpu.hip) */
 	if (argc >= 2 && strcmp(argv[1], "index") == 0) return index_main(argc - 1, argv + 1);
 	if (argc >= 2 && strcmp(argv[1], "analysis") == 0) return analysis_main(argc - 1, argv + 1, dsb_version());
 	if (argc < 2 || strcmp(argv[1], "classify") != 0) {

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Regenerates tests/golden/build/*: small reference FASTA files (synthetic, seeded) and, for each, the md5 of every
+"""Regenerates tests/golden/index_build/*: small reference FASTA files (synthetic, seeded) and, for each, the md5 of every
 index file the REFERENCE binary writes for it (oracle/_ref/kmer_srt -> oracle/_ref/deSAMBA index; needs
 /root/reference to have been compiled by oracle/Makefile, i.e. this container).  Fixtures are data: FASTA inputs and
 expected digests.  `.bwt` is digested with the bytes behind its last symbol zeroed when the index has fewer than 257
@@ -18,7 +18,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 import build_lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-OUT = os.path.join(ROOT, "tests", "golden", "build")
+OUT = os.path.join(ROOT, "tests", "golden", "index_build")
 REF = os.path.join(ROOT, "oracle", "_ref")
 
 

@@ -1,6 +1,6 @@
 """Index construction (`deSAMBA index`): the files written must be those of the reference's builder.
 
-Golden digests (tests/golden/build/*.md5.json, made by tests/golden/make_build_golden.py from the reference binary)
+Golden digests (tests/golden/index_build/*.md5.json, made by tests/golden/make_build_golden.py from the reference binary)
 for small synthetic references, and the demo index's md5s.  CPU tests run the builder's stages in the
 host emulation (tests/emu/emu_build.cpp: the same dsb_build_impl.h the GPU runs); GPU tests go through
 dsb_index_build / the CLI."""
@@ -16,7 +16,7 @@ import pytest
 import build_lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(ROOT, "tests", "golden", "build")
+GOLD = os.path.join(ROOT, "tests", "golden", "index_build")
 CASES = ["graph1", "graph2", "graph3", "reader"]
 # md5 of the demo index files as the reference builds them (stable across rebuilds)
 DEMO_MD5 = {".bwt": "1532b15ccccbf7268386e2758000f5c2", ".exk0": "000472fabf9c519d075726634427736f", ".exk1": "bbbd736229d6b4a3e21c494f094c0ac4",

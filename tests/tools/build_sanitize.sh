@@ -12,7 +12,7 @@ import build_lib
 L = C.CDLL("$tmp/libdsbemu_build_san.so")
 L.dsb_emu_index_build_parts.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
 L.dsb_emu_index_build.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64)]
-G = "tests/golden/build"; bad = 0
+G = "tests/golden/index_build"; bad = 0
 for name, parts in (("graph3", 7), ("graph1", 3), ("reader", 2)):
     want = json.load(open(G + "/" + name + ".md5.json"))
     d = tempfile.mkdtemp(dir="$tmp"); st = (C.c_uint64 * 11)()

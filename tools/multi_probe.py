@@ -3,7 +3,6 @@ python3 tools/multi_probe.py [n_reads] [len]   (demo index; prints wall times an
 import ctypes as C, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import __graft_entry__ as G
 import desamba_amd as D
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 131072; L = int(sys.argv[2]) if len(sys.argv) > 2 else 5000
