@@ -61,6 +61,13 @@ class DsbBuildStats(C.Structure):
                [("spilled_bytes", C.c_uint64)]
 
 
+class DsbReadTaxon(C.Structure):
+    _fields_ = [("taxid", C.c_uint32), ("score", C.c_uint32), ("len", C.c_uint32), ("mapq", C.c_uint8), ("flags", C.c_uint8), ("pad", C.c_uint16)]
+
+
+DSB_TAXON_CLASSIFIED, DSB_TAXON_HOST = 1, 2
+
+
 class DsbChunk(C.Structure):
     _fields_ = [("start", C.c_uint64), ("end", C.c_uint64), ("hist_max_before", C.c_uint32), ("rank", C.c_int32)]
 
@@ -70,7 +77,10 @@ EXPORTS = ["dsb_index_open", "dsb_index_close", "dsb_index_n_ref", "dsb_index_re
            "dsb_batch_upload", "dsb_batch_upload_fastq", "dsb_batch_upload_text", "dsb_ctx_set_history", "dsb_host_alloc", "dsb_host_free", "dsb_host_cpus", "dsb_batch_run", "dsb_batch_fetch", "dsb_batch_timing", "dsb_batch_seeds", "dsb_batch_exist_bits",
            "dsb_format_sam", "dsb_format_des", "dsb_strerror", "dsb_version",
            "dsb_device_count", "dsb_ctx_select_slot", "dsb_ctx_create_multi", "dsb_multi_destroy", "dsb_multi_n", "dsb_multi_ctx",
-           "dsb_multi_reset_history", "dsb_multi_last_calls", "dsb_multi_classify_batch", "dsb_shard_plan", "dsb_ctx_use_synthetic_filter", "dsb_synthetic_filter_bit", "dsb_index_prefix_interval", "dsb_index_build"]
+           "dsb_multi_reset_history", "dsb_multi_last_calls", "dsb_multi_classify_batch", "dsb_shard_plan", "dsb_ctx_use_synthetic_filter", "dsb_synthetic_filter_bit", "dsb_index_prefix_interval", "dsb_index_build",
+           "dsb_taxonomy_load", "dsb_taxonomy_load_any", "dsb_taxonomy_close", "dsb_taxonomy_max_tid", "dsb_taxonomy_parent",
+           "dsb_ctx_set_taxonomy", "dsb_multi_set_taxonomy", "dsb_batch_taxa", "dsb_multi_taxa",
+           "dsb_report_create", "dsb_report_add", "dsb_report_add_sam", "dsb_report_format", "dsb_report_destroy"]
 
 _lib = None
 
@@ -125,6 +135,20 @@ def lib():
     L.dsb_index_prefix_interval.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.dsb_index_build.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(DsbBuildStats)]
     L.dsb_index_close.restype = None; L.dsb_ctx_destroy.restype = None; L.dsb_ctx_reset_history.restype = None
+    L.dsb_taxonomy_load.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
+    L.dsb_taxonomy_load_any.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
+    L.dsb_taxonomy_close.argtypes = [C.c_void_p]; L.dsb_taxonomy_close.restype = None
+    L.dsb_taxonomy_max_tid.argtypes = [C.c_void_p]; L.dsb_taxonomy_max_tid.restype = C.c_uint32
+    L.dsb_taxonomy_parent.argtypes = [C.c_void_p, C.c_uint32]; L.dsb_taxonomy_parent.restype = C.c_uint32
+    L.dsb_ctx_set_taxonomy.argtypes = [C.c_void_p, C.c_void_p]
+    L.dsb_multi_set_taxonomy.argtypes = [C.c_void_p, C.c_void_p]
+    L.dsb_batch_taxa.argtypes = [C.c_void_p, C.POINTER(C.POINTER(DsbReadTaxon))]
+    L.dsb_multi_taxa.argtypes = [C.c_void_p, C.POINTER(C.POINTER(DsbReadTaxon))]
+    L.dsb_report_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.dsb_report_add.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(DsbRead), C.POINTER(DsbResult), C.POINTER(DsbReadTaxon), C.c_size_t, C.c_int]
+    L.dsb_report_add_sam.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+    L.dsb_report_format.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t]; L.dsb_report_format.restype = C.c_long
+    L.dsb_report_destroy.argtypes = [C.c_void_p]; L.dsb_report_destroy.restype = None
     L.dsb_strerror.argtypes = [C.c_int]; L.dsb_strerror.restype = C.c_char_p
     L.dsb_version.restype = C.c_char_p
     _lib = L
@@ -290,6 +314,26 @@ class Ctx:
             raise DsbError(rc, "dsb_batch_exist_bits")
         return bytes(buf[:n.value])
 
+    def set_taxonomy(self, taxonomy):
+        """attach a Taxonomy (None detaches): every batch from now on ends with the per-read taxon kernel"""
+        rc = lib().dsb_ctx_set_taxonomy(self.h, taxonomy.h if taxonomy is not None else None)
+        if rc != 0:
+            raise DsbError(rc, "dsb_ctx_set_taxonomy")
+        self.taxonomy = taxonomy
+
+    def taxa(self, records=False):
+        """the taxon of each read of the last batch (numpy u32, 0 = unclassified): the walk over the read's own records;
+        records=True: the DsbReadTaxon array itself (what Report.add takes)"""
+        p = C.POINTER(DsbReadTaxon)()
+        rc = lib().dsb_batch_taxa(self.h, C.byref(p))
+        if rc != 0:
+            raise DsbError(rc, "dsb_batch_taxa")
+        n = self.in_last_batch()
+        return _taxa(p, n, records)
+
+    def in_last_batch(self):
+        return len(self.reads) if self.reads is not None else getattr(self, "n_uploaded", 0)
+
     def sam(self, res, full=False, reads=None):
         """Format a whole batch exactly as output_one_result_sam does (src/cly_mt.c:245-344)."""
         return format_sam(self.index, reads if reads is not None else self.reads, res, self.opts.max_sec_N, full)
@@ -340,7 +384,90 @@ class Multi:
         rc = lib().dsb_multi_classify_batch(self.h, reads, len(reads), C.byref(res))
         if rc != 0 and (strict or rc != DSB_ECAP):
             raise DsbError(rc, "dsb_multi_classify_batch")
+        self.n_last = len(reads)
         return res
+
+    def set_taxonomy(self, taxonomy):
+        rc = lib().dsb_multi_set_taxonomy(self.h, taxonomy.h if taxonomy is not None else None)
+        if rc != 0:
+            raise DsbError(rc, "dsb_multi_set_taxonomy")
+        self.taxonomy = taxonomy
+
+    def taxa(self, records=False):
+        """Ctx.taxa for the last classify(), in input order"""
+        p = C.POINTER(DsbReadTaxon)()
+        rc = lib().dsb_multi_taxa(self.h, C.byref(p))
+        if rc != 0:
+            raise DsbError(rc, "dsb_multi_taxa")
+        return _taxa(p, getattr(self, "n_last", 0), records)
+
+
+def _taxa(p, n, records):
+    arr = (DsbReadTaxon * n)()
+    if n:
+        C.memmove(arr, p, n * C.sizeof(DsbReadTaxon))
+    if records:
+        return arr
+    import numpy as np
+    return np.array([arr[i].taxid for i in range(n)], dtype=np.uint32)
+
+
+class Taxonomy:
+    """nodes.dmp as `deSAMBA analysis` reads it (max_tid = last line's taxid + 1 000 000); DsbError on a parent cycle
+    (DSB_EINVAL) or a file that cannot be read (DSB_EIO)."""
+
+    def __init__(self, path):
+        self.h = C.c_void_p()
+        rc = lib().dsb_taxonomy_load(os.fsencode(path), C.byref(self.h))
+        if rc != 0:
+            raise DsbError(rc, "dsb_taxonomy_load(%s)" % path)
+        self.path = path
+
+    def close(self):
+        if self.h:
+            lib().dsb_taxonomy_close(self.h); self.h = C.c_void_p()
+
+    @property
+    def max_tid(self):
+        return int(lib().dsb_taxonomy_max_tid(self.h))
+
+    def parent(self, taxid):
+        return int(lib().dsb_taxonomy_parent(self.h, taxid))
+
+
+class Report:
+    """the abundance report of `analysis ana_meta[_base]`, fed batch by batch in input order"""
+
+    def __init__(self, taxonomy):
+        self.taxonomy = taxonomy
+        self.h = C.c_void_p()
+        rc = lib().dsb_report_create(taxonomy.h, C.byref(self.h))
+        if rc != 0:
+            raise DsbError(rc, "dsb_report_create")
+
+    def close(self):
+        if self.h:
+            lib().dsb_report_destroy(self.h); self.h = C.c_void_p()
+
+    def add(self, index, reads, res, taxa=None, max_sec_N=5):
+        """reads / res of one batch; taxa: Ctx.taxa(records=True) of it, or None (every read walked on the host)"""
+        rc = lib().dsb_report_add(self.h, index.h, reads, C.byref(res), taxa, len(reads), max_sec_N)
+        if rc != 0:
+            raise DsbError(rc, "dsb_report_add")
+
+    def add_sam(self, text):
+        rc = lib().dsb_report_add_sam(self.h, text, len(text))
+        if rc != 0:
+            raise DsbError(rc, "dsb_report_add_sam")
+
+    def text(self, by_base=False):
+        cap = 1 << 16
+        while True:
+            buf = C.create_string_buffer(cap)
+            n = lib().dsb_report_format(self.h, 1 if by_base else 0, buf, cap)
+            if n >= 0:
+                return buf.raw[:n]
+            cap *= 4
 
 
 def shard_plan(lengths, world, chunk_bases=0, chunk_reads=0):

@@ -60,6 +60,7 @@ typedef struct {
 	void **own; int n_own, cap_own;                   /* malloc'd blocks the reads point into: names, records joined across blocks */
 	gzbuf_t **gzb; int n_gzb, cap_gzb;                /* inflated blocks the reads point into */
 	dsb_read_result *rr; dsb_hit *hits; size_t cap_rr, cap_hits, n_hits;
+	dsb_read_taxon *taxa; size_t cap_taxa;            /* --report: the device's per-read taxa of the batch */
 } batch_t;
 
 typedef struct { batch_t *slot[N_BATCH + 2]; int head, n, closed; pthread_mutex_t mu; pthread_cond_t cv; } queue_t;
@@ -129,6 +130,8 @@ typedef struct {
 	int trace; trace_t tr; pthread_mutex_t tr_mu; long thr0; double t0;
 	/* recycled inflated blocks */
 	gzbuf_t *gz_free; pthread_mutex_t gz_mu;
+	/* --taxonomy / --report / --report-base: the abundance report of `analysis ana_meta[_base]`, fed by the writer in input order */
+	dsb_taxonomy *tx; dsb_report *rep; FILE *rep_out[2];
 } app_t;
 
 /* ================================================================ gzip input: inflate ahead of the parser ==========
@@ -750,6 +753,12 @@ static void *gpu_main(void *arg)
 			memcpy(b->rr, res.reads, b->n * sizeof *b->rr);
 			if (res.n_hits) memcpy(b->hits, res.hits, res.n_hits * sizeof *b->hits);
 			b->n_hits = res.n_hits;
+			if (a->rep) {
+				const dsb_read_taxon *t; int rt = dsb_batch_taxa(ctx, &t);
+				if (rt) { fprintf(stderr, "[dsb_batch_taxa] %s\n", dsb_strerror(rt)); exit(1); }
+				if (b->n > b->cap_taxa) { b->cap_taxa = b->n * 2; b->taxa = xrealloc(b->taxa, b->cap_taxa * sizeof *b->taxa); }
+				memcpy(b->taxa, t, b->n * sizeof *b->taxa);
+			}
 			t_idle = now();
 		}
 		q_push(&a->done_q, b);
@@ -806,6 +815,11 @@ static void *writer_main(void *arg)
 		const double t1 = now();
 		for (int t = 0; t < nt; t++) { if (t) pthread_join(th[t], NULL); fwrite(job[t].buf, 1, job[t].len, a->out); a->tr.out_bytes += job[t].len; a->n_status += job[t].n_status; }
 		a->tr.fmt_s += t1 - t0; a->tr.write_s += now() - t1;
+		if (a->rep && b->n) {
+			dsb_result res; res.reads = b->rr; res.hits = b->hits; res.n_hits = b->n_hits;
+			int rc = dsb_report_add(a->rep, a->idx, b->reads, &res, b->taxa, b->n, a->o.max_sec_N);
+			if (rc) { fprintf(stderr, "[dsb_report_add] %s\n", dsb_strerror(rc)); exit(1); }
+		}
 		if (a->trace) fprintf(stderr, "[writer] batch %ld written at %.3f s\n", b->seqno, now() - a->t0);
 		a->total += b->n;
 		next++;
@@ -829,7 +843,10 @@ static void usage(void)
 	fprintf(stderr, "    -g, LIST        GPU device ids, e.g. 0 or 0,1,2,3 or all [0]\n");
 	fprintf(stderr, "    -f, STR         output format, one of:\n                    - SAM: SAM-like results without SEQ and QUAL and header, default\n");
 	fprintf(stderr, "                    - SAM_FULL: SAM-like results with SEQ and QUAL\n");
-	fprintf(stderr, "                    - DES: smaller format\n                    - DES_FULL: all results are showed, ignore '-r' opinion\n\n");
+	fprintf(stderr, "                    - DES: smaller format\n                    - DES_FULL: all results are showed, ignore '-r' opinion\n");
+	fprintf(stderr, "    --taxonomy FILE  nodes.dmp of the taxids in the reference names (needed by the two options below)\n");
+	fprintf(stderr, "    --report FILE    write the read counts per taxon of the run into FILE, as `analysis ana_meta` prints them for its SAM\n");
+	fprintf(stderr, "    --report-base FILE  the same for `analysis ana_meta_base` (bases weighted by MAPQ)\n\n");
 }
 
 static double now(void) { struct timeval tv; gettimeofday(&tv, NULL); return tv.tv_sec + tv.tv_usec * 1e-6; }
@@ -886,8 +903,12 @@ static int classify_main(int argc, char **argv)
 	static app_t a; int c;
 	int dev[MAX_DEV], n_dev = 1; dev[0] = 0;
 	a.o.L_min_matching = 170; a.o.min_score = 64; a.o.max_sec_N = 5; a.o.n_slots = 0; a.out = stdout;
-	while ((c = getopt(argc, argv, "ht:l:r:f:o:s:g:")) >= 0) {
+	static const struct option long_opts[] = {{"taxonomy", required_argument, NULL, 1}, {"report", required_argument, NULL, 2}, {"report-base", required_argument, NULL, 3}, {NULL, 0, NULL, 0}};
+	const char *tax_path = NULL, *rep_path[2] = {NULL, NULL};
+	while ((c = getopt_long(argc, argv, "ht:l:r:f:o:s:g:", long_opts, NULL)) >= 0) {
 		if (c == 'h') { usage(); return 0; }
+		else if (c == 1) tax_path = optarg;
+		else if (c == 2 || c == 3) rep_path[c - 2] = optarg;
 		else if (c == 't') { /* thread count: accepted for compatibility, unused */ }
 		else if (c == 'l') a.o.L_min_matching = atoi(optarg);
 		else if (c == 'r') a.o.max_sec_N = atoi(optarg);
@@ -920,6 +941,15 @@ static int classify_main(int argc, char **argv)
 		   writer would lose its reader again and die) */
 		if (strcmp(argv[i], "-") != 0 && access(argv[i], R_OK) != 0) { fprintf(stderr, "[xzopen] fail to open file '%s'\n", argv[i]); exit(1); }
 	}
+	if ((rep_path[0] || rep_path[1]) && !tax_path) die("[classify] --report and --report-base need --taxonomy nodes.dmp");
+	if (tax_path) {
+		int rt = dsb_taxonomy_load(tax_path, &a.tx);
+		if (rt == DSB_EIO) { fprintf(stderr, "[classify] fail to open file '%s'\n", tax_path); exit(1); }
+		if (rt) { fprintf(stderr, "[classify] --taxonomy %s: %s\n", tax_path, rt == DSB_EINVAL ? "a chain of parent links runs in a cycle" : dsb_strerror(rt)); exit(1); }
+		for (int k = 0; k < 2; k++)
+			if (rep_path[k] && !(a.rep_out[k] = fopen(rep_path[k], "w"))) { fprintf(stderr, "[xopen] fail to open file '%s'\n", rep_path[k]); exit(1); }
+		if ((rep_path[0] || rep_path[1]) && dsb_report_create(a.tx, &a.rep)) die("[classify] out of memory");
+	}
 	app_defaults(&a);
 	setvbuf(a.out, NULL, _IOFBF, 8 << 20);
 
@@ -934,6 +964,7 @@ static int classify_main(int argc, char **argv)
 	rc = dsb_ctx_create_multi(a.idx, ids, a.n_ctx, &a.o, &a.multi);
 	if (rc) { fprintf(stderr, "\n[dsb_ctx_create] %s\n", dsb_strerror(rc)); exit(1); }
 	for (int k = 0; k < a.n_ctx; k++) a.ctx[k] = dsb_multi_ctx(a.multi, k);
+	if (a.rep && (rc = dsb_multi_set_taxonomy(a.multi, a.tx))) { fprintf(stderr, "\n[dsb_ctx_set_taxonomy] %s\n", dsb_strerror(rc)); exit(1); }
 	double t0 = now(), cpu0 = cputime(); a.t0 = t0;
 	a.thr0 = a.trace ? throttled_usec() : -1;
 	fprintf(stderr, "Start classify\n");
@@ -954,7 +985,16 @@ static int classify_main(int argc, char **argv)
 	if (a.n_status) fprintf(stderr, "[classify] %lu read(s) exceeded a device capacity even in the second run; their records may be incomplete\n", a.n_status);
 	if (a.trace) trace_summary(&a, sec);
 	if (a.out != stdout) fclose(a.out); else fflush(stdout);
+	for (int k = 0; k < 2; k++) {
+		if (!a.rep_out[k]) continue;
+		size_t cap = 1 << 16; char *buf = NULL; long w;
+		do { cap *= 4; buf = xrealloc(buf, cap); w = dsb_report_format(a.rep, k, buf, cap); } while (w < 0);
+		if (fwrite(buf, 1, (size_t)w, a.rep_out[k]) != (size_t)w || fclose(a.rep_out[k])) die("[classify] cannot write the report");
+		free(buf);
+	}
+	dsb_report_destroy(a.rep);
 	dsb_multi_destroy(a.multi);
+	dsb_taxonomy_close(a.tx);
 	dsb_index_close(a.idx);
 	return a.n_status ? 1 : 0;
 }

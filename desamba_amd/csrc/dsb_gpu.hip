@@ -28,6 +28,8 @@
 #undef DSB_GROUP
 #undef DSB_NS
 #include "dsb_host.h"
+#include "dsb_sam_fields.h"
+#include "dsb_taxonomy.h"
 
 #define HIPCHK(e) do { hipError_t _e = (e); if (_e != hipSuccess) { fprintf(stderr, "[desamba_amd] HIP error %s at %s:%d\n", hipGetErrorString(_e), __FILE__, __LINE__); return DSB_ENODEV; } } while (0)
 
@@ -719,6 +721,54 @@ __global__ void k_collect_retry(const DsbReadOut *rout, uint32_t n, uint32_t *li
 	(void)clear_n;
 }
 
+// One lane per read, after the batch's last classify work: the taxon of the read's own records as `deSAMBA analysis`
+// reads them back from the SAM (dsb_taxonomy.cpp, ana_get_tid src/analysis.c:1271-1330).  The records are the ones
+// dsb_format_sam prints -- the primary, the supplementary ones, the secondary ones up to max_sec -- taken where the classify
+// kernels left them (DsbReadOut / DsbHitOut); MAPQ and the CIGAR's length come from dsb_sam_fields.h, as the writer's do.
+// Each parent walk stops after `bound` steps (the deepest chain of the taxonomy + 2: the loader rejects cycles); a read the
+// host must walk itself is flagged DSB_TAXON_HOST: a first record with score 0 or a taxid above max_tid (the read ends
+// there and its other records become reads of their own), a reference whose name does not come back from the SAM as it
+// is, or a walk that ran out of steps.
+__global__ void __launch_bounds__(256) k_read_taxon(const DsbReadOut *__restrict__ rout, const DsbHitOut *__restrict__ hout, const unsigned int *__restrict__ counters,
+                                                    uint32_t cap_hout, const DsbReadDesc *__restrict__ rd, uint32_t n, const uint32_t *__restrict__ parent,
+                                                    const uint32_t *__restrict__ ref_tid, uint32_t n_ref, uint32_t max_tid, uint32_t bound, int max_sec, dsb_read_taxon *__restrict__ out)
+{
+	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= n) return;
+	const uint32_t nh = counters[1] < cap_hout ? counters[1] : cap_hout;
+	const DsbReadOut r = rout[i];
+	dsb_read_taxon t; t.taxid = 0; t.score = 0; t.len = 0; t.mapq = 0; t.flags = 0; t.pad = 0;
+	const uint32_t nrec = (uint64_t)r.first + r.n > nh ? 0u : r.n;   // (what dsb_batch_fetch hands out)
+	if (nrec) {
+		const dsb_hit *h = reinterpret_cast<const dsb_hit *>(hout + r.first);
+		const uint32_t read_l = rd[i].len;
+		const uint32_t t0 = h[0].ref_ID < n_ref ? ref_tid[h[0].ref_ID] : DSB_TID_NONE;
+		t.flags = DSB_TAXON_CLASSIFIED;
+		t.score = h[0].sum_score; t.len = dsb_sam_cigar_len(h, read_l, false); t.mapq = (uint8_t)dsb_sam_mapq_pri(h, nrec);
+		if (t0 == DSB_TID_NONE || t0 > max_tid || t.score == 0) { t.flags |= DSB_TAXON_HOST; t.taxid = t0 <= max_tid ? t0 : 0; }
+		else {
+			uint32_t tid = t0;
+			for (int pass = 0; pass <= 1 && !(t.flags & DSB_TAXON_HOST); pass++)
+				for (uint32_t k = 1; k < nrec; k++) {
+					const dsb_hit *c = h + k;
+					if (!dsb_sam_shown(c, pass, max_sec)) continue;
+					const uint32_t rt = c->ref_ID < n_ref ? ref_tid[c->ref_ID] : DSB_TID_NONE;
+					if (rt == DSB_TID_NONE) { t.flags |= DSB_TAXON_HOST; break; }
+					if (c->sum_score != t.score || rt > max_tid) continue;
+					uint32_t p = rt, steps = 0;
+					for (; steps < bound; steps++) {                                // is rt at or below the taxon held?
+						if (p == tid) { tid = rt; break; }
+						if (p < 1 || p == DSB_TID_NONE || p > max_tid) break;
+						p = parent[p];
+					}
+					if (steps == bound) { t.flags |= DSB_TAXON_HOST; break; }
+				}
+			t.taxid = tid;
+		}
+	}
+	out[i] = t;
+}
+
 // ================================== host side ====================================================
 #include <mutex>
 #include <thread>
@@ -904,6 +954,10 @@ struct dsb_ctx {
 	uint32_t *dbg_host = nullptr, *dbg_dev = nullptr;
 	std::vector<UpStage> up; size_t up_chunk = 0;     // pinned staging of dsb_batch_upload (upload_gather)
 	dsb_opts opts;
+	// taxonomy (dsb_ctx_set_taxonomy): the parent table and each reference's taxid in HBM, one k_read_taxon launch per batch
+	const dsb_taxonomy *tx = nullptr; uint32_t *d_parent = nullptr, *d_ref_tid = nullptr;
+	dsb_read_taxon *d_taxa = nullptr; size_t cap_taxa = 0; std::vector<dsb_read_taxon> h_taxa;
+	bool taxa_run = false, taxa_done = false;     // k_read_taxon ran for the batch of the current slot / its records are fetched and completed
 	dsb_ctx() { memset(&dx, 0, sizeof dx); memset(&arena, 0, sizeof arena); memset(&arena_big, 0, sizeof arena_big); memset(&timing, 0, sizeof timing); memset(&opts, 0, sizeof opts); }
 };
 
@@ -943,6 +997,7 @@ extern "C" void dsb_ctx_destroy(dsb_ctx *c)
 	if (c->stream2) hipStreamSynchronize(c->stream2);
 	for (InSlot &s : c->in) { hipFree(s.d_rd); hipFree(s.d_ascii); hipFree(s.d_scan_order); }
 	hipFree(c->d_wd); hipFree(c->d_bin); hipFree(c->d_pk); hipFree(c->d_bits);
+	hipFree(c->d_parent); hipFree(c->d_ref_tid); hipFree(c->d_taxa);
 	hipFree(c->d_rout); hipFree(c->d_hout); hipFree(c->d_counters); hipFree(c->arena.base); hipFree(c->arena_big.base); hipFree(c->d_score); hipFree(c->d_order); hipFree(c->d_heavy); hipFree(c->d_seeds); hipFree(c->d_sinfo); hipFree(c->syn0); hipFree(c->syn1);
 	if (c->dbg_host) hipHostFree(c->dbg_host);
 	for (UpStage &u : c->up) { if (u.st) { hipStreamSynchronize(u.st); hipStreamDestroy(u.st); } for (int k = 0; k < 2; k++) { if (u.ev[k]) hipEventDestroy(u.ev[k]); if (u.buf[k]) hipHostFree(u.buf[k]); } }
@@ -1494,6 +1549,7 @@ static int batch_run_locked(dsb_ctx *c, std::unique_lock<std::mutex> *turn)
 	size_t n = s.n_reads;
 	memset(&c->timing, 0, sizeof c->timing);
 	c->timing.upload_bytes = s.upload_bytes;
+	c->taxa_run = c->tx != nullptr && n == 0; c->taxa_done = false;
 	if (n == 0) return DSB_OK;
 	HIPCHK(hipMemsetAsync(c->d_counters, 0, 256, c->stream));
 	HIPCHK(hipEventRecord(c->ev[0], c->stream));
@@ -1653,6 +1709,15 @@ static int batch_run_locked(dsb_ctx *c, std::unique_lock<std::mutex> *turn)
 			c->timing.n_regrow = n3;
 		}
 	}
+	if (c->tx) {
+		// the per-read taxa: after every classify launch of the batch (the second runs and the run after a regrown hit buffer included)
+		if (grow(&c->d_taxa, &c->cap_taxa, n)) return DSB_ENOMEM;
+		const uint32_t bound = c->tx->max_depth + 2;
+		hipLaunchKernelGGL(k_read_taxon, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const DsbReadOut *)c->d_rout, (const DsbHitOut *)c->d_hout,
+		                   (const unsigned int *)c->d_counters, (uint32_t)c->cap_hout, (const DsbReadDesc *)s.d_rd, (uint32_t)n, (const uint32_t *)c->d_parent,
+		                   (const uint32_t *)c->d_ref_tid, (uint32_t)dsb_index_n_ref(c->idx), c->tx->max_tid, bound, c->opts.max_sec_N, c->d_taxa);
+		c->taxa_run = true;
+	}
 	if (dbg) {
 		static const char *nm[10] = {"seed_vector", "fast_classify", "resolve_tree", "slow+resolve", "hash_build", "sdp_middle", "sdp_right", "sdp_left", "sort/filter", "primary"};
 		double tot[10] = {0}, all = 0; unsigned sl = (unsigned)c->n_slots; if (sl > n) sl = (unsigned)n;
@@ -1722,7 +1787,10 @@ extern "C" int dsb_batch_fetch(dsb_ctx *c, dsb_result *out)
 	}
 	const size_t nh = cnt[1] < c->cap_hout ? cnt[1] : c->cap_hout;
 	c->h_hout.resize(nh);
-	if (nh) { HIPCHK(hipMemcpyAsync(c->h_hout.data(), c->d_hout, nh * sizeof(DsbHitOut), hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream)); }
+	if (nh) HIPCHK(hipMemcpyAsync(c->h_hout.data(), c->d_hout, nh * sizeof(DsbHitOut), hipMemcpyDeviceToHost, c->stream));
+	c->taxa_done = false;
+	if (c->taxa_run) { c->h_taxa.resize(n); if (n) HIPCHK(hipMemcpyAsync(c->h_taxa.data(), c->d_taxa, n * sizeof(dsb_read_taxon), hipMemcpyDeviceToHost, c->stream)); }
+	if (nh || (c->taxa_run && n)) HIPCHK(hipStreamSynchronize(c->stream));
 	// The hits of a read lie together in the device's hit buffer, in the order the reads finished; dsb_hit has the
 	// layout of the device record, so nothing is repacked: the per-read `first` points into the buffer as fetched.
 	static_assert(sizeof(DsbHitOut) == sizeof(dsb_hit), "dsb_hit mirrors DsbHitOut");
@@ -1736,7 +1804,48 @@ extern "C" int dsb_batch_fetch(dsb_ctx *c, dsb_result *out)
 		if ((size_t)r.first + r.n > nh) { o.n = 0; o.first = 0; }
 	}
 	out->reads = c->res_reads.data(); out->hits = reinterpret_cast<const dsb_hit *>(c->h_hout.data()); out->n_hits = nh;
+	if (c->taxa_run) {
+		// the reads the device left to the host get their taxon here (rare: see k_read_taxon)
+		const dsb_hit *H = reinterpret_cast<const dsb_hit *>(c->h_hout.data());
+		const InSlot &s = c->in[c->cur];
+		for (size_t i = 0; i < n; i++)
+			if (c->h_taxa[i].flags & DSB_TAXON_HOST)
+				c->h_taxa[i].taxid = dsb_read_taxid_host(c->tx, c->idx, s.h_rd[i].len, H + c->res_reads[i].first, c->res_reads[i].n, c->opts.max_sec_N);
+		c->taxa_done = true;
+	}
 	return worst;
+}
+
+// ---- taxonomy ----
+extern "C" int dsb_ctx_set_taxonomy(dsb_ctx *c, const dsb_taxonomy *tx)
+{
+	if (!c) return DSB_EINVAL;
+	if (tx && !tx->acyclic) return DSB_EINVAL;                 // (dsb_taxonomy_load_any: the device's walks need the bound)
+	HIPCHK(hipSetDevice(c->device));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	hipFree(c->d_parent); hipFree(c->d_ref_tid); c->d_parent = c->d_ref_tid = nullptr;
+	c->tx = nullptr; c->taxa_run = c->taxa_done = false;
+	if (!tx) { hipFree(c->d_taxa); c->d_taxa = nullptr; c->cap_taxa = 0; return DSB_OK; }
+	const size_t n_ref = (size_t)dsb_index_n_ref(c->idx);
+	std::vector<uint32_t> rt(n_ref ? n_ref : 1);
+	for (size_t r = 0; r < n_ref; r++) rt[r] = dsb_ref_taxid(dsb_index_ref_name(c->idx, (uint32_t)r));
+	if (hipMalloc((void **)&c->d_parent, ((size_t)tx->max_tid + 1) * 4) != hipSuccess || hipMalloc((void **)&c->d_ref_tid, rt.size() * 4) != hipSuccess) {
+		hipFree(c->d_parent); c->d_parent = nullptr; return DSB_ENOMEM;
+	}
+	HIPCHK(hipMemcpy(c->d_parent, tx->parent, ((size_t)tx->max_tid + 1) * 4, hipMemcpyHostToDevice));
+	HIPCHK(hipMemcpy(c->d_ref_tid, rt.data(), rt.size() * 4, hipMemcpyHostToDevice));
+	// the per-read records for the batches the ctx was sized for now, not inside a batch (grow() waits for the device)
+	if (grow(&c->d_taxa, &c->cap_taxa, std::max(c->cap_rout, (size_t)c->opts.max_batch_reads))) return DSB_ENOMEM;
+	c->tx = tx;
+	return DSB_OK;
+}
+
+extern "C" int dsb_batch_taxa(dsb_ctx *c, const dsb_read_taxon **out)
+{
+	if (!c || !out || !c->tx || !c->taxa_run) return DSB_EINVAL;
+	if (!c->taxa_done) { dsb_result r; int rc = dsb_batch_fetch(c, &r); if (rc && rc != DSB_ECAP) return rc; }
+	*out = c->h_taxa.data();
+	return DSB_OK;
 }
 
 extern "C" int dsb_classify_batch(dsb_ctx *c, const dsb_read *reads, size_t n, dsb_result *out)
@@ -1851,6 +1960,7 @@ struct dsb_multi {
 	uint32_t chunk_reads_env = 0;                 // DSB_SHARD_CHUNK_READS, read when the contexts are made (tests: many small chunks)
 	std::vector<uint32_t> last_calls;             // dsb_classify_batch calls each context made in the last dsb_multi_classify_batch
 	std::vector<dsb_read_result> reads; std::vector<dsb_hit> hits;
+	const dsb_taxonomy *tx = nullptr; std::vector<dsb_read_taxon> taxa; bool taxa_ok = false;   // dsb_multi_set_taxonomy / dsb_multi_taxa
 };
 
 extern "C" void dsb_multi_destroy(dsb_multi *m)
@@ -1905,6 +2015,7 @@ extern "C" int dsb_multi_classify_batch(dsb_multi *m, const dsb_read *reads, siz
 	std::vector<dsb_chunk> plan(nc ? nc : 1);
 	dsb_shard_plan(len.data(), n, W, chunk_bases, chunk_reads, plan.data(), nc, &nc);
 	m->reads.assign(n, dsb_read_result());
+	m->taxa_ok = false; if (m->tx) m->taxa.assign(n, dsb_read_taxon());
 	std::vector<std::vector<dsb_hit>> chunk_hits(nc);
 	std::vector<int> rcs(W, DSB_OK);
 	const uint32_t hist0 = m->hist;
@@ -1922,6 +2033,11 @@ extern "C" int dsb_multi_classify_batch(dsb_multi *m, const dsb_read *reads, siz
 			m->last_calls[(size_t)w]++;
 			if (rc && rc != DSB_ECAP) { rcs[w] = rc; return; }
 			if (rc == DSB_ECAP) rcs[w] = DSB_ECAP;
+			if (m->tx) {
+				const dsb_read_taxon *t = nullptr;
+				if ((rc = dsb_batch_taxa(c, &t))) { rcs[w] = rc; return; }
+				std::copy(t, t + (ch.end - ch.start), m->taxa.begin() + (ptrdiff_t)ch.start);
+			}
 			std::vector<dsb_hit> &H = chunk_hits[k];
 			for (uint64_t i = ch.start; i < ch.end; i++) {
 				dsb_read_result rr = r.reads[i - ch.start];
@@ -1946,6 +2062,22 @@ extern "C" int dsb_multi_classify_batch(dsb_multi *m, const dsb_read *reads, siz
 	}
 	for (size_t i = 0; i < n; i++) if (len[i] > m->hist) m->hist = len[i];
 	out->reads = m->reads.data(); out->hits = m->hits.data(); out->n_hits = m->hits.size();
+	m->taxa_ok = m->tx != nullptr;
 	return worst;
+}
+
+extern "C" int dsb_multi_set_taxonomy(dsb_multi *m, const dsb_taxonomy *tx)
+{
+	if (!m) return DSB_EINVAL;
+	m->tx = nullptr; m->taxa_ok = false;
+	for (dsb_ctx *c : m->ctx) { int rc = dsb_ctx_set_taxonomy(c, tx); if (rc) { for (dsb_ctx *d : m->ctx) dsb_ctx_set_taxonomy(d, nullptr); return rc; } }
+	m->tx = tx;
+	return DSB_OK;
+}
+extern "C" int dsb_multi_taxa(dsb_multi *m, const dsb_read_taxon **out)
+{
+	if (!m || !out || !m->tx || !m->taxa_ok) return DSB_EINVAL;
+	*out = m->taxa.data();
+	return DSB_OK;
 }
 #endif  // DSB_UNIT_HOST

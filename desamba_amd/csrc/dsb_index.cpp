@@ -9,6 +9,7 @@
 #include <sched.h>
 #include <vector>
 #include "dsb_host.h"
+#include "dsb_sam_fields.h"
 
 struct dsb_index { DsbHostIndex h; };
 
@@ -273,20 +274,21 @@ extern "C" long dsb_format_sam(const dsb_index *x, const dsb_read *rd_, const ds
 #define EMIT(...) do { w = snprintf(buf + o, cap > o ? cap - o : 0, __VA_ARGS__); if (w < 0 || (size_t)w >= (cap > o ? cap - o : 0)) return -1; o += (size_t)w; } while (0)
 	if (n == 0) { EMIT("%s\t4\t*\t0\t0\t*\t*\t0\t0\t%.*s\t%.*s\t\n", rd_->name, seq_n, seq_s, qual_n, qual_s); return (long)o; }
 	uint32_t read_l = rd_->len;
-	int flag = h[0].direction ? 0 : 0x10, mapQ_PRI;
-	if (n == 1 || (h[0].sum_score - h[1].sum_score > 5)) mapQ_PRI = 30;
-	else mapQ_PRI = (h[0].sum_score - h[1].sum_score) << 2;
+	int flag = h[0].direction ? 0 : 0x10, mapQ_PRI = dsb_sam_mapq_pri(h, n), cg[3];
+	dsb_sam_cigar(h, read_l, cg);
 	EMIT("%s\t%d\t%s\t%d\t%d\t%dS%dM%dS\t*\t0\t0\t%.*s\t%.*s\tAS:i:%d\t\n", rd_->name, flag, dsb_index_ref_name(x, h[0].ref_ID),
-	     h[0].t_st, mapQ_PRI, h[0].q_st, h[0].q_ed - h[0].q_st, read_l - h[0].q_ed, seq_n, seq_s, qual_n, qual_s, h[0].sum_score);
+	     h[0].t_st, mapQ_PRI, cg[0], cg[1], cg[2], seq_n, seq_s, qual_n, qual_s, h[0].sum_score);
 	for (int loop = 0; loop <= 1; loop++)
 		for (uint32_t i = 1; i < n; i++) {
 			const dsb_hit *c = h + i;
-			int show = 0, fl = c->direction ? 0 : 0x10, mapQ = 0;
-			if (loop == 0 && c->pri_index == 0) { show = 1; fl += 0x800; mapQ = mapQ_PRI < 30 ? mapQ_PRI : 30; }
-			else if (loop == 1 && c->pri_index > 0 && c->pri_index <= max_sec) { show = 1; fl += 0x100; }
-			if (show)
+			int show = dsb_sam_shown(c, loop, max_sec), fl = c->direction ? 0 : 0x10, mapQ = 0;
+			if (show && loop == 0) { fl += 0x800; mapQ = mapQ_PRI < 30 ? mapQ_PRI : 30; }
+			else if (show) fl += 0x100;
+			if (show) {
+				dsb_sam_cigar(c, read_l, cg);
 				EMIT("%s\t%d\t%s\t%d\t%d\t%d%c%dM%d%c\t*\t0\t0\t*\t*\tAS:i:%d\t\n", rd_->name, fl, dsb_index_ref_name(x, c->ref_ID), c->t_st, mapQ,
-				     c->q_st, loop == 0 ? 'H' : 'S', c->q_ed - c->q_st, read_l - c->q_ed, loop == 0 ? 'H' : 'S', c->sum_score);
+				     cg[0], loop == 0 ? 'H' : 'S', cg[1], cg[2], loop == 0 ? 'H' : 'S', c->sum_score);
+			}
 		}
 #undef EMIT
 	return (long)o;

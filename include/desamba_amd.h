@@ -219,6 +219,62 @@ long dsb_format_sam(const dsb_index *idx, const dsb_read *read, const dsb_hit *h
 long dsb_format_des(const dsb_index *idx, const dsb_read *read, const dsb_read_result *rr, const dsb_hit *hits,
                     int max_sec_N, int full, char *buf, size_t cap);
 
+/* ---- taxonomy: per-read taxa on the GPU and the abundance report of `deSAMBA analysis ana_meta[_base]` in the run itself.
+ * The report a run accumulates equals what `deSAMBA analysis ana_meta` (by_base = 0) or `ana_meta_base` (by_base = 1) prints
+ * for the SAM dsb_format_sam writes for the same reads, hits and max_sec_N (src/analysis.c:1271-1330,1831-1855), without its
+ * leading "Current read <SAM>.temp\t<SAM>.temp\t"; a report that saw no read is empty. */
+typedef struct dsb_taxonomy dsb_taxonomy;   /* nodes.dmp: the parent of every taxid up to max_tid */
+typedef struct dsb_report dsb_report;       /* read counts / bases per taxid of a run, in input order */
+
+/* load nodes.dmp as analysis does: the table ends at max_tid = (taxid of the LAST line) + 1 000 000.  DSB_EIO: cannot be
+ * read; DSB_EINVAL: a chain of parent links runs in a cycle (the walks on the device are bounded by the deepest chain, which
+ * the loader records).  dsb_taxonomy_load_any accepts cycles, as analysis always has: such a taxonomy serves a report
+ * (whose walks then loop where analysis loops) but not dsb_ctx_set_taxonomy. */
+int      dsb_taxonomy_load(const char *nodes_dmp, dsb_taxonomy **tx);
+int      dsb_taxonomy_load_any(const char *nodes_dmp, dsb_taxonomy **tx);
+void     dsb_taxonomy_close(dsb_taxonomy *tx);
+uint32_t dsb_taxonomy_max_tid(const dsb_taxonomy *tx);
+uint32_t dsb_taxonomy_parent(const dsb_taxonomy *tx, uint32_t taxid);   /* 0xffffffff: not in the file (or above max_tid) */
+
+/* one read's taxon as k_read_taxon finds it.  taxid is the walk over THIS read's own records alone, in SAM order
+ * (primary, supplementary, secondary up to max_sec_N): the primary's taxid (the second '|' field of the reference name),
+ * moved to a later record's taxid when that record has the same AS and its taxid descends from the one held; 0 =
+ * unclassified or not in the taxonomy.  The rules that join reads -- adjacent reads of one name are one read, a read
+ * whose first AS is 0 ends at once, the last read of a run counts only in total_read_number -- belong to dsb_report. */
+typedef struct {
+	uint32_t taxid;
+	uint32_t score;       /* AS of the first record */
+	uint32_t len;         /* read length as analysis counts the first record's CIGAR */
+	uint8_t  mapq;        /* MAPQ of the first record */
+	uint8_t  flags;       /* DSB_TAXON_* */
+	uint16_t pad;
+} dsb_read_taxon;
+#define DSB_TAXON_CLASSIFIED 1   /* the read has records (hits) */
+#define DSB_TAXON_HOST       2   /* the device left the read to the host: first AS 0 or taxid above max_tid, an odd reference
+                                    name, or a walk deeper than the bound.  taxid is final all the same (completed on the host). */
+
+/* attach a taxonomy to a ctx (NULL detaches): its parent table and each reference's taxid are staged in HBM, and every batch
+ * from then on ends with k_read_taxon.  The taxonomy must outlive the attachment.  Without one nothing is launched. */
+int  dsb_ctx_set_taxonomy(dsb_ctx *ctx, const dsb_taxonomy *tx);
+int  dsb_multi_set_taxonomy(dsb_multi *m, const dsb_taxonomy *tx);
+/* the taxa of the last batch (n reads, valid until the next batch); DSB_EINVAL when no taxonomy is attached */
+int  dsb_batch_taxa(dsb_ctx *ctx, const dsb_read_taxon **out);
+/* the same for the last dsb_multi_classify_batch, in input order */
+int  dsb_multi_taxa(dsb_multi *m, const dsb_read_taxon **out);
+
+/* The report.  dsb_report_add feeds n reads in input order (res->reads[i], its hits res->hits + first): a read with a
+ * device record (taxa[i], DSB_TAXON_HOST clear) is counted from it; the others, and a read whose name is that of the read
+ * before it, are walked on the host over the records dsb_format_sam prints for it.  taxa may be NULL: every read is then
+ * walked on the host.  A classified read stays open until a read of another name arrives.
+ * dsb_report_add_sam feeds SAM text (the `@` lines at the top skipped), as `analysis` reads it.
+ * dsb_report_format: same return convention as dsb_format_sam.  by_base = 0: ana_meta, 1: ana_meta_base. */
+int  dsb_report_create(const dsb_taxonomy *tx, dsb_report **rep);
+int  dsb_report_add(dsb_report *rep, const dsb_index *idx, const dsb_read *reads, const dsb_result *res, const dsb_read_taxon *taxa,
+                    size_t n, int max_sec_N);
+int  dsb_report_add_sam(dsb_report *rep, const char *text, size_t len);
+long dsb_report_format(const dsb_report *rep, int by_base, char *buf, size_t cap);
+void dsb_report_destroy(dsb_report *rep);
+
 const char *dsb_strerror(int code);
 const char *dsb_version(void);
 
