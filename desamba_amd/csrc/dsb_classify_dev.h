@@ -3522,12 +3522,14 @@ DN void fast_classify_lane(WCtxL &w, bool valid, uint8_t *bin, uint32_t read_len
 	wave_sync();
 }
 
+// (have_anchors: w.anc holds the read's anchors already; anc_lsteps = the loop steps their walk spent, charged to the read's budget)
 template <bool MW>
-DN uint32_t classify_read(WCtxL &w, const uint64_t *bitsF, const uint64_t *bitsR, const bool have_anchors = false)
+DN uint32_t classify_read(WCtxL &w, const uint64_t *bitsF, const uint64_t *bitsR, const bool have_anchors = false, const uint32_t anc_lsteps = 0)
 {
 	uint32_t read_len = w.L;
 	if (!have_anchors) w.n_anc = 0;
 	w.n_hit = 0; w.n_sms = 0; w.steps = 0; w.lsteps = 0; w.dp_preds = 0; w.boosted = 0; w.k.uni = 1;
+	if (have_anchors) w.lsteps = anc_lsteps;
 	uint32_t fast = 1;
 	if (read_len < 40) return fast;
 	SDirL *sd = w.sd;

@@ -76,6 +76,9 @@ struct DsbScHash { uint16_t next; uint16_t seed_ID; };                   // bit 
 
 struct DsbHitOut { uint32_t ref_ID, t_st, t_ed, q_st, q_ed, sum_score, indel; uint8_t direction, primary, pri_index, pad; };
 struct DsbReadOut { uint32_t first, n; int32_t status; uint32_t fast; uint32_t n_anc, pad; };   // n_anc: cly_r.anchor_v.n at the end (DES header)
+// per read, written by k_anchor (the anchor stage of a batch's main launch): where its anchors lie in the anchor pool, how many,
+// the loop steps the walk spent and whether k_classify takes them (use = 0: it walks the islands itself, as without k_anchor)
+struct DsbAncRec { uint32_t off, n, lsteps, use; };
 
 // ---- arena sizes (per wave slot) ---------------------------------------------------------------
 #define DSB_QPAD_L 64

@@ -49,8 +49,9 @@ struct DsbWordDesc { uint32_t read; uint32_t word; };   // word: bit 31 = strand
 
 // Compilation units.  k_classify inlines every stage function (dsb_wave.h: a callee would save ~64 callee-saved vector registers per call and
 // lane -- 58 GB written per launch in round 3 -- and pin local state in scratch memory), which makes it, its two siblings and k_classify_heavy
-// a minute of compile time EACH.  -DDSB_KUNIT=n compiles this file as one of five units that are built side by side and linked into the
-// library: 0 = the host side and the small kernels (the four big ones only declared), 1 .. 4 = one big kernel each and nothing else.
+// a minute of compile time EACH (k_anchor, which inlines the island walk, less).  -DDSB_KUNIT=n compiles this file as one of six units that are
+// built side by side and linked into the library: 0 = the host side and the small kernels (the five big ones only declared), 1 .. 5 = one big
+// kernel each and nothing else.
 // Without DSB_KUNIT the file is one unit, as before (tools/kernel_resources.sh, experiments).
 #if !defined(DSB_KUNIT)
 #define DSB_UNIT_HAS(n) 1
@@ -458,7 +459,8 @@ struct DsbSlotArena {
 #if DSB_UNIT_HAS(1) || DSB_UNIT_HAS(2) || DSB_UNIT_HAS(3)
 __device__ __forceinline__ void classify_kernel_body(const DsbDevIndex &x, const DsbReadDesc *rd, uint32_t n_fixed, const unsigned int *n_ptr,
         const uint32_t *list, uint8_t *bin, const uint64_t *bits, const DsbSlotArena &ar, unsigned int *work_counter, DsbReadOut *rout,
-        DsbHitOut *hout, unsigned int *hout_counter, uint32_t hout_cap, uint32_t *dbg, uint32_t item_base, uint32_t slot_base, unsigned long long *work_cnt, DsbSeed *seed_blob, const DsbSeedInfo *sinfo, const uint64_t *pk, uint32_t group_mode)
+        DsbHitOut *hout, unsigned int *hout_counter, uint32_t hout_cap, uint32_t *dbg, uint32_t item_base, uint32_t slot_base, unsigned long long *work_cnt, DsbSeed *seed_blob, const DsbSeedInfo *sinfo, const uint64_t *pk, uint32_t group_mode,
+        const DsbAncRec *arec, const DsbAnchor *apool)
 {
 	const int lane = threadIdx.x;
 	const uint32_t slot_id = slot_base + blockIdx.x;            /* arena slot (and debug row) of this wave */
@@ -546,14 +548,23 @@ __device__ __forceinline__ void classify_kernel_body(const DsbDevIndex &x, const
 		w.bin = bin + d.bin_off + DSB_QPAD_L; w.L = d.len; w.status = 0; w.max_read_l = d.hist_max;
 		w.pre_seeds = seed_blob ? seed_blob + d.seed_off : nullptr; w.pre_info = sinfo + r;
 		w.pk[0] = pk + d.pk_off; w.pk[1] = w.pk[0] + ((d.len + 31) / 32 + 1);
+		uint32_t anc_lsteps = 0;
 		if (have_anc) {   /* the anchors lane gl made for this read */
 			const uint32_t na = dsb_g64::dsb_shfl(g_nanc, (int)gl);
 			const DsbAnchor *src = w.lane_anc + (size_t)gl * DSB_LANE_ANC_CAP;
 			for (uint32_t i = lane; i < na; i += 64) w.anc[i] = src[i];
 			w.n_anc = na;
 			dsb_g64::wave_sync();
+		} else if (arec) {   /* the anchors k_anchor made for this read, if it finished them */
+			const DsbAncRec ar_r = arec[r];
+			if (ar_r.use) {
+				const DsbAnchor *src = apool + ar_r.off;
+				for (uint32_t i = lane; i < ar_r.n; i += 64) w.anc[i] = src[i];
+				w.n_anc = ar_r.n; anc_lsteps = ar_r.lsteps; have_anc = true;
+				dsb_g64::wave_sync();
+			}
 		}
-		uint32_t fast = dsb_g64::classify_read<false>(w, bits + d.bit_off, bits + d.bit_off + d.n_words, have_anc);
+		uint32_t fast = dsb_g64::classify_read<false>(w, bits + d.bit_off, bits + d.bit_off + d.n_words, have_anc, anc_lsteps);
 		if (w.boosted) __builtin_amdgcn_s_setprio(0);
 		/* publish the hits of this read (none if it is handed over to k_classify_heavy) */
 		if (w.status & DSB_ST_HEAVY) w.n_hit = 0;
@@ -579,8 +590,8 @@ __device__ __forceinline__ void classify_kernel_body(const DsbDevIndex &x, const
 
 #define DSB_CLASSIFY_ARGS DsbDevIndex x, const DsbReadDesc *rd, uint32_t n_fixed, const unsigned int *n_ptr, const uint32_t *list, uint8_t *bin, const uint64_t *bits, DsbSlotArena ar, \
         unsigned int *work_counter, DsbReadOut *rout, DsbHitOut *hout, unsigned int *hout_counter, uint32_t hout_cap, uint32_t *dbg, uint32_t item_base, uint32_t slot_base, unsigned long long *work_cnt, \
-        DsbSeed *seed_blob, const DsbSeedInfo *sinfo, const uint64_t *pk, uint32_t group_mode
-#define DSB_CLASSIFY_PASS x, rd, n_fixed, n_ptr, list, bin, bits, ar, work_counter, rout, hout, hout_counter, hout_cap, dbg, item_base, slot_base, work_cnt, seed_blob, sinfo, pk, group_mode
+        DsbSeed *seed_blob, const DsbSeedInfo *sinfo, const uint64_t *pk, uint32_t group_mode, const DsbAncRec *arec, const DsbAnchor *apool
+#define DSB_CLASSIFY_PASS x, rd, n_fixed, n_ptr, list, bin, bits, ar, work_counter, rout, hout, hout_counter, hout_cap, dbg, item_base, slot_base, work_cnt, seed_blob, sinfo, pk, group_mode, arec, apool
 #if DSB_UNIT_HAS(1)
 __global__ void __launch_bounds__(64, DSB_WAVES_PER_EU) k_classify(DSB_CLASSIFY_ARGS) { classify_kernel_body(DSB_CLASSIFY_PASS); }
 #else
@@ -597,6 +608,93 @@ __global__ void k_classify_early(DSB_CLASSIFY_ARGS);
 __global__ void __launch_bounds__(64, DSB_WAVES_PER_EU) k_classify_second(DSB_CLASSIFY_ARGS) { classify_kernel_body(DSB_CLASSIFY_PASS); }
 #else
 __global__ void k_classify_second(DSB_CLASSIFY_ARGS);
+#endif
+
+// The anchor stage of the main launch as a kernel of its own (DSB_ANCHOR_KERNEL, on by default): persistent, one read per wavefront in
+// the same LPT order, fast_classify on the read's strand(s) from k_seed_scan's seed lists -- the strand swap and the both-direction rule
+// of classify_read -- and the anchors, in commit order, copied into a per-batch pool; k_classify then starts such a read from them
+// (classify_read with have_anchors).  Its LDS is the context, the index descriptor and the 128-word island histogram, without the
+// 12 KB window table of k_classify; its slots (arena_anc) hold only what the island walk uses.  A read whose walk overflowed the
+// anchor cap or its lane scratch, ran out of its loop budget, or whose anchors do not fit the pool, is marked use = 0 and walked
+// again by k_classify as before; its work is then not counted here (the counters are those of the main launch).
+#ifndef DSB_ANCHOR_WPE
+#define DSB_ANCHOR_WPE 5      /* 96 VGPRs: spills, and still faster than 3 waves without */
+#endif
+#if DSB_UNIT_HAS(5)
+__global__ void __launch_bounds__(64, DSB_ANCHOR_WPE) k_anchor(DsbDevIndex x, const DsbReadDesc *rd, uint32_t n_items, uint32_t item_base, const uint32_t *list,
+        uint8_t *bin, DsbSlotArena ar, unsigned int *work_counter, DsbSeed *seed_blob, const DsbSeedInfo *sinfo, DsbAncRec *arec, DsbAnchor *apool,
+        unsigned int *pool_counter, uint32_t pool_cap, unsigned long long *work_cnt)
+{
+	const int lane = threadIdx.x;
+	uint8_t *slot = ar.base + (size_t)blockIdx.x * ar.stride;
+	__shared__ DsbDevIndex sx;
+	__shared__ __attribute__((aligned(16))) uint32_t lds_hist[128];   /* fast_classify's island histogram (w.wtab) */
+	__shared__ uint32_t lds_red[2];
+	__shared__ unsigned int s_word;
+	__shared__ uint32_t lds_cnt[4];
+	if (lane < 4) lds_cnt[lane] = 0;
+	if (lane == 0) sx = x;
+	__syncthreads();
+	__shared__ dsb_g64::WCtx s_w;
+	dsb_g64::WCtxL &w = *(dsb_g64::WCtxL *)&s_w;
+	w.red = lds_red; w.k.c = (dsb_g64::lds_u32 *)lds_cnt; w.k.uni = 1;
+	w.x = (dsb_g64::DsbXP)&sx; w.dbg = nullptr; w.wtab = lds_hist; w.mw = nullptr; w.n_waves = 1;
+	w.anc = (DsbAnchor *)(slot + ar.off_anc);
+	w.spset = (uint64_t *)(slot + ar.off_spset);
+	w.sortidx = (uint32_t *)(slot + ar.off_sortidx);
+	w.lane_anc = (DsbAnchor *)(slot + ar.off_lane_anc); w.lane_spset = (uint64_t *)(slot + ar.off_lane_sp);
+	w.top_idx = (uint32_t *)(slot + ar.off_top); w.round_info = (uint32_t *)(slot + ar.off_round);
+	w.anc_cap = ar.anc_cap; w.anc_cap_main = ar.anc_cap; w.step_limit = x.step_limit; w.sp_gen = 0;
+	for (uint32_t i = lane; i < 64u * DSB_SPHASH; i += 64) w.lane_spset[i] = 0;
+	for (uint32_t i = lane; i < DSB_SPHASH; i += 64) w.spset[i] = 0;
+	__syncthreads();
+	for (;;) {
+		if (lane == 0) s_word = atomicAdd(work_counter, 1u);
+		__syncthreads();
+		const unsigned int k = s_word + item_base;
+		__syncthreads();
+		if (k >= n_items) {
+			if (lane < 4 && lds_cnt[lane]) atomicAdd(work_cnt + lane, (unsigned long long)lds_cnt[lane]);
+			break;
+		}
+		const unsigned int r = list ? list[k] : k;
+		const DsbReadDesc d = rd[r];
+		DsbAncRec rec = {0u, 0u, 0u, 0u};
+		if (d.len >= 40) {
+			const uint32_t cnt0 = lane < 4 ? lds_cnt[lane] : 0u;
+			w.bin = bin + d.bin_off + DSB_QPAD_L; w.L = d.len; w.status = 0; w.n_anc = 0; w.steps = 0; w.lsteps = 0;
+			const DsbSeedInfo si = sinfo[r];
+			dsb_g64::SDirL *sd = w.sd;
+			DsbSeed *sv = seed_blob + d.seed_off;
+			dsb_g64::sdir_set(sd, sv, si.n_seed[0], w.bin, nullptr, D_FORWARD, si.total[0]);
+			dsb_g64::sdir_set(sd + 1, sv + (d.len >> 2), si.n_seed[1], w.bin + d.len, nullptr, D_REVERSE, si.total[1]);
+			if (sd[0].total_score < sd[1].total_score) dsb_g64::sdir_swap(sd, sd + 1);
+			const bool both_direction = ((sd[0].total_score - sd[1].total_score) <= (sd[0].total_score >> 3));
+			dsb_g64::fast_classify(w, sd, d.len);
+			if (both_direction) dsb_g64::fast_classify(w, sd + 1, d.len);
+			const uint32_t na = w.n_anc;
+			bool use = (w.status & (DSB_ST_ANC_OVF | DSB_ST_TIMEOUT)) == 0;
+			if (use) {
+				if (lane == 0) s_word = na ? atomicAdd(pool_counter, na) : 0u;
+				__syncthreads();
+				const unsigned int off = s_word;
+				__syncthreads();
+				use = (uint64_t)off + na <= pool_cap;
+				if (use) {
+					for (uint32_t i = lane; i < na; i += 64) apool[off + i] = w.anc[i];
+					rec.off = off; rec.n = na; rec.lsteps = w.lsteps; rec.use = 1u;
+				}
+			}
+			if (!use && lane < 4) lds_cnt[lane] = cnt0;   /* k_classify does this read's walk (and counts it) again */
+			__syncthreads();
+		}
+		if (lane == 0) arec[r] = rec;
+	}
+}
+#else
+__global__ void k_anchor(DsbDevIndex x, const DsbReadDesc *rd, uint32_t n_items, uint32_t item_base, const uint32_t *list,
+        uint8_t *bin, DsbSlotArena ar, unsigned int *work_counter, DsbSeed *seed_blob, const DsbSeedInfo *sinfo, DsbAncRec *arec, DsbAnchor *apool,
+        unsigned int *pool_counter, uint32_t pool_cap, unsigned long long *work_cnt);
 #endif
 
 
@@ -893,6 +991,7 @@ struct DsbKnobs {
 	long hout_cap = 0, sms_cap = 0, anc_cap_rt = 0, upload_chunk_kb = 0, step_limit_rt = 0, group_head = -1;
 	int upload_threads = 0, seed_scan = -1, heavy_mw = -1, heavy_first = 0;
 	bool heavy_preds_set = false; uint32_t heavy_preds = 0;
+	bool anchor_kernel = true; long anc_pool_rt = 0;   // DSB_ANCHOR_KERNEL=0: the anchor stage inside k_classify (no k_anchor); DSB_ANC_POOL_RT: anchors the pool holds (diagnostics)
 	bool scan_look_set = false; DsbScanLook scan_look;   // DSB_SCAN_LOOK=after_seed,back_fwd,fwd_n,stride_n: k_seed_scan's look-ahead (experiments; default dsb_scan_look_for)
 	std::string order_file;
 };
@@ -912,6 +1011,8 @@ static void knobs_read(DsbKnobs &k)
 	k.seed_scan = getenv("DSB_SEED_SCAN") ? (num("DSB_SEED_SCAN", 0) != 0 ? 1 : 0) : -1;
 	k.heavy_mw = getenv("DSB_HEAVY_MW") ? (int)num("DSB_HEAVY_MW", 0) : -1;
 	k.heavy_first_set = getenv("DSB_HEAVY_FIRST") != nullptr; k.heavy_first = (int)num("DSB_HEAVY_FIRST", 0);
+	k.anchor_kernel = num("DSB_ANCHOR_KERNEL", 1) != 0;
+	k.anc_pool_rt = num("DSB_ANC_POOL_RT", 0); if (getenv("DSB_ANC_POOL_RT") && k.anc_pool_rt < 1) k.anc_pool_rt = 1;
 	if (const char *e = getenv("DSB_HEAVY_PREDS")) { k.heavy_preds_set = true; k.heavy_preds = (uint32_t)strtoul(e, nullptr, 10); }
 	if (const char *e = getenv("DSB_ORDER_FILE")) k.order_file = e;
 	k.scan_look_set = false;
@@ -937,6 +1038,8 @@ struct dsb_ctx {
 	unsigned int *d_counters = nullptr;            // u32: [0] work, [1] hits, [2..3] u64 table-1 probes, [4] early work, [6] listed reads, [7] work of the second run, [8] third run list, [9] its work; u64 x 4 at +16 (main launch), +24 (early launch), +32 (second runs): occ, MEM searches, SA lookups, reference bases
 	DsbSlotArena arena; int n_slots = 0, n_extra = 0;   // n_extra: slots behind the n_slots of the main launch, for the early launch of the heaviest reads (batches of >= 4096 reads)
 	DsbSlotArena arena_big; int n_slots_big = 0;  // second run of reads that outgrew an arena or their loop budget
+	DsbSlotArena arena_anc; int n_slots_anc = 0;  // k_anchor's slots (only the island walk's scratch)
+	DsbAncRec *d_arec = nullptr; DsbAnchor *d_apool = nullptr; size_t cap_arec = 0, cap_apool = 0;   // k_anchor's per-read records and anchor pool
 	uint32_t hint_len = 0;                           // the read length the caller announced (dsb_opts.max_read_len): arenas are never built for less
 	unsigned mw_reads = 16; bool mw_grown = false; int mw_calm = 0;   // reads of the early launch that get eight wavefronts each: follows what the batches of this ctx show (end of dsb_batch_run)
 	uint32_t *d_score = nullptr, *d_order = nullptr, *d_heavy = nullptr; size_t cap_score = 0, cap_order = 0, cap_heavy = 0;
@@ -958,7 +1061,7 @@ struct dsb_ctx {
 	const dsb_taxonomy *tx = nullptr; uint32_t *d_parent = nullptr, *d_ref_tid = nullptr;
 	dsb_read_taxon *d_taxa = nullptr; size_t cap_taxa = 0; std::vector<dsb_read_taxon> h_taxa;
 	bool taxa_run = false, taxa_done = false;     // k_read_taxon ran for the batch of the current slot / its records are fetched and completed
-	dsb_ctx() { memset(&dx, 0, sizeof dx); memset(&arena, 0, sizeof arena); memset(&arena_big, 0, sizeof arena_big); memset(&timing, 0, sizeof timing); memset(&opts, 0, sizeof opts); }
+	dsb_ctx() { memset(&dx, 0, sizeof dx); memset(&arena, 0, sizeof arena); memset(&arena_big, 0, sizeof arena_big); memset(&arena_anc, 0, sizeof arena_anc); memset(&timing, 0, sizeof timing); memset(&opts, 0, sizeof opts); }
 };
 
 // HIP spreads the streams of a process over GPU_MAX_HW_QUEUES hardware queues.  Two contexts on a device have eight streams
@@ -998,7 +1101,7 @@ extern "C" void dsb_ctx_destroy(dsb_ctx *c)
 	for (InSlot &s : c->in) { hipFree(s.d_rd); hipFree(s.d_ascii); hipFree(s.d_scan_order); }
 	hipFree(c->d_wd); hipFree(c->d_bin); hipFree(c->d_pk); hipFree(c->d_bits);
 	hipFree(c->d_parent); hipFree(c->d_ref_tid); hipFree(c->d_taxa);
-	hipFree(c->d_rout); hipFree(c->d_hout); hipFree(c->d_counters); hipFree(c->arena.base); hipFree(c->arena_big.base); hipFree(c->d_score); hipFree(c->d_order); hipFree(c->d_heavy); hipFree(c->d_seeds); hipFree(c->d_sinfo); hipFree(c->syn0); hipFree(c->syn1);
+	hipFree(c->d_rout); hipFree(c->d_hout); hipFree(c->d_counters); hipFree(c->arena.base); hipFree(c->arena_big.base); hipFree(c->arena_anc.base); hipFree(c->d_arec); hipFree(c->d_apool); hipFree(c->d_score); hipFree(c->d_order); hipFree(c->d_heavy); hipFree(c->d_seeds); hipFree(c->d_sinfo); hipFree(c->syn0); hipFree(c->syn1);
 	if (c->dbg_host) hipHostFree(c->dbg_host);
 	for (UpStage &u : c->up) { if (u.st) { hipStreamSynchronize(u.st); hipStreamDestroy(u.st); } for (int k = 0; k < 2; k++) { if (u.ev[k]) hipEventDestroy(u.ev[k]); if (u.buf[k]) hipHostFree(u.buf[k]); } }
 	for (int i = 0; i < 4; i++) if (c->ev[i]) hipEventDestroy(c->ev[i]);
@@ -1189,23 +1292,24 @@ static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 #define DSB_RETRY_MAX_NODES (8u << 20)
 #define DSB_RETRY_ANC (8u * DSB_ANC_CAP)
 #define DSB_RETRY_HIT (4u * DSB_HIT_CAP)
+// hit_cap == 0: a slot of k_anchor -- only the anchor list, the visited-row sets, the island order and the lanes' scratch
 static size_t arena_layout(DsbSlotArena &a, uint32_t max_len, int group, uint32_t sms_cap, uint32_t anc_cap, uint32_t hit_cap)
 {
-	size_t o = 0;
+	size_t o = 0; const size_t f = hit_cap ? 1 : 0;
 	a.max_len = max_len; a.sms_cap = sms_cap; a.anc_cap = anc_cap; a.hit_cap = hit_cap;
-	a.off_seeds = o;   o += al256(((size_t)(max_len >> 1) + 64) * sizeof(DsbSeed));
+	a.off_seeds = o;   o += f * al256(((size_t)(max_len >> 1) + 64) * sizeof(DsbSeed));
 	a.off_anc = o;     o += al256((size_t)anc_cap * sizeof(DsbAnchor));
-	a.off_anc_tmp = o; o += al256((size_t)anc_cap * sizeof(DsbAnchor));
+	a.off_anc_tmp = o; o += f * al256((size_t)anc_cap * sizeof(DsbAnchor));
 	a.off_hit = o;     o += al256((size_t)hit_cap * sizeof(DsbChain));
 	a.off_hit_tmp = o; o += al256((size_t)hit_cap * sizeof(DsbChain));
-	a.off_sms = o;     o += al256((size_t)sms_cap * sizeof(DsbSms));
-	a.off_sc = o;      o += al256((size_t)(256 + 2 * 400 + 64) * sizeof(DsbScHash));
-	a.off_mem = o;     o += al256((size_t)DSB_MEMSLOW_CAP * sizeof(DsbMem));
+	a.off_sms = o;     o += f * al256((size_t)sms_cap * sizeof(DsbSms));
+	a.off_sc = o;      o += f * al256((size_t)(256 + 2 * 400 + 64) * sizeof(DsbScHash));
+	a.off_mem = o;     o += f * al256((size_t)DSB_MEMSLOW_CAP * sizeof(DsbMem));
 	a.off_spset = o;   o += al256((size_t)DSB_SPHASH * 8);
-	a.off_scorev = o;  o += al256((size_t)1024 * sizeof(int));
-	a.off_sortkey = o; o += al256((size_t)2 * anc_cap * sizeof(uint64_t));
+	a.off_scorev = o;  o += f * al256((size_t)1024 * sizeof(int));
+	a.off_sortkey = o; o += f * al256((size_t)2 * anc_cap * sizeof(uint64_t));
 	a.off_sortidx = o; o += al256((size_t)2 * anc_cap * sizeof(uint32_t));
-	a.off_win = o;     o += al256((size_t)3 * DSB_REFWIN + DSB_REFWIN_FRONT);
+	a.off_win = o;     o += f * al256((size_t)3 * DSB_REFWIN + DSB_REFWIN_FRONT);
 	a.off_lane_anc = o; o += al256((size_t)group * DSB_LANE_ANC_CAP * sizeof(DsbAnchor));
 	a.off_lane_sp = o;  o += al256((size_t)group * DSB_SPHASH * 8);
 	a.off_top = o;      o += al256(((size_t)(max_len >> 1) + 64) * 4);
@@ -1263,10 +1367,24 @@ static int ensure_buffers(dsb_ctx *c, size_t n, uint32_t max_len, uint64_t bin_b
 	if ((rc = grow(&c->d_score, &c->cap_score, n + 1))) return rc;
 	if ((rc = grow(&c->d_heavy, &c->cap_heavy, n + 1))) return rc;
 	if ((rc = grow(&c->d_order, &c->cap_order, n + 1))) return rc;
+	// k_anchor: a record per read and one pool for the anchors of the batch (a read's share of it is not fixed: the reads of a 50-kbp
+	// batch have ~500 anchors on average, a few have thousands); reads that find the pool full keep the anchor stage in k_classify
+	if (c->knobs.anchor_kernel) {
+		if ((rc = grow(&c->d_arec, &c->cap_arec, n + 1))) return rc;
+		uint64_t pool = (uint64_t)bin_bytes / 128 + 64 * (uint64_t)n;
+		if (c->knobs.anc_pool_rt) pool = (uint64_t)c->knobs.anc_pool_rt;
+		if (pool > 0xffffffffu) pool = 0xffffffffu;
+		if (c->cap_apool < pool || c->knobs.anc_pool_rt) {
+			if (c->cap_apool != pool) { hipFree(c->d_apool); c->d_apool = nullptr; c->cap_apool = 0; if (hipMalloc((void **)&c->d_apool, pool * sizeof(DsbAnchor)) != hipSuccess) return DSB_ENOMEM; c->cap_apool = pool; }
+		}
+	}
 	// reads in flight: one wavefront each; default = what is resident at once (12 waves per CU: LDS), bounded by the batch
 	int want = c->opts.n_slots > 0 ? c->opts.n_slots : 256 * 4 * DSB_WAVES_PER_EU;
 	if ((size_t)want > n) want = (int)(n ? n : 1);
 	if (want < c->n_slots) want = c->n_slots;
+	int want_anc = 256 * 4 * DSB_ANCHOR_WPE;                  // k_anchor: one slot per wavefront it can keep resident
+	if ((size_t)want_anc > n) want_anc = (int)(n ? n : 1);
+	if (want_anc < c->n_slots_anc) want_anc = c->n_slots_anc;
 	// The arenas are built for the length the caller announced even when this batch's reads are shorter: the four-read batch that
 	// warms a new ctx up (longest read 1500) used to count a 100-kbase arena as "oversized", give it back and leave the first real
 	// batch to build it again -- on the per-batch path, behind the sibling context's kernels: seconds (PacBio-mixed reads, CLI).
@@ -1286,18 +1404,23 @@ static int ensure_buffers(dsb_ctx *c, size_t n, uint32_t max_len, uint64_t bin_b
 	int want_extra = (n >= 4096 || c->knobs.heavy_first_set) ? DSB_HEAVY_SLOTS : 0;
 	if (want_extra < c->n_extra) want_extra = c->n_extra;
 	for (int pass = 0; pass < 2; pass++) {
-		size_t budget_big = 0, budget_main = 0;
+		size_t budget_big = 0, budget_main = 0, budget_anc = 0;
 		if (pass) {
 			size_t free_b = 0, total_b = 0;
 			if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { free_b = (size_t)64 << 30; }
 			const size_t reserve = (size_t)2 << 30;
 			budget_big = free_b > reserve ? (free_b - reserve) / 4 : 0; budget_main = free_b > reserve ? (free_b - reserve) / 2 : 0;
+			budget_anc = free_b > reserve ? (free_b - reserve) / 8 : 0;
 		}
 		const int r1 = size_arena(c->arena_big, &c->n_slots_big, max_len, DSB_RETRY_SLOTS, 4, (uint32_t)cap2, DSB_RETRY_ANC, DSB_RETRY_HIT, 0, budget_big, false, pass == 0);
 		const int r2 = size_arena(c->arena, &c->n_slots, max_len, want, 64 < want ? 64 : want, cap1, anc1, DSB_HIT_CAP, want_extra, budget_main, exact, pass == 0, &c->n_extra);
-		if (r1 == 1 || r2 == 1) continue;            // (first pass: an arena must be built -- again with the budget)
+		// k_anchor's slots: sms_cap 0 and hit_cap 0 make the small layout (arena_layout); the anchor cap must be k_classify's
+		if (c->knobs.anchor_kernel && c->arena_anc.base && c->arena_anc.anc_cap != anc1) { hipFree(c->arena_anc.base); c->arena_anc.base = nullptr; c->n_slots_anc = 0; }
+		const int r3 = c->knobs.anchor_kernel ? size_arena(c->arena_anc, &c->n_slots_anc, max_len, want_anc, 64 < want_anc ? 64 : want_anc, 0u, anc1, 0u, 0, budget_anc, false, pass == 0) : 0;
+		if (r1 == 1 || r2 == 1 || r3 == 1) continue;            // (first pass: an arena must be built -- again with the budget)
 		if (r1) return r1;
 		if (r2) return r2;
+		if (r3) return r3;
 		break;
 	}
 	return DSB_OK;
@@ -1525,11 +1648,11 @@ extern "C" long dsb_batch_upload_fastq(dsb_ctx *c, const char *path, size_t skip
 template <class K>
 static void launch_classify(K kern, dsb_ctx *c, hipStream_t st, unsigned grid, const DsbDevIndex &dx, const InSlot &s, uint32_t n_fixed, const unsigned int *n_ptr,
                             const uint32_t *list, const DsbSlotArena &ar, unsigned int *work_counter, uint32_t *dbg, uint32_t item_base, uint32_t slot_base, int cnt_set,
-                            bool pre_seeds)
+                            bool pre_seeds, const DsbAncRec *arec = nullptr, const DsbAnchor *apool = nullptr)
 {
 	hipLaunchKernelGGL(kern, dim3(grid), dim3(64), 0, st, dx, (const DsbReadDesc *)s.d_rd, n_fixed, n_ptr, list, c->d_bin, (const uint64_t *)c->d_bits, ar, work_counter,
 	                   c->d_rout, c->d_hout, c->d_counters + 1, (uint32_t)c->cap_hout, dbg, item_base, slot_base, (unsigned long long *)(c->d_counters + 16 + 8 * cnt_set),
-	                   pre_seeds ? c->d_seeds : nullptr, (const DsbSeedInfo *)c->d_sinfo, (const uint64_t *)c->d_pk, (uint32_t)((pre_seeds && s.max_len <= DSB_GROUP_MAX_LEN && !c->knobs.no_group) ? (c->knobs.group_head >= 0 ? (unsigned)c->knobs.group_head : 8u * grid) : 0u));
+	                   pre_seeds ? c->d_seeds : nullptr, (const DsbSeedInfo *)c->d_sinfo, (const uint64_t *)c->d_pk, (uint32_t)((pre_seeds && s.max_len <= DSB_GROUP_MAX_LEN && !c->knobs.no_group) ? (c->knobs.group_head >= 0 ? (unsigned)c->knobs.group_head : 8u * grid) : 0u), arec, apool);
 }
 
 static int batch_run_locked(dsb_ctx *c, std::unique_lock<std::mutex> *turn);
@@ -1649,7 +1772,18 @@ static int batch_run_locked(dsb_ctx *c, std::unique_lock<std::mutex> *turn)
 	{
 		uint32_t *dbgp = dbg ? c->dbg_dev : nullptr;
 		if (dbg) memset(c->dbg_host, 0, 32 * 65536 * sizeof(uint32_t));
-		launch_classify(k_classify, c, c->stream, slots, dx1, s, (uint32_t)n, nullptr, (const uint32_t *)c->d_order, c->arena, c->d_counters, dbgp, (uint32_t)n_heavy, 0u, 0, use_scan);
+		// The anchor stage of the main launch's reads first, as a kernel of its own (k_anchor; timing.classify_ms covers both).  Not for
+		// stage dumps, short-read batches (group mode has its own anchor stage) and the hit-bit path (no seed lists).
+		const bool grp = s.max_len <= DSB_GROUP_MAX_LEN && !c->knobs.no_group;
+		const bool anc_k = use_scan && !dbg && !grp && c->knobs.anchor_kernel && c->arena_anc.base && c->n_slots_anc > 0 && c->arena_anc.anc_cap == c->arena.anc_cap
+		                   && c->d_arec && c->cap_arec >= n && c->d_apool && n > n_heavy;
+		if (anc_k) {
+			unsigned ga = (unsigned)c->n_slots_anc; if (ga > n - n_heavy) ga = (unsigned)(n - n_heavy);
+			hipLaunchKernelGGL(k_anchor, dim3(ga), dim3(64), 0, c->stream, dx1, (const DsbReadDesc *)s.d_rd, (uint32_t)n, (uint32_t)n_heavy, (const uint32_t *)c->d_order, c->d_bin, c->arena_anc,
+			                   c->d_counters + 14, c->d_seeds, (const DsbSeedInfo *)c->d_sinfo, c->d_arec, c->d_apool, c->d_counters + 15, (uint32_t)c->cap_apool, (unsigned long long *)(c->d_counters + 16));
+		}
+		launch_classify(k_classify, c, c->stream, slots, dx1, s, (uint32_t)n, nullptr, (const uint32_t *)c->d_order, c->arena, c->d_counters, dbgp, (uint32_t)n_heavy, 0u, 0, use_scan,
+		                anc_k ? c->d_arec : nullptr, anc_k ? c->d_apool : nullptr);
 		HIPCHK(hipEventRecord(c->ev_cls, c->stream));
 		HIPCHK(hipEventRecord(c->ev_cls_wait, c->stream));
 		if (n_heavy) { HIPCHK(hipStreamWaitEvent(c->stream, c->ev_heavy, 0)); if (c->timing.n_heavy_mw) HIPCHK(hipStreamWaitEvent(c->stream, c->ev_heavy3, 0)); }
