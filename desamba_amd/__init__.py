@@ -68,6 +68,13 @@ class DsbReadTaxon(C.Structure):
 DSB_TAXON_CLASSIFIED, DSB_TAXON_HOST = 1, 2
 
 
+class DsbRefCoverage(C.Structure):
+    _fields_ = [("numreads", C.c_uint64), ("covbases", C.c_uint64), ("aligned_bases", C.c_uint64), ("mapq_sum", C.c_uint64)]
+
+
+COVERAGE_FIELDS = ("numreads", "covbases", "aligned_bases", "mapq_sum")
+
+
 class DsbChunk(C.Structure):
     _fields_ = [("start", C.c_uint64), ("end", C.c_uint64), ("hist_max_before", C.c_uint32), ("rank", C.c_int32)]
 
@@ -80,7 +87,9 @@ EXPORTS = ["dsb_index_open", "dsb_index_close", "dsb_index_n_ref", "dsb_index_re
            "dsb_multi_reset_history", "dsb_multi_last_calls", "dsb_multi_classify_batch", "dsb_shard_plan", "dsb_ctx_use_synthetic_filter", "dsb_synthetic_filter_bit", "dsb_index_prefix_interval", "dsb_index_build",
            "dsb_taxonomy_load", "dsb_taxonomy_load_any", "dsb_taxonomy_close", "dsb_taxonomy_max_tid", "dsb_taxonomy_parent",
            "dsb_ctx_set_taxonomy", "dsb_multi_set_taxonomy", "dsb_batch_taxa", "dsb_multi_taxa",
-           "dsb_report_create", "dsb_report_add", "dsb_report_add_sam", "dsb_report_format", "dsb_report_destroy"]
+           "dsb_report_create", "dsb_report_add", "dsb_report_add_sam", "dsb_report_format", "dsb_report_destroy",
+           "dsb_ctx_enable_coverage", "dsb_ctx_reset_coverage", "dsb_ctx_coverage", "dsb_multi_enable_coverage", "dsb_multi_coverage",
+           "dsb_coverage_format"]
 
 _lib = None
 
@@ -149,6 +158,12 @@ def lib():
     L.dsb_report_add_sam.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.dsb_report_format.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t]; L.dsb_report_format.restype = C.c_long
     L.dsb_report_destroy.argtypes = [C.c_void_p]; L.dsb_report_destroy.restype = None
+    L.dsb_ctx_enable_coverage.argtypes = [C.c_void_p, C.c_int]
+    L.dsb_ctx_reset_coverage.argtypes = [C.c_void_p]
+    L.dsb_ctx_coverage.argtypes = [C.c_void_p, C.c_void_p]
+    L.dsb_multi_enable_coverage.argtypes = [C.c_void_p, C.c_int]
+    L.dsb_multi_coverage.argtypes = [C.c_void_p, C.c_void_p]
+    L.dsb_coverage_format.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]; L.dsb_coverage_format.restype = C.c_long
     L.dsb_strerror.argtypes = [C.c_int]; L.dsb_strerror.restype = C.c_char_p
     L.dsb_version.restype = C.c_char_p
     _lib = L
@@ -185,6 +200,9 @@ class Index:
 
     def ref_name(self, i):
         return lib().dsb_index_ref_name(self.h, i).decode()
+
+    def ref_len(self, i):
+        return int(lib().dsb_index_ref_len(self.h, i))
 
     def occ_host(self, r, c):
         cc = C.c_uint8(c)
@@ -331,6 +349,21 @@ class Ctx:
         n = self.in_last_batch()
         return _taxa(p, n, records)
 
+    def enable_coverage(self, on=True):
+        """per-reference coverage from now on (a bitmap of one bit per reference base in HBM), or off (freed)"""
+        rc = lib().dsb_ctx_enable_coverage(self.h, 1 if on else 0)
+        if rc != 0:
+            raise DsbError(rc, "dsb_ctx_enable_coverage")
+
+    def reset_coverage(self):
+        rc = lib().dsb_ctx_reset_coverage(self.h)
+        if rc != 0:
+            raise DsbError(rc, "dsb_ctx_reset_coverage")
+
+    def coverage(self):
+        """everything since enable / reset: numpy structured array of n_ref rows (COVERAGE_FIELDS, u64)"""
+        return _coverage(lib().dsb_ctx_coverage, self.h, self.index.n_ref, "dsb_ctx_coverage")
+
     def in_last_batch(self):
         return len(self.reads) if self.reads is not None else getattr(self, "n_uploaded", 0)
 
@@ -393,6 +426,15 @@ class Multi:
             raise DsbError(rc, "dsb_multi_set_taxonomy")
         self.taxonomy = taxonomy
 
+    def enable_coverage(self, on=True):
+        rc = lib().dsb_multi_enable_coverage(self.h, 1 if on else 0)
+        if rc != 0:
+            raise DsbError(rc, "dsb_multi_enable_coverage")
+
+    def coverage(self):
+        """Ctx.coverage merged over the contexts"""
+        return _coverage(lib().dsb_multi_coverage, self.h, self.index.n_ref, "dsb_multi_coverage")
+
     def taxa(self, records=False):
         """Ctx.taxa for the last classify(), in input order"""
         p = C.POINTER(DsbReadTaxon)()
@@ -410,6 +452,33 @@ def _taxa(p, n, records):
         return arr
     import numpy as np
     return np.array([arr[i].taxid for i in range(n)], dtype=np.uint32)
+
+
+COVERAGE_DTYPE = [(f, "<u8") for f in COVERAGE_FIELDS]
+
+
+def _coverage(fn, h, n_ref, what):
+    import numpy as np
+    out = np.zeros(n_ref, dtype=COVERAGE_DTYPE)
+    rc = fn(h, out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise DsbError(rc, what)
+    return out
+
+
+def format_coverage(index, cov):
+    """dsb_coverage_format: the `samtools coverage`-style table (bytes) of a coverage array (Ctx/Multi.coverage())"""
+    import numpy as np
+    cov = np.ascontiguousarray(cov, dtype=COVERAGE_DTYPE)
+    if len(cov) != index.n_ref:
+        raise ValueError("format_coverage: %d rows for %d references" % (len(cov), index.n_ref))
+    cap = 1 << 16
+    while True:
+        buf = C.create_string_buffer(cap)
+        n = lib().dsb_coverage_format(index.h, cov.ctypes.data_as(C.c_void_p), buf, cap)
+        if n >= 0:
+            return buf.raw[:n]
+        cap *= 4
 
 
 class Taxonomy:

@@ -846,7 +846,8 @@ static void usage(void)
 	fprintf(stderr, "                    - DES: smaller format\n                    - DES_FULL: all results are showed, ignore '-r' opinion\n");
 	fprintf(stderr, "    --taxonomy FILE  nodes.dmp of the taxids in the reference names (needed by the two options below)\n");
 	fprintf(stderr, "    --report FILE    write the read counts per taxon of the run into FILE, as `analysis ana_meta` prints them for its SAM\n");
-	fprintf(stderr, "    --report-base FILE  the same for `analysis ana_meta_base` (bases weighted by MAPQ)\n\n");
+	fprintf(stderr, "    --report-base FILE  the same for `analysis ana_meta_base` (bases weighted by MAPQ)\n");
+	fprintf(stderr, "    --coverage FILE  write the coverage of every reference the run touched into FILE (columns of `samtools coverage`)\n\n");
 }
 
 static double now(void) { struct timeval tv; gettimeofday(&tv, NULL); return tv.tv_sec + tv.tv_usec * 1e-6; }
@@ -903,12 +904,14 @@ static int classify_main(int argc, char **argv)
 	static app_t a; int c;
 	int dev[MAX_DEV], n_dev = 1; dev[0] = 0;
 	a.o.L_min_matching = 170; a.o.min_score = 64; a.o.max_sec_N = 5; a.o.n_slots = 0; a.out = stdout;
-	static const struct option long_opts[] = {{"taxonomy", required_argument, NULL, 1}, {"report", required_argument, NULL, 2}, {"report-base", required_argument, NULL, 3}, {NULL, 0, NULL, 0}};
-	const char *tax_path = NULL, *rep_path[2] = {NULL, NULL};
+	static const struct option long_opts[] = {{"taxonomy", required_argument, NULL, 1}, {"report", required_argument, NULL, 2}, {"report-base", required_argument, NULL, 3},
+	                                              {"coverage", required_argument, NULL, 4}, {NULL, 0, NULL, 0}};
+	const char *tax_path = NULL, *rep_path[2] = {NULL, NULL}, *cov_path = NULL;
 	while ((c = getopt_long(argc, argv, "ht:l:r:f:o:s:g:", long_opts, NULL)) >= 0) {
 		if (c == 'h') { usage(); return 0; }
 		else if (c == 1) tax_path = optarg;
 		else if (c == 2 || c == 3) rep_path[c - 2] = optarg;
+		else if (c == 4) cov_path = optarg;
 		else if (c == 't') { /* thread count: accepted for compatibility, unused */ }
 		else if (c == 'l') a.o.L_min_matching = atoi(optarg);
 		else if (c == 'r') a.o.max_sec_N = atoi(optarg);
@@ -950,6 +953,8 @@ static int classify_main(int argc, char **argv)
 			if (rep_path[k] && !(a.rep_out[k] = fopen(rep_path[k], "w"))) { fprintf(stderr, "[xopen] fail to open file '%s'\n", rep_path[k]); exit(1); }
 		if ((rep_path[0] || rep_path[1]) && dsb_report_create(a.tx, &a.rep)) die("[classify] out of memory");
 	}
+	FILE *cov_out = NULL;
+	if (cov_path && !(cov_out = fopen(cov_path, "w"))) { fprintf(stderr, "[xopen] fail to open file '%s'\n", cov_path); exit(1); }
 	app_defaults(&a);
 	setvbuf(a.out, NULL, _IOFBF, 8 << 20);
 
@@ -965,6 +970,7 @@ static int classify_main(int argc, char **argv)
 	if (rc) { fprintf(stderr, "\n[dsb_ctx_create] %s\n", dsb_strerror(rc)); exit(1); }
 	for (int k = 0; k < a.n_ctx; k++) a.ctx[k] = dsb_multi_ctx(a.multi, k);
 	if (a.rep && (rc = dsb_multi_set_taxonomy(a.multi, a.tx))) { fprintf(stderr, "\n[dsb_ctx_set_taxonomy] %s\n", dsb_strerror(rc)); exit(1); }
+	if (cov_out && (rc = dsb_multi_enable_coverage(a.multi, 1))) { fprintf(stderr, "\n[dsb_ctx_enable_coverage] %s\n", dsb_strerror(rc)); exit(1); }
 	double t0 = now(), cpu0 = cputime(); a.t0 = t0;
 	a.thr0 = a.trace ? throttled_usec() : -1;
 	fprintf(stderr, "Start classify\n");
@@ -991,6 +997,16 @@ static int classify_main(int argc, char **argv)
 		do { cap *= 4; buf = xrealloc(buf, cap); w = dsb_report_format(a.rep, k, buf, cap); } while (w < 0);
 		if (fwrite(buf, 1, (size_t)w, a.rep_out[k]) != (size_t)w || fclose(a.rep_out[k])) die("[classify] cannot write the report");
 		free(buf);
+	}
+	if (cov_out) {
+		/* --coverage: the per-reference coverage of the whole run, merged over the contexts */
+		const size_t n_ref = (size_t)dsb_index_n_ref(a.idx);
+		dsb_ref_coverage *cov = xrealloc(NULL, (n_ref ? n_ref : 1) * sizeof *cov);
+		if ((rc = dsb_multi_coverage(a.multi, cov))) { fprintf(stderr, "[dsb_multi_coverage] %s\n", dsb_strerror(rc)); exit(1); }
+		size_t cap = 1 << 16; char *buf = NULL; long w;
+		do { cap *= 4; buf = xrealloc(buf, cap); w = dsb_coverage_format(a.idx, cov, buf, cap); } while (w < 0);
+		if (fwrite(buf, 1, (size_t)w, cov_out) != (size_t)w || fclose(cov_out)) die("[classify] cannot write the coverage table");
+		free(buf); free(cov);
 	}
 	dsb_report_destroy(a.rep);
 	dsb_multi_destroy(a.multi);

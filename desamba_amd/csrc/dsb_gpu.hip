@@ -867,6 +867,81 @@ __global__ void __launch_bounds__(256) k_read_taxon(const DsbReadOut *__restrict
 	out[i] = t;
 }
 
+// Per-reference coverage (dsb_ctx_enable_coverage).  One wavefront per read, after the batch's last classify work: each
+// record printed without FLAG 0x100 (dsb_sam_counted) adds to its reference's counters (lane 0) and sets the bits of its interval
+// [min(t_st, LN), min(t_ed, LN)), the lanes striding over its words.  The bits are set by agent-scope atomic ORs, never by plain
+// stores: two records may share a word, and their workgroups may sit on XCDs whose L2s are not coherent with each other.  A
+// reference's bits start at word word_off[ref]; bits at LN and beyond are never set.
+__global__ void __launch_bounds__(256) k_ref_cover(const DsbReadOut *__restrict__ rout, const DsbHitOut *__restrict__ hout, const unsigned int *__restrict__ counters,
+                                                   uint32_t cap_hout, uint32_t n, const uint64_t *__restrict__ ref_len, const uint64_t *__restrict__ word_off,
+                                                   uint32_t n_ref, uint64_t *bits, dsb_ref_coverage *cov)
+{
+	const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+	if (i >= n) return;
+	const uint32_t nh = counters[1] < cap_hout ? counters[1] : cap_hout;
+	const DsbReadOut r = rout[i];
+	const uint32_t nrec = (uint64_t)r.first + r.n > nh ? 0u : r.n;   // (what dsb_batch_fetch hands out)
+	if (!nrec) return;
+	const dsb_hit *h = reinterpret_cast<const dsb_hit *>(hout + r.first);
+	const int mq_pri = dsb_sam_mapq_pri(h, nrec);
+	for (uint32_t k = 0; k < nrec; k++) {
+		const dsb_hit *c = h + k;
+		if (!dsb_sam_counted(c, k) || c->ref_ID >= n_ref) continue;
+		const uint64_t ln = ref_len[c->ref_ID];
+		const uint64_t s = c->t_st < ln ? c->t_st : ln, e = c->t_ed < ln ? c->t_ed : ln;
+		if (lane == 0) {
+			dsb_ref_coverage *o = cov + c->ref_ID;
+			__hip_atomic_fetch_add(&o->numreads, (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			if (e > s) __hip_atomic_fetch_add(&o->aligned_bases, e - s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			const int mq = k ? dsb_sam_mapq_sup(mq_pri) : mq_pri;
+			if (mq) __hip_atomic_fetch_add(&o->mapq_sum, (uint64_t)mq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		}
+		if (e <= s) continue;
+		uint64_t *w = bits + word_off[c->ref_ID];
+		for (uint64_t q = (s >> 6) + lane; q <= ((e - 1) >> 6); q += 64) {
+			const uint64_t lo = q * 64 < s ? s - q * 64 : 0, hi = q * 64 + 64 > e ? e - q * 64 : 64;   // bits [lo, hi) of word q
+			const uint64_t m = (hi == 64 ? ~0ull : (1ull << hi) - 1) & (~0ull << lo);
+			__hip_atomic_fetch_or(w + q, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		}
+	}
+}
+
+// End of a run: covbases, a segmented popcount over words [w0, w0 + nw) of the bitmap (bits[q - w0] holds word q), balanced by words
+// rather than by reference.  Each wavefront takes DSB_COVER_CHUNK words, finds the reference of its first word by binary search in
+// the word offsets (empty references skipped: the last r with word_off[r] <= a) and adds one partial sum per reference it spans.
+#define DSB_COVER_CHUNK 1024
+__global__ void __launch_bounds__(256) k_cover_count(const uint64_t *__restrict__ bits, uint64_t w0, uint64_t nw, const uint64_t *__restrict__ word_off,
+                                                     uint32_t n_ref, dsb_ref_coverage *cov)
+{
+	const uint64_t a = w0 + ((uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * DSB_COVER_CHUNK, end = w0 + nw;
+	const uint32_t lane = threadIdx.x & 63;
+	if (a >= end) return;
+	const uint64_t b = a + DSB_COVER_CHUNK < end ? a + DSB_COVER_CHUNK : end;
+	uint32_t lo = 0, hi = n_ref;                           // word_off[lo] <= a < word_off[hi] (= the bitmap's size for hi = n_ref)
+	while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (word_off[mid] <= a) lo = mid; else hi = mid; }
+	for (uint32_t r = lo;; r++) {
+		const uint64_t s = word_off[r] > a ? word_off[r] : a, e = word_off[r + 1] < b ? word_off[r + 1] : b;
+		uint32_t sum = 0;                                  // (at most 64 bits x DSB_COVER_CHUNK words)
+		for (uint64_t q = s + lane; q < e; q += 64) sum += (uint32_t)__popcll(bits[q - w0]);
+		for (int o = 32; o; o >>= 1) sum += __shfl_xor(sum, o, 64);
+		if (lane == 0 && sum) __hip_atomic_fetch_add(&cov[r].covbases, (uint64_t)sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		if (e >= b) break;
+	}
+}
+
+// before a count: covbases = 0 (the other three counters stay)
+__global__ void __launch_bounds__(256) k_cover_clear(dsb_ref_coverage *cov, uint32_t n_ref)
+{
+	const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+	if (r < n_ref) cov[r].covbases = 0;
+}
+
+// dsb_multi_coverage: dst |= src over nw words (the contexts' bitmaps merged before the count)
+__global__ void __launch_bounds__(256) k_cover_or(uint64_t *__restrict__ dst, const uint64_t *__restrict__ src, uint64_t nw)
+{
+	for (uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x; q < nw; q += (uint64_t)gridDim.x * 256) dst[q] |= src[q];
+}
+
 // ================================== host side ====================================================
 #include <mutex>
 #include <thread>
@@ -1061,6 +1136,9 @@ struct dsb_ctx {
 	const dsb_taxonomy *tx = nullptr; uint32_t *d_parent = nullptr, *d_ref_tid = nullptr;
 	dsb_read_taxon *d_taxa = nullptr; size_t cap_taxa = 0; std::vector<dsb_read_taxon> h_taxa;
 	bool taxa_run = false, taxa_done = false;     // k_read_taxon ran for the batch of the current slot / its records are fetched and completed
+	// per-reference coverage (dsb_ctx_enable_coverage): a bitmap of one bit per reference base (each reference from a word boundary,
+	// cov_off: the prefix sum of ceil(LN / 64), n_ref + 1 words), the lengths, and the four counters per reference; one k_ref_cover launch per batch
+	uint64_t *d_cov_bits = nullptr, *d_cov_off = nullptr, *d_cov_len = nullptr; dsb_ref_coverage *d_cov = nullptr; uint64_t cov_words = 0;
 	dsb_ctx() { memset(&dx, 0, sizeof dx); memset(&arena, 0, sizeof arena); memset(&arena_big, 0, sizeof arena_big); memset(&arena_anc, 0, sizeof arena_anc); memset(&timing, 0, sizeof timing); memset(&opts, 0, sizeof opts); }
 };
 
@@ -1101,6 +1179,7 @@ extern "C" void dsb_ctx_destroy(dsb_ctx *c)
 	for (InSlot &s : c->in) { hipFree(s.d_rd); hipFree(s.d_ascii); hipFree(s.d_scan_order); }
 	hipFree(c->d_wd); hipFree(c->d_bin); hipFree(c->d_pk); hipFree(c->d_bits);
 	hipFree(c->d_parent); hipFree(c->d_ref_tid); hipFree(c->d_taxa);
+	hipFree(c->d_cov_bits); hipFree(c->d_cov_off); hipFree(c->d_cov_len); hipFree(c->d_cov);
 	hipFree(c->d_rout); hipFree(c->d_hout); hipFree(c->d_counters); hipFree(c->arena.base); hipFree(c->arena_big.base); hipFree(c->arena_anc.base); hipFree(c->d_arec); hipFree(c->d_apool); hipFree(c->d_score); hipFree(c->d_order); hipFree(c->d_heavy); hipFree(c->d_seeds); hipFree(c->d_sinfo); hipFree(c->syn0); hipFree(c->syn1);
 	if (c->dbg_host) hipHostFree(c->dbg_host);
 	for (UpStage &u : c->up) { if (u.st) { hipStreamSynchronize(u.st); hipStreamDestroy(u.st); } for (int k = 0; k < 2; k++) { if (u.ev[k]) hipEventDestroy(u.ev[k]); if (u.buf[k]) hipHostFree(u.buf[k]); } }
@@ -1852,6 +1931,12 @@ static int batch_run_locked(dsb_ctx *c, std::unique_lock<std::mutex> *turn)
 		                   (const uint32_t *)c->d_ref_tid, (uint32_t)dsb_index_n_ref(c->idx), c->tx->max_tid, bound, c->opts.max_sec_N, c->d_taxa);
 		c->taxa_run = true;
 	}
+	if (c->d_cov) {
+		// the per-reference coverage, after the same launches, whether or not a taxonomy is attached
+		hipLaunchKernelGGL(k_ref_cover, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, (const DsbReadOut *)c->d_rout, (const DsbHitOut *)c->d_hout,
+		                   (const unsigned int *)c->d_counters, (uint32_t)c->cap_hout, (uint32_t)n, (const uint64_t *)c->d_cov_len, (const uint64_t *)c->d_cov_off,
+		                   (uint32_t)dsb_index_n_ref(c->idx), c->d_cov_bits, c->d_cov);
+	}
 	if (dbg) {
 		static const char *nm[10] = {"seed_vector", "fast_classify", "resolve_tree", "slow+resolve", "hash_build", "sdp_middle", "sdp_right", "sdp_left", "sort/filter", "primary"};
 		double tot[10] = {0}, all = 0; unsigned sl = (unsigned)c->n_slots; if (sl > n) sl = (unsigned)n;
@@ -1979,6 +2064,70 @@ extern "C" int dsb_batch_taxa(dsb_ctx *c, const dsb_read_taxon **out)
 	if (!c || !out || !c->tx || !c->taxa_run) return DSB_EINVAL;
 	if (!c->taxa_done) { dsb_result r; int rc = dsb_batch_fetch(c, &r); if (rc && rc != DSB_ECAP) return rc; }
 	*out = c->h_taxa.data();
+	return DSB_OK;
+}
+
+// ---- per-reference coverage ----
+static void cover_free(dsb_ctx *c)
+{
+	hipFree(c->d_cov_bits); hipFree(c->d_cov_off); hipFree(c->d_cov_len); hipFree(c->d_cov);
+	c->d_cov_bits = c->d_cov_off = c->d_cov_len = nullptr; c->d_cov = nullptr; c->cov_words = 0;
+}
+
+extern "C" int dsb_ctx_reset_coverage(dsb_ctx *c)
+{
+	if (!c || !c->d_cov) return DSB_EINVAL;
+	HIPCHK(hipSetDevice(c->device));
+	const size_t n_ref = (size_t)dsb_index_n_ref(c->idx);
+	HIPCHK(hipMemsetAsync(c->d_cov_bits, 0, (c->cov_words ? c->cov_words : 1) * 8, c->stream));
+	HIPCHK(hipMemsetAsync(c->d_cov, 0, (n_ref ? n_ref : 1) * sizeof(dsb_ref_coverage), c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	return DSB_OK;
+}
+
+extern "C" int dsb_ctx_enable_coverage(dsb_ctx *c, int on)
+{
+	if (!c) return DSB_EINVAL;
+	HIPCHK(hipSetDevice(c->device));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	if (on && c->d_cov) return dsb_ctx_reset_coverage(c);
+	cover_free(c);
+	if (!on) return DSB_OK;
+	const size_t n_ref = (size_t)dsb_index_n_ref(c->idx);
+	std::vector<uint64_t> off(n_ref + 1, 0), len(n_ref ? n_ref : 1, 0);
+	for (size_t r = 0; r < n_ref; r++) { len[r] = dsb_index_ref_len(c->idx, (uint32_t)r); off[r + 1] = off[r] + (len[r] + 63) / 64; }
+	const uint64_t nw = off[n_ref];
+	if (hipMalloc((void **)&c->d_cov_bits, (nw ? nw : 1) * 8) != hipSuccess || hipMalloc((void **)&c->d_cov_off, off.size() * 8) != hipSuccess ||
+	    hipMalloc((void **)&c->d_cov_len, len.size() * 8) != hipSuccess || hipMalloc((void **)&c->d_cov, (n_ref ? n_ref : 1) * sizeof(dsb_ref_coverage)) != hipSuccess) {
+		cover_free(c); (void)hipGetLastError(); return DSB_ENOMEM;
+	}
+	c->cov_words = nw;
+	HIPCHK(hipMemcpy(c->d_cov_off, off.data(), off.size() * 8, hipMemcpyHostToDevice));
+	HIPCHK(hipMemcpy(c->d_cov_len, len.data(), len.size() * 8, hipMemcpyHostToDevice));
+	return dsb_ctx_reset_coverage(c);
+}
+
+// covbases of words [w0, w0 + nw) of the bitmap, held in bits[0 .. nw), added to c's counters
+static void cover_count(dsb_ctx *c, const uint64_t *bits, uint64_t w0, uint64_t nw, hipStream_t st)
+{
+	if (!nw) return;
+	const uint64_t waves = (nw + DSB_COVER_CHUNK - 1) / DSB_COVER_CHUNK;
+	hipLaunchKernelGGL(k_cover_count, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, bits, w0, nw, (const uint64_t *)c->d_cov_off,
+	                   (uint32_t)dsb_index_n_ref(c->idx), c->d_cov);
+}
+
+extern "C" int dsb_ctx_coverage(dsb_ctx *c, dsb_ref_coverage *out)
+{
+	if (!c || !out || !c->d_cov) return DSB_EINVAL;
+	HIPCHK(hipSetDevice(c->device));
+	const uint32_t n_ref = (uint32_t)dsb_index_n_ref(c->idx);
+	if (!n_ref) return DSB_OK;
+	// on the ctx's stream: after the batches it has run (k_ref_cover leaves covbases alone, so a batch behind it changes nothing here)
+	hipLaunchKernelGGL(k_cover_clear, dim3((n_ref + 255) / 256), dim3(256), 0, c->stream, c->d_cov, n_ref);
+	cover_count(c, c->d_cov_bits, 0, c->cov_words, c->stream);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(out, c->d_cov, n_ref * sizeof(dsb_ref_coverage), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
 	return DSB_OK;
 }
 
@@ -2212,6 +2361,67 @@ extern "C" int dsb_multi_taxa(dsb_multi *m, const dsb_read_taxon **out)
 {
 	if (!m || !out || !m->tx || !m->taxa_ok) return DSB_EINVAL;
 	*out = m->taxa.data();
+	return DSB_OK;
+}
+
+extern "C" int dsb_multi_enable_coverage(dsb_multi *m, int on)
+{
+	if (!m) return DSB_EINVAL;
+	for (dsb_ctx *c : m->ctx) { int rc = dsb_ctx_enable_coverage(c, on); if (rc) { for (dsb_ctx *d : m->ctx) dsb_ctx_enable_coverage(d, 0); return rc; } }
+	return DSB_OK;
+}
+
+// The contexts' coverage merged: the counters are added on the host; the bitmaps are ORed chunk by chunk into a buffer on the first
+// context's device -- read in place where a context shares that device, copied over (hipMemcpyPeerAsync) where it does not -- and
+// each chunk is counted there.  The contexts' own bitmaps are left as they are.
+extern "C" int dsb_multi_coverage(dsb_multi *m, dsb_ref_coverage *out)
+{
+	if (!m || !out || m->ctx.empty()) return DSB_EINVAL;
+	for (dsb_ctx *c : m->ctx) if (!c->d_cov) return DSB_EINVAL;
+	dsb_ctx *c0 = m->ctx[0];
+	if (m->ctx.size() == 1) return dsb_ctx_coverage(c0, out);
+	const uint32_t n_ref = (uint32_t)dsb_index_n_ref(m->idx);
+	if (!n_ref) return DSB_OK;
+	memset(out, 0, n_ref * sizeof *out);
+	std::vector<dsb_ref_coverage> part(n_ref);
+	bool remote = false;
+	for (dsb_ctx *c : m->ctx) {
+		HIPCHK(hipSetDevice(c->device));
+		HIPCHK(hipStreamSynchronize(c->stream));
+		HIPCHK(hipMemcpy(part.data(), c->d_cov, n_ref * sizeof(dsb_ref_coverage), hipMemcpyDeviceToHost));
+		for (uint32_t r = 0; r < n_ref; r++) { out[r].numreads += part[r].numreads; out[r].aligned_bases += part[r].aligned_bases; out[r].mapq_sum += part[r].mapq_sum; }
+		remote |= c->device != c0->device;
+	}
+	HIPCHK(hipSetDevice(c0->device));
+	const uint64_t nw = c0->cov_words, chunk = nw < (4ull << 20) ? nw : (4ull << 20);   // (32 MiB of words per chunk)
+	uint64_t *acc = nullptr, *buf = nullptr;
+	if (nw && (hipMalloc((void **)&acc, chunk * 8) != hipSuccess || (remote && hipMalloc((void **)&buf, chunk * 8) != hipSuccess))) {
+		hipFree(acc); (void)hipGetLastError(); return DSB_ENOMEM;
+	}
+	const hipStream_t st = c0->stream;
+	hipLaunchKernelGGL(k_cover_clear, dim3((n_ref + 255) / 256), dim3(256), 0, st, c0->d_cov, n_ref);
+	int rc = DSB_OK;
+	for (uint64_t w0 = 0; w0 < nw && !rc; w0 += chunk) {
+		const uint64_t k = nw - w0 < chunk ? nw - w0 : chunk;
+		const unsigned grid = (unsigned)std::min<uint64_t>((k + 255) / 256, 8192);
+		if (hipMemcpyAsync(acc, c0->d_cov_bits + w0, k * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) rc = DSB_ENODEV;
+		for (size_t i = 1; i < m->ctx.size() && !rc; i++) {
+			const dsb_ctx *c = m->ctx[i];
+			const uint64_t *src = c->d_cov_bits + w0;
+			if (c->device != c0->device) {
+				if (hipMemcpyPeerAsync(buf, c0->device, c->d_cov_bits + w0, c->device, k * 8, st) != hipSuccess) { rc = DSB_ENODEV; break; }
+				src = buf;
+			}
+			hipLaunchKernelGGL(k_cover_or, dim3(grid), dim3(256), 0, st, acc, src, k);
+		}
+		if (!rc) cover_count(c0, acc, w0, k, st);
+	}
+	if (!rc && hipGetLastError() != hipSuccess) rc = DSB_ENODEV;
+	if (!rc && hipMemcpyAsync(part.data(), c0->d_cov, n_ref * sizeof(dsb_ref_coverage), hipMemcpyDeviceToHost, st) != hipSuccess) rc = DSB_ENODEV;
+	if (hipStreamSynchronize(st) != hipSuccess) rc = DSB_ENODEV;
+	hipFree(acc); hipFree(buf);
+	if (rc) return rc;
+	for (uint32_t r = 0; r < n_ref; r++) out[r].covbases = part[r].covbases;
 	return DSB_OK;
 }
 #endif  // DSB_UNIT_HOST

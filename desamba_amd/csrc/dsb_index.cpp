@@ -282,7 +282,7 @@ extern "C" long dsb_format_sam(const dsb_index *x, const dsb_read *rd_, const ds
 		for (uint32_t i = 1; i < n; i++) {
 			const dsb_hit *c = h + i;
 			int show = dsb_sam_shown(c, loop, max_sec), fl = c->direction ? 0 : 0x10, mapQ = 0;
-			if (show && loop == 0) { fl += 0x800; mapQ = mapQ_PRI < 30 ? mapQ_PRI : 30; }
+			if (show && loop == 0) { fl += 0x800; mapQ = dsb_sam_mapq_sup(mapQ_PRI); }
 			else if (show) fl += 0x100;
 			if (show) {
 				dsb_sam_cigar(c, read_l, cg);
@@ -327,6 +327,26 @@ extern "C" long dsb_format_des(const dsb_index *x, const dsb_read *rd_, const ds
 			     dsb_index_ref_name(x, c->ref_ID), (int)c->t_st, (int)c->t_ed, (int)c->q_st, (int)c->q_ed, (int)c->sum_score, (int)c->indel);
 		}
 	EMIT("\n");
+#undef EMIT
+	return (long)o;
+}
+
+// the per-reference coverage table: the columns of `samtools coverage` but its base-quality one
+extern "C" long dsb_coverage_format(const dsb_index *x, const dsb_ref_coverage *cov, char *buf, size_t cap)
+{
+	if (!x || !cov || (!buf && cap)) return -1;
+	size_t o = 0; int w;
+#define EMIT(...) do { w = snprintf(buf + o, cap > o ? cap - o : 0, __VA_ARGS__); if (w < 0 || (size_t)w >= (cap > o ? cap - o : 0)) return -1; o += (size_t)w; } while (0)
+	EMIT("#rname\tstartpos\tendpos\tnumreads\tcovbases\tcoverage\tmeandepth\tmeanmapq\n");
+	const uint64_t n_ref = dsb_index_n_ref(x);
+	for (uint64_t r = 0; r < n_ref; r++) {
+		const dsb_ref_coverage &c = cov[r];
+		if (!c.numreads) continue;
+		const uint64_t ln = dsb_index_ref_len(x, (uint32_t)r);
+		const double L = ln ? (double)ln : 1.0;
+		EMIT("%s\t1\t%llu\t%llu\t%llu\t%g\t%g\t%.1f\n", dsb_index_ref_name(x, (uint32_t)r), (unsigned long long)ln, (unsigned long long)c.numreads,
+		     (unsigned long long)c.covbases, 100.0 * (double)c.covbases / L, (double)c.aligned_bases / L, (double)c.mapq_sum / (double)c.numreads);
+	}
 #undef EMIT
 	return (long)o;
 }

@@ -25,6 +25,13 @@ DSB_HD bool dsb_sam_shown(const dsb_hit *c, int pass, int max_sec)
 	return pass == 0 ? c->pri_index == 0 : (c->pri_index > 0 && c->pri_index <= max_sec);
 }
 
+// MAPQ of a supplementary record (pass 0, FLAG 0x800), from the primary's
+DSB_HD int dsb_sam_mapq_sup(int mapq_pri) { return mapq_pri < 30 ? mapq_pri : 30; }
+
+// record i of a read is printed without FLAG 0x100: the primary (i = 0) or a supplementary record.  The records the
+// per-reference coverage counts (k_ref_cover), whatever max_sec is.
+DSB_HD bool dsb_sam_counted(const dsb_hit *c, uint32_t i) { return i == 0 || dsb_sam_shown(c, 0, 0); }
+
 // the three numbers of a record's CIGAR as the writer prints them with %d: "<v0>S<v1>M<v2>S" (primary, secondary) or
 // "<v0>H<v1>M<v2>H" (supplementary)
 DSB_HD void dsb_sam_cigar(const dsb_hit *c, uint32_t read_l, int v[3])

@@ -275,6 +275,28 @@ int  dsb_report_add_sam(dsb_report *rep, const char *text, size_t len);
 long dsb_report_format(const dsb_report *rep, int by_base, char *buf, size_t cap);
 void dsb_report_destroy(dsb_report *rep);
 
+/* ---- per-reference coverage of a run (breadth and depth), accumulated on the GPU after every batch.
+ * Counted are the records dsb_format_sam prints without FLAG 0x100: the primary and the supplementary ones (pri_index 0);
+ * secondary records never count, so the numbers do not depend on max_sec_N.  A record's interval is
+ * [min(t_st, LN), min(t_ed, LN)) of its reference (LN = dsb_index_ref_len), empty when t_ed <= t_st. */
+typedef struct {
+	uint64_t numreads;        /* counted records */
+	uint64_t covbases;        /* size of the union of their intervals */
+	uint64_t aligned_bases;   /* sum of their interval lengths */
+	uint64_t mapq_sum;        /* sum of the MAPQ each prints */
+} dsb_ref_coverage;
+/* on: allocate a bitmap of one bit per reference base (plus 4 counters per reference) and zero it; DSB_ENOMEM if it does
+ * not fit.  off: free it.  While it is on, every batch ends with k_ref_cover; while it is off nothing is allocated or launched. */
+int  dsb_ctx_enable_coverage(dsb_ctx *ctx, int on);
+int  dsb_ctx_reset_coverage(dsb_ctx *ctx);                    /* zero, keep the allocation */
+/* dsb_index_n_ref entries: everything since enable / reset (fetching changes nothing); DSB_EINVAL when coverage is off */
+int  dsb_ctx_coverage(dsb_ctx *ctx, dsb_ref_coverage *out);
+int  dsb_multi_enable_coverage(dsb_multi *m, int on);
+int  dsb_multi_coverage(dsb_multi *m, dsb_ref_coverage *out);  /* merged over the contexts: what one context would count */
+/* the table of `samtools coverage` without its base-quality column: a header line, then one row per reference with
+ * numreads > 0, in ref_ID order.  Same return convention as dsb_format_sam. */
+long dsb_coverage_format(const dsb_index *idx, const dsb_ref_coverage *cov, char *buf, size_t cap);
+
 const char *dsb_strerror(int code);
 const char *dsb_version(void);
 
