@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- `deSAMBA classify` hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--reads-per-gpu R] [--read-len L] [--batches B] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--reads-per-gpu R] [--read-len L] [--batches B] [--dump-outputs DIR] [--full]
 
 Headline workload (BASELINE.json configs[1]: "viral RefSeq index (~1 GB), synthetic 50 kbp ONT-15 %-error reads"): the RefSeq
 index is not in the mount and cannot be downloaded, so a viral-RefSeq-sized one is made here -- a >= 300-Mbp synthetic strain
@@ -11,6 +11,9 @@ are simulated from it (tools/readgen.c).
 
 A step = one pass of the whole device path (encode -> exist-kmer seed lookup -> classify) over one batch that is already
 resident in HBM when the timed region starts; step i runs batch i mod B.  `value` = reads / s over the K timed steps.
+A plain run does only what `value` needs: it builds the index, simulates and uploads the batches, warms up, times the K
+steps, writes --dump-outputs and prints the result line, whose `roofline` and per-kernel times come from the counters of the
+timed steps.  Every other measurement runs with --full alone (where each --no-... option leaves one of them out):
 `end_to_end` = batches streamed from pinned host memory through two contexts of the GPU (H2D, all kernels, D2H inside the
 timed region).  `cli_end_to_end` = the product: the `deSAMBA classify` binary on a FASTQ file in /dev/shm, its own
 "processed in" figure (reader, parser, upload, kernels, SAM writer), SAM compared with the library path; with --gpus N > 1
@@ -625,27 +628,32 @@ def main():
     ap.add_argument("--batches", type=int, default=0, help="distinct batches per GPU (0 = 4, fewer if host memory is short)")
     ap.add_argument("--index-mbp", type=int, default=320, help="size of the synthetic strain collection of the headline index")
     ap.add_argument("--headline", choices=["strain", "demo"], default="strain", help="profiling runs: `demo` puts the reference's demo index in the headline position (nothing is built)")
-    ap.add_argument("--cpu-sample", type=int, default=8192)
-    ap.add_argument("--t1-sample", type=int, default=1024, help="reads of the stock reference's -t 1 vs -t N self-comparison (0 = skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-end-to-end", action="store_true")
-    ap.add_argument("--no-cli", action="store_true", help="skip the runs of the deSAMBA binary (cli_end_to_end)")
-    ap.add_argument("--cli-reads", type=int, default=262144, help="reads per GPU of the CLI run on the headline index")
-    ap.add_argument("--no-demo-index", action="store_true", help="skip the measurements on the reference's demo index")
-    ap.add_argument("--demo-batches", type=int, default=8)
-    ap.add_argument("--demo-steps", type=int, default=8)
-    ap.add_argument("--demo-cli-reads", type=int, default=524288)
-    ap.add_argument("--no-short-reads", action="store_true", help="skip the 1 M x 150 bp measurement (BASELINE configs[2] shape)")
-    ap.add_argument("--no-seed-hbm", action="store_true", help="skip the seed-lookup measurement on synthetic multi-GiB filter tables")
-    ap.add_argument("--seed-hbm-mib", type=int, default=2048, help="size of each synthetic filter table (MiB, power of two 128 .. 16384)")
-    ap.add_argument("--no-budget-build", action="store_true", help="skip building the headline index a second time within an eighth of the device memory (files compared)")
-    ap.add_argument("--no-proxy", action="store_true", help="skip the BASELINE configs[4] proxy (a >= 1-Gbp index built in the run, PacBio-mixed reads)")
-    ap.add_argument("--proxy-mbp", type=int, default=1000)
-    ap.add_argument("--proxy-reads", type=int, default=65536)
-    ap.add_argument("--proxy-parity", type=int, default=2048, help="reads of the proxy's parity sample against the reference's UB-pinned build")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline (the options below); a plain run sets up, warms up, times the steps, writes --dump-outputs and prints the result line")
+    fx = ap.add_argument_group("measurements of a --full run")
+    fx.add_argument("--cpu-sample", type=int, default=8192)
+    fx.add_argument("--t1-sample", type=int, default=1024, help="reads of the stock reference's -t 1 vs -t N self-comparison (0 = skip)")
+    fx.add_argument("--no-cpu-baseline", action="store_true")
+    fx.add_argument("--no-end-to-end", action="store_true")
+    fx.add_argument("--no-cli", action="store_true", help="skip the runs of the deSAMBA binary (cli_end_to_end)")
+    fx.add_argument("--cli-reads", type=int, default=262144, help="reads per GPU of the CLI run on the headline index")
+    fx.add_argument("--no-demo-index", action="store_true", help="skip the measurements on the reference's demo index")
+    fx.add_argument("--demo-batches", type=int, default=8)
+    fx.add_argument("--demo-steps", type=int, default=8)
+    fx.add_argument("--demo-cli-reads", type=int, default=524288)
+    fx.add_argument("--no-short-reads", action="store_true", help="skip the 1 M x 150 bp measurement (BASELINE configs[2] shape)")
+    fx.add_argument("--no-seed-hbm", action="store_true", help="skip the seed-lookup measurement on synthetic multi-GiB filter tables")
+    fx.add_argument("--seed-hbm-mib", type=int, default=2048, help="size of each synthetic filter table (MiB, power of two 128 .. 16384)")
+    fx.add_argument("--no-budget-build", action="store_true", help="skip building the headline index a second time within an eighth of the device memory (files compared)")
+    fx.add_argument("--no-proxy", action="store_true", help="skip the BASELINE configs[4] proxy (a >= 1-Gbp index built in the run, PacBio-mixed reads)")
+    fx.add_argument("--proxy-mbp", type=int, default=1000)
+    fx.add_argument("--proxy-reads", type=int, default=65536)
+    fx.add_argument("--proxy-parity", type=int, default=2048, help="reads of the proxy's parity sample against the reference's UB-pinned build")
     ap.add_argument("--slots", type=int, default=0, help="reads in flight per GPU (0 = library default)")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write the results of the last timed step as DIR/<name>.npy (float64, at most 64 MB)")
     a = ap.parse_args()
+    if not a.full:
+        for k in ("no_budget_build", "no_end_to_end", "no_cpu_baseline", "no_short_reads", "no_proxy", "no_cli", "no_demo_index", "no_seed_hbm"):
+            setattr(a, k, True)
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(a)
@@ -673,7 +681,8 @@ def main():
     if rank == 0:
         if not os.path.exists(D.LIB_PATH):
             G.build()
-        subprocess.check_call([os.path.join(ROOT, "tools", "make_demo_index.sh"), os.path.join(DATA, "demo")], stdout=sys.stderr)   # (one line on stdout)
+        if a.headline == "demo" or not a.no_demo_index:
+            subprocess.check_call([os.path.join(ROOT, "tools", "make_demo_index.sh"), os.path.join(DATA, "demo")], stdout=sys.stderr)   # (one line on stdout)
 
     def barrier():
         if dist:
