@@ -75,6 +75,18 @@ class DsbRefCoverage(C.Structure):
 COVERAGE_FIELDS = ("numreads", "covbases", "aligned_bases", "mapq_sum")
 
 
+class DsbEmOpts(C.Structure):
+    _fields_ = [("max_iter", C.c_uint32), ("reserved", C.c_uint32), ("tol", C.c_double)]
+
+
+class DsbAbundanceSummary(C.Structure):
+    _fields_ = [("reads", C.c_uint64), ("classified", C.c_uint64), ("classes", C.c_uint64), ("iterations", C.c_uint32),
+                ("converged", C.c_uint32), ("max_change", C.c_double), ("min_permille", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+ABUNDANCE_DTYPE = [("numreads", "<u8"), ("uniqreads", "<u8"), ("est_reads", "<f8"), ("read_share", "<f8"), ("copy_share", "<f8")]
+
+
 class DsbChunk(C.Structure):
     _fields_ = [("start", C.c_uint64), ("end", C.c_uint64), ("hist_max_before", C.c_uint32), ("rank", C.c_int32)]
 
@@ -89,7 +101,8 @@ EXPORTS = ["dsb_index_open", "dsb_index_close", "dsb_index_n_ref", "dsb_index_re
            "dsb_ctx_set_taxonomy", "dsb_multi_set_taxonomy", "dsb_batch_taxa", "dsb_multi_taxa",
            "dsb_report_create", "dsb_report_add", "dsb_report_add_sam", "dsb_report_format", "dsb_report_destroy",
            "dsb_ctx_enable_coverage", "dsb_ctx_reset_coverage", "dsb_ctx_coverage", "dsb_multi_enable_coverage", "dsb_multi_coverage",
-           "dsb_coverage_format"]
+           "dsb_coverage_format", "dsb_ctx_enable_abundance", "dsb_ctx_reset_abundance", "dsb_ctx_abundance", "dsb_multi_enable_abundance",
+           "dsb_multi_abundance", "dsb_abundance_format"]
 
 _lib = None
 
@@ -164,6 +177,12 @@ def lib():
     L.dsb_multi_enable_coverage.argtypes = [C.c_void_p, C.c_int]
     L.dsb_multi_coverage.argtypes = [C.c_void_p, C.c_void_p]
     L.dsb_coverage_format.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]; L.dsb_coverage_format.restype = C.c_long
+    L.dsb_ctx_enable_abundance.argtypes = [C.c_void_p, C.c_int, C.c_uint32]
+    L.dsb_ctx_reset_abundance.argtypes = [C.c_void_p]
+    L.dsb_ctx_abundance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.dsb_multi_enable_abundance.argtypes = [C.c_void_p, C.c_int, C.c_uint32]
+    L.dsb_multi_abundance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.dsb_abundance_format.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]; L.dsb_abundance_format.restype = C.c_long
     L.dsb_strerror.argtypes = [C.c_int]; L.dsb_strerror.restype = C.c_char_p
     L.dsb_version.restype = C.c_char_p
     _lib = L
@@ -364,6 +383,22 @@ class Ctx:
         """everything since enable / reset: numpy structured array of n_ref rows (COVERAGE_FIELDS, u64)"""
         return _coverage(lib().dsb_ctx_coverage, self.h, self.index.n_ref, "dsb_ctx_coverage")
 
+    def enable_abundance(self, on=True, min_frac=0.95):
+        """per-reference abundance by EM from now on (each read's candidate set kept in HBM), or off (freed).  min_frac: a read's
+        candidates are the references whose best AS is at least min_frac x its best AS (0 < min_frac <= 1, in steps of 0.001)"""
+        rc = lib().dsb_ctx_enable_abundance(self.h, 1 if on else 0, _permille(min_frac) if on else 0)
+        if rc != 0:
+            raise DsbError(rc, "dsb_ctx_enable_abundance")
+
+    def reset_abundance(self):
+        rc = lib().dsb_ctx_reset_abundance(self.h)
+        if rc != 0:
+            raise DsbError(rc, "dsb_ctx_reset_abundance")
+
+    def abundance(self, max_iter=10000, tol=0.01):
+        """EM over everything since enable / reset: (numpy structured array of n_ref rows, ABUNDANCE_DTYPE; summary dict)"""
+        return _abundance(lib().dsb_ctx_abundance, self.h, self.index.n_ref, max_iter, tol, "dsb_ctx_abundance")
+
     def in_last_batch(self):
         return len(self.reads) if self.reads is not None else getattr(self, "n_uploaded", 0)
 
@@ -435,6 +470,21 @@ class Multi:
         """Ctx.coverage merged over the contexts"""
         return _coverage(lib().dsb_multi_coverage, self.h, self.index.n_ref, "dsb_multi_coverage")
 
+    def enable_abundance(self, on=True, min_frac=0.95):
+        rc = lib().dsb_multi_enable_abundance(self.h, 1 if on else 0, _permille(min_frac) if on else 0)
+        if rc != 0:
+            raise DsbError(rc, "dsb_multi_enable_abundance")
+
+    def reset_abundance(self):
+        for i in range(int(lib().dsb_multi_n(self.h))):
+            rc = lib().dsb_ctx_reset_abundance(lib().dsb_multi_ctx(self.h, i))
+            if rc != 0:
+                raise DsbError(rc, "dsb_ctx_reset_abundance")
+
+    def abundance(self, max_iter=10000, tol=0.01):
+        """Ctx.abundance over the contexts' reads together"""
+        return _abundance(lib().dsb_multi_abundance, self.h, self.index.n_ref, max_iter, tol, "dsb_multi_abundance")
+
     def taxa(self, records=False):
         """Ctx.taxa for the last classify(), in input order"""
         p = C.POINTER(DsbReadTaxon)()
@@ -464,6 +514,43 @@ def _coverage(fn, h, n_ref, what):
     if rc != 0:
         raise DsbError(rc, what)
     return out
+
+
+def _permille(min_frac):
+    f = float(min_frac)
+    if not (0.0 < f <= 1.0) or int(f * 1000 + 0.5) < 1:
+        raise ValueError("min_frac must lie in (0, 1] (steps of 0.001): %r" % (min_frac,))
+    return int(f * 1000 + 0.5)
+
+
+SUMMARY_FIELDS = ("reads", "classified", "classes", "iterations", "converged", "max_change", "min_permille")
+
+
+def _abundance(fn, h, n_ref, max_iter, tol, what):
+    import numpy as np
+    out = np.zeros(n_ref, dtype=ABUNDANCE_DTYPE)
+    s = DsbAbundanceSummary()
+    o = DsbEmOpts(int(max_iter), 0, float(tol))
+    rc = fn(h, C.byref(o), out.ctypes.data_as(C.c_void_p), C.byref(s))
+    if rc != 0:
+        raise DsbError(rc, what)
+    return out, {f: getattr(s, f) for f in SUMMARY_FIELDS}
+
+
+def format_abundance(index, ab, summary):
+    """dsb_abundance_format: the abundance table (bytes) of Ctx/Multi.abundance()'s array and summary dict"""
+    import numpy as np
+    ab = np.ascontiguousarray(ab, dtype=ABUNDANCE_DTYPE)
+    if len(ab) != index.n_ref:
+        raise ValueError("format_abundance: %d rows for %d references" % (len(ab), index.n_ref))
+    s = DsbAbundanceSummary(**{f: summary[f] for f in SUMMARY_FIELDS})
+    cap = 1 << 16
+    while True:
+        buf = C.create_string_buffer(cap)
+        n = lib().dsb_abundance_format(index.h, ab.ctypes.data_as(C.c_void_p), C.byref(s), buf, cap)
+        if n >= 0:
+            return buf.raw[:n]
+        cap *= 4
 
 
 def format_coverage(index, cov):

@@ -847,7 +847,9 @@ static void usage(void)
 	fprintf(stderr, "    --taxonomy FILE  nodes.dmp of the taxids in the reference names (needed by the two options below)\n");
 	fprintf(stderr, "    --report FILE    write the read counts per taxon of the run into FILE, as `analysis ana_meta` prints them for its SAM\n");
 	fprintf(stderr, "    --report-base FILE  the same for `analysis ana_meta_base` (bases weighted by MAPQ)\n");
-	fprintf(stderr, "    --coverage FILE  write the coverage of every reference the run touched into FILE (columns of `samtools coverage`)\n\n");
+	fprintf(stderr, "    --coverage FILE  write the coverage of every reference the run touched into FILE (columns of `samtools coverage`)\n");
+	fprintf(stderr, "    --abundance FILE  write the reads and shares per reference, estimated by EM over each read's near-best references, into FILE\n");
+	fprintf(stderr, "    --abundance-min-frac F  a read's candidates: references whose AS is at least F x its best AS, 0 < F <= 1 [0.95]\n\n");
 }
 
 static double now(void) { struct timeval tv; gettimeofday(&tv, NULL); return tv.tv_sec + tv.tv_usec * 1e-6; }
@@ -905,13 +907,21 @@ static int classify_main(int argc, char **argv)
 	int dev[MAX_DEV], n_dev = 1; dev[0] = 0;
 	a.o.L_min_matching = 170; a.o.min_score = 64; a.o.max_sec_N = 5; a.o.n_slots = 0; a.out = stdout;
 	static const struct option long_opts[] = {{"taxonomy", required_argument, NULL, 1}, {"report", required_argument, NULL, 2}, {"report-base", required_argument, NULL, 3},
-	                                              {"coverage", required_argument, NULL, 4}, {NULL, 0, NULL, 0}};
-	const char *tax_path = NULL, *rep_path[2] = {NULL, NULL}, *cov_path = NULL;
+	                                              {"coverage", required_argument, NULL, 4}, {"abundance", required_argument, NULL, 5},
+	                                              {"abundance-min-frac", required_argument, NULL, 6}, {NULL, 0, NULL, 0}};
+	const char *tax_path = NULL, *rep_path[2] = {NULL, NULL}, *cov_path = NULL, *ab_path = NULL;
+	uint32_t ab_permille = 950;
 	while ((c = getopt_long(argc, argv, "ht:l:r:f:o:s:g:", long_opts, NULL)) >= 0) {
 		if (c == 'h') { usage(); return 0; }
 		else if (c == 1) tax_path = optarg;
 		else if (c == 2 || c == 3) rep_path[c - 2] = optarg;
 		else if (c == 4) cov_path = optarg;
+		else if (c == 5) ab_path = optarg;
+		else if (c == 6) {
+			char *e; const double f = strtod(optarg, &e);
+			if (e == optarg || *e || !(f > 0 && f <= 1) || f * 1000 + 0.5 < 1) die("[classify] --abundance-min-frac takes a number F with 0 < F <= 1 (steps of 0.001)");
+			ab_permille = (uint32_t)(f * 1000 + 0.5);
+		}
 		else if (c == 't') { /* thread count: accepted for compatibility, unused */ }
 		else if (c == 'l') a.o.L_min_matching = atoi(optarg);
 		else if (c == 'r') a.o.max_sec_N = atoi(optarg);
@@ -955,6 +965,8 @@ static int classify_main(int argc, char **argv)
 	}
 	FILE *cov_out = NULL;
 	if (cov_path && !(cov_out = fopen(cov_path, "w"))) { fprintf(stderr, "[xopen] fail to open file '%s'\n", cov_path); exit(1); }
+	FILE *ab_out = NULL;
+	if (ab_path && !(ab_out = fopen(ab_path, "w"))) { fprintf(stderr, "[xopen] fail to open file '%s'\n", ab_path); exit(1); }
 	app_defaults(&a);
 	setvbuf(a.out, NULL, _IOFBF, 8 << 20);
 
@@ -971,6 +983,7 @@ static int classify_main(int argc, char **argv)
 	for (int k = 0; k < a.n_ctx; k++) a.ctx[k] = dsb_multi_ctx(a.multi, k);
 	if (a.rep && (rc = dsb_multi_set_taxonomy(a.multi, a.tx))) { fprintf(stderr, "\n[dsb_ctx_set_taxonomy] %s\n", dsb_strerror(rc)); exit(1); }
 	if (cov_out && (rc = dsb_multi_enable_coverage(a.multi, 1))) { fprintf(stderr, "\n[dsb_ctx_enable_coverage] %s\n", dsb_strerror(rc)); exit(1); }
+	if (ab_out && (rc = dsb_multi_enable_abundance(a.multi, 1, ab_permille))) { fprintf(stderr, "\n[dsb_ctx_enable_abundance] %s\n", dsb_strerror(rc)); exit(1); }
 	double t0 = now(), cpu0 = cputime(); a.t0 = t0;
 	a.thr0 = a.trace ? throttled_usec() : -1;
 	fprintf(stderr, "Start classify\n");
@@ -1007,6 +1020,20 @@ static int classify_main(int argc, char **argv)
 		do { cap *= 4; buf = xrealloc(buf, cap); w = dsb_coverage_format(a.idx, cov, buf, cap); } while (w < 0);
 		if (fwrite(buf, 1, (size_t)w, cov_out) != (size_t)w || fclose(cov_out)) die("[classify] cannot write the coverage table");
 		free(buf); free(cov);
+	}
+	if (ab_out) {
+		/* --abundance: the EM estimate over the whole run's candidate sets, the contexts' sets together */
+		const size_t n_ref = (size_t)dsb_index_n_ref(a.idx);
+		dsb_ref_abundance *ab = xrealloc(NULL, (n_ref ? n_ref : 1) * sizeof *ab);
+		dsb_abundance_summary sum;
+		const double ta = now();
+		if ((rc = dsb_multi_abundance(a.multi, NULL, ab, &sum))) { fprintf(stderr, "[dsb_multi_abundance] %s\n", dsb_strerror(rc)); exit(1); }
+		fprintf(stderr, "[classify] abundance: %llu classified reads, %llu classes, %u EM iterations (%s), %.1f ms\n", (unsigned long long)sum.classified,
+		        (unsigned long long)sum.classes, sum.iterations, sum.converged ? "converged" : "max_iter reached", 1e3 * (now() - ta));
+		size_t cap = 1 << 16; char *buf = NULL; long w;
+		do { cap *= 4; buf = xrealloc(buf, cap); w = dsb_abundance_format(a.idx, ab, &sum, buf, cap); } while (w < 0);
+		if (fwrite(buf, 1, (size_t)w, ab_out) != (size_t)w || fclose(ab_out)) die("[classify] cannot write the abundance table");
+		free(buf); free(ab);
 	}
 	dsb_report_destroy(a.rep);
 	dsb_multi_destroy(a.multi);

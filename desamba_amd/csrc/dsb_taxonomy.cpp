@@ -368,3 +368,26 @@ extern "C" long dsb_report_format(const dsb_report *R, int by_base, char *buf, s
 	memcpy(buf, o.data(), o.size()); buf[o.size()] = 0;
 	return (long)o.size();
 }
+
+// ---- the per-reference abundance table: fixed formats, so that equal doubles give equal text ----
+extern "C" long dsb_abundance_format(const dsb_index *x, const dsb_ref_abundance *ab, const dsb_abundance_summary *sum, char *buf, size_t cap)
+{
+	if (!x || !ab || !sum || (!buf && cap)) return -1;
+	size_t o = 0; int w;
+#define EMIT(...) do { w = snprintf(buf + o, cap > o ? cap - o : 0, __VA_ARGS__); if (w < 0 || (size_t)w >= (cap > o ? cap - o : 0)) return -1; o += (size_t)w; } while (0)
+	EMIT("#reads=%llu\tclassified=%llu\tclasses=%llu\titerations=%u\tconverged=%s\tmax_change=%.6e\tmin_frac=%.3f\n", (unsigned long long)sum->reads,
+	     (unsigned long long)sum->classified, (unsigned long long)sum->classes, sum->iterations, sum->converged ? "yes" : "no", sum->max_change,
+	     sum->min_permille / 1000.0);
+	EMIT("#rname\ttaxid\tlength\tnumreads\tuniqreads\testreads\treadshare\tcopyshare\n");
+	const uint64_t n_ref = dsb_index_n_ref(x);
+	for (uint64_t r = 0; r < n_ref; r++) {
+		const dsb_ref_abundance &a = ab[r];
+		if (!a.numreads) continue;
+		const char *name = dsb_index_ref_name(x, (uint32_t)r);
+		const uint32_t tid = dsb_ref_taxid(name);
+		EMIT("%s\t%u\t%llu\t%llu\t%llu\t%.3f\t%.6e\t%.6e\n", name, tid == DSB_TID_NONE ? 0u : tid, (unsigned long long)dsb_index_ref_len(x, (uint32_t)r),
+		     (unsigned long long)a.numreads, (unsigned long long)a.uniqreads, a.est_reads, a.read_share, a.copy_share);
+	}
+#undef EMIT
+	return (long)o;
+}

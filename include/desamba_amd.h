@@ -297,6 +297,51 @@ int  dsb_multi_coverage(dsb_multi *m, dsb_ref_coverage *out);  /* merged over th
  * numreads > 0, in ref_ID order.  Same return convention as dsb_format_sam. */
 long dsb_coverage_format(const dsb_index *idx, const dsb_ref_coverage *cov, char *buf, size_t cap);
 
+/* ---- per-reference abundance of a run by expectation-maximisation on the GPU.
+ * Every read with hits (those dsb_batch_fetch hands out, whatever max_sec_N is) has a candidate set: the references r < n_ref
+ * whose best AS S_r has S_r * 1000 >= S_max * min_permille (S_max: the read's best AS), ascending, each once.  Reads are not
+ * joined by name.  A distinct set is a class k with c_k reads.  With L_r = dsb_index_ref_len(r) and N classified reads, the
+ * read shares a_r start at 1 / R on the R references that occur in some class, and one iteration is
+ *     a'_r = (a_r / L_r) * (sum over the classes k holding r of c_k / sum_{s in k} a_s / L_s) / N,
+ * until the first iteration with max_r N |a'_r - a_r| < tol or max_iter iterations.  The doubles do not depend on how the reads
+ * were split into batches, input slots or contexts, nor on the run: every sum has a fixed order. */
+typedef struct {
+	uint64_t numreads;     /* classified reads whose set holds the reference */
+	uint64_t uniqreads;    /* ... whose set is that reference alone */
+	double   est_reads;    /* N * a_r */
+	double   read_share;   /* a_r */
+	double   copy_share;   /* (a_r / L_r) / sum_s (a_s / L_s) */
+} dsb_ref_abundance;
+typedef struct {
+	uint32_t max_iter;     /* >= 1; default 10000 */
+	uint32_t reserved;     /* 0 */
+	double   tol;          /* >= 0, in reads; default 0.01 */
+} dsb_em_opts;
+typedef struct {
+	uint64_t reads;        /* reads the batches held */
+	uint64_t classified;   /* N: reads with a candidate set */
+	uint64_t classes;      /* distinct candidate sets */
+	uint32_t iterations;   /* iterations run (the state returned is the one after the last) */
+	uint32_t converged;    /* 1: the last iteration met tol (also for a run without classified reads); 0: max_iter ran out */
+	double   max_change;   /* max_r N |a'_r - a_r| of the last iteration (0 when none ran) */
+	uint32_t min_permille; /* the threshold the sets were formed with */
+	uint32_t reserved;
+} dsb_abundance_summary;
+/* on: every batch from now on ends with k_em_collect, which appends each read's set to a store in HBM (16 bytes per read + 4 per
+ * hit; grown between batches, DSB_ENOMEM rather than a lost read); min_permille in 1 .. 1000 (1000: ties
+ * only), else DSB_EINVAL.  On again: new threshold, store emptied.  off: freed; nothing is allocated or launched while off. */
+int  dsb_ctx_enable_abundance(dsb_ctx *ctx, int on, uint32_t min_permille);
+int  dsb_ctx_reset_abundance(dsb_ctx *ctx);                   /* empty the store, keep the allocation */
+/* the estimate over everything since enable / reset (the store is left as it is): out has dsb_index_n_ref entries.  opts NULL:
+ * the defaults.  DSB_EINVAL when abundance is off or an option is out of range. */
+int  dsb_ctx_abundance(dsb_ctx *ctx, const dsb_em_opts *opts, dsb_ref_abundance *out, dsb_abundance_summary *summary);
+int  dsb_multi_enable_abundance(dsb_multi *m, int on, uint32_t min_permille);
+/* the contexts' stores together, solved on the first context's device: bitwise what one context would give */
+int  dsb_multi_abundance(dsb_multi *m, const dsb_em_opts *opts, dsb_ref_abundance *out, dsb_abundance_summary *summary);
+/* a '#' summary line, a header line, then one row per reference with numreads > 0, in ref_ID order (DESIGN 2.10 has the
+ * formats).  Same return convention as dsb_format_sam. */
+long dsb_abundance_format(const dsb_index *idx, const dsb_ref_abundance *ab, const dsb_abundance_summary *summary, char *buf, size_t cap);
+
 const char *dsb_strerror(int code);
 const char *dsb_version(void);
 
