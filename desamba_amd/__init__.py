@@ -50,7 +50,8 @@ class DsbTiming(C.Structure):
                 ("n_regrow", C.c_uint32), ("seed_scan", C.c_uint32),
                 ("n_occ", C.c_uint64), ("n_mem", C.c_uint64), ("n_sa", C.c_uint64), ("ref_bases", C.c_uint64),
                 ("main_occ", C.c_uint64), ("main_mem", C.c_uint64), ("main_sa", C.c_uint64), ("main_ref_bases", C.c_uint64),
-                ("n_heavy_mw", C.c_uint32), ("n_requeue", C.c_uint32), ("upload_bytes", C.c_uint64)]
+                ("n_heavy_mw", C.c_uint32), ("n_requeue", C.c_uint32), ("upload_bytes", C.c_uint64),
+                ("anc_pool_asked", C.c_uint64), ("anc_pool_cap", C.c_uint64)]
 
 
 class DsbBuildStats(C.Structure):
@@ -265,6 +266,11 @@ class Ctx:
         if rc != 0:
             raise DsbError(rc, "dsb_ctx_create(device %d)" % device)
         self.reads = None
+        # (reads, count) staged in each input slot, and those of the batch the last run() ran: taxa(), sam() and in_last_batch()
+        # speak of that batch, as dsb_batch_taxa does
+        self.slot = 0
+        self.staged = {}
+        self.ran = (None, 0)
 
     def close(self):
         if self.h:
@@ -291,6 +297,7 @@ class Ctx:
         rc = lib().dsb_ctx_select_slot(self.h, slot)
         if rc != 0:
             raise DsbError(rc, "dsb_ctx_select_slot(%d)" % slot)
+        self.slot = slot
 
     def upload_text(self, text_ptr, text_len, seq_off, seq_len, n):
         """sequences inside one host blob (pinned if it came from dsb_host_alloc): one H2D copy, no per-read gather"""
@@ -298,12 +305,14 @@ class Ctx:
         rc = lib().dsb_batch_upload_text(self.h, text_ptr, text_len, seq_off, seq_len, n)
         if rc != 0:
             raise DsbError(rc, "dsb_batch_upload_text")
+        self.staged[self.slot] = (None, int(n))
 
     def upload(self, reads):
         self.reads = reads
         rc = lib().dsb_batch_upload(self.h, reads, len(reads))
         if rc != 0:
             raise DsbError(rc, "dsb_batch_upload")
+        self.staged[self.slot] = (reads, len(reads))
 
     def upload_fastq(self, path, skip=0, max_reads=1 << 62):
         """stage a plain-text FASTQ file straight into HBM; returns the number of reads"""
@@ -312,12 +321,14 @@ class Ctx:
         if n < 0:
             raise DsbError(int(n), "dsb_batch_upload_fastq(%s)" % path)
         self.n_uploaded = int(n)
+        self.staged[self.slot] = (None, int(n))
         return int(n)
 
     def run(self):
         rc = lib().dsb_batch_run(self.h)
         if rc != 0:
             raise DsbError(rc, "dsb_batch_run")
+        self.ran = self.staged.get(self.slot, (None, 0))
 
     def fetch(self, strict=True):
         res = DsbResult()
@@ -400,11 +411,13 @@ class Ctx:
         return _abundance(lib().dsb_ctx_abundance, self.h, self.index.n_ref, max_iter, tol, "dsb_ctx_abundance")
 
     def in_last_batch(self):
-        return len(self.reads) if self.reads is not None else getattr(self, "n_uploaded", 0)
+        return self.ran[1]
 
     def sam(self, res, full=False, reads=None):
         """Format a whole batch exactly as output_one_result_sam does (src/cly_mt.c:245-344)."""
-        return format_sam(self.index, reads if reads is not None else self.reads, res, self.opts.max_sec_N, full)
+        if reads is None:
+            reads = self.ran[0] if self.ran[0] is not None else self.reads      # (a batch staged from text: names set by the caller)
+        return format_sam(self.index, reads, res, self.opts.max_sec_N, full)
 
 
 def format_sam(index, reads, res, max_sec_N=5, full=False):

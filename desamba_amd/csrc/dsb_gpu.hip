@@ -967,10 +967,11 @@ __device__ inline uint32_t wave_max_u32(uint32_t v) { for (int o = 32; o; o >>= 
 // ascending order by repeated selection: each round the lanes find the smallest qualifying ref_ID above the last one taken
 // (|C| + 1 rounds over the hits).  Lane j keeps element j for the first 64; a longer set is selected a second time as it is written.
 // The host reserved n records and cap_hout elements behind (base_s, base_e); thread 0 of the grid moves the counters past them.
+// hash_mask keeps the low DSB_EM_HASH_BITS of the hash (all 64 by default; a hash of 0 becomes 1 either way).
 __global__ void __launch_bounds__(256) k_em_collect(const DsbReadOut *__restrict__ rout, const DsbHitOut *__restrict__ hout, const unsigned int *__restrict__ counters,
                                                     uint32_t cap_hout, uint32_t n, uint32_t n_ref, uint32_t min_permille, DsbEmSet *__restrict__ sets,
                                                     uint32_t *__restrict__ elems, unsigned long long *em_cnt, uint64_t base_s, uint64_t base_e,
-                                                    uint64_t cap_sets, uint64_t cap_elems)
+                                                    uint64_t cap_sets, uint64_t cap_elems, uint64_t hash_mask)
 {
 	const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
 	const uint32_t nh = counters[1] < cap_hout ? counters[1] : cap_hout;
@@ -1002,6 +1003,7 @@ __global__ void __launch_bounds__(256) k_em_collect(const DsbReadOut *__restrict
 		hash = dsb_em_mix(hash, best); last = best; k++;
 	}
 	if (e + k > cap_elems) { if (lane == 0) atomicOr(em_cnt + 2, 1ull); return; }
+	hash &= hash_mask;                                            // (DSB_EM_HASH_BITS: collisions on purpose)
 	if (lane == 0) { DsbEmSet o; o.hash = hash ? hash : 1; o.off = (uint32_t)e; o.len = k; sets[s] = o; }
 	if (k <= 64) { if (lane < k) elems[e + lane] = mine; return; }
 	last = -1;
@@ -1276,6 +1278,7 @@ struct DsbKnobs {
 	long hout_cap = 0, sms_cap = 0, anc_cap_rt = 0, upload_chunk_kb = 0, step_limit_rt = 0, group_head = -1;
 	int upload_threads = 0, seed_scan = -1, heavy_mw = -1, heavy_first = 0;
 	bool heavy_preds_set = false; uint32_t heavy_preds = 0;
+	uint64_t em_hash_mask = ~0ull;     // DSB_EM_HASH_BITS=1..64: k_em_collect keeps only the low bits of a set's hash (tests of the collision path)
 	bool anchor_kernel = true; long anc_pool_rt = 0;   // DSB_ANCHOR_KERNEL=0: the anchor stage inside k_classify (no k_anchor); DSB_ANC_POOL_RT: anchors the pool holds (diagnostics)
 	bool scan_look_set = false; DsbScanLook scan_look;   // DSB_SCAN_LOOK=after_seed,back_fwd,fwd_n,stride_n: k_seed_scan's look-ahead (experiments; default dsb_scan_look_for)
 	std::string order_file;
@@ -1297,6 +1300,7 @@ static void knobs_read(DsbKnobs &k)
 	k.heavy_mw = getenv("DSB_HEAVY_MW") ? (int)num("DSB_HEAVY_MW", 0) : -1;
 	k.heavy_first_set = getenv("DSB_HEAVY_FIRST") != nullptr; k.heavy_first = (int)num("DSB_HEAVY_FIRST", 0);
 	k.anchor_kernel = num("DSB_ANCHOR_KERNEL", 1) != 0;
+	if (getenv("DSB_EM_HASH_BITS")) { const long b = num("DSB_EM_HASH_BITS", 64); k.em_hash_mask = b >= 64 ? ~0ull : b < 1 ? 1ull : (1ull << b) - 1; }
 	k.anc_pool_rt = num("DSB_ANC_POOL_RT", 0); if (getenv("DSB_ANC_POOL_RT") && k.anc_pool_rt < 1) k.anc_pool_rt = 1;
 	if (const char *e = getenv("DSB_HEAVY_PREDS")) { k.heavy_preds_set = true; k.heavy_preds = (uint32_t)strtoul(e, nullptr, 10); }
 	if (const char *e = getenv("DSB_ORDER_FILE")) k.order_file = e;
@@ -2163,7 +2167,7 @@ static int batch_run_locked(dsb_ctx *c, std::unique_lock<std::mutex> *turn)
 		hipLaunchKernelGGL(k_em_collect, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, (const DsbReadOut *)c->d_rout, (const DsbHitOut *)c->d_hout,
 		                   (const unsigned int *)c->d_counters, (uint32_t)c->cap_hout, (uint32_t)n, (uint32_t)dsb_index_n_ref(c->idx), c->em_permille,
 		                   c->d_em_sets, c->d_em_elems, c->d_em_cnt, (uint64_t)c->em_used_sets, (uint64_t)c->em_used_elems, (uint64_t)c->em_cap_sets,
-		                   (uint64_t)c->em_cap_elems);
+		                   (uint64_t)c->em_cap_elems, (uint64_t)c->knobs.em_hash_mask);
 	}
 	if (dbg) {
 		static const char *nm[10] = {"seed_vector", "fast_classify", "resolve_tree", "slow+resolve", "hash_build", "sdp_middle", "sdp_right", "sdp_left", "sort/filter", "primary"};
@@ -2196,7 +2200,11 @@ static int batch_run_locked(dsb_ctx *c, std::unique_lock<std::mutex> *turn)
 	unsigned long long wk[12] = {0};                   // work counters: main launch, early launch, second runs
 	HIPCHK(hipMemcpy(&c->p1, c->d_counters + 2, 8, hipMemcpyDeviceToHost));
 	HIPCHK(hipMemcpy(&c->timing.n_retry, c->d_counters + 6, 4, hipMemcpyDeviceToHost));
-	HIPCHK(hipMemcpy(&c->timing.n_requeue, c->d_counters + 12, 4, hipMemcpyDeviceToHost));
+	{	// counters [12] reads handed over as heavy, [15] anchors k_anchor asked its pool for: one copy
+		unsigned int h[4] = {0, 0, 0, 0};
+		HIPCHK(hipMemcpy(h, c->d_counters + 12, sizeof h, hipMemcpyDeviceToHost));
+		c->timing.n_requeue = h[0]; c->timing.anc_pool_asked = h[3]; c->timing.anc_pool_cap = c->cap_apool;
+	}
 	// A batch that made the device wait for its early launches (no read handed over, nothing run again: the wait was for the
 	// heaviest reads themselves -- on the demo index one read in a thousand lies in a tandem repeat and takes 150 ms on a
 	// wavefront, longer than the main launch) gets more of its heaviest reads onto eight wavefronts next time: 16 -> 32 -> 64.

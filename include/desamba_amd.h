@@ -99,6 +99,9 @@ typedef struct {
 	uint32_t n_heavy_mw;   /* reads of the early launch that ran on several wavefronts each (k_classify_heavy) */
 	uint32_t n_requeue;    /* reads given up by their wavefront as heavy (quadratic sparse DP) and run again by a workgroup of wavefronts */
 	uint64_t upload_bytes; /* bytes the sequences of the batch took over PCIe: bases / 4 from dsb_batch_upload (packed by the gather threads), the text from dsb_batch_upload_text */
+	uint64_t anc_pool_asked;   /* anchors k_anchor asked its pool for: 0 when k_anchor did not run (the anchor stage ran inside k_classify) or no read of the
+	                              batch had anchors; above anc_pool_cap, the reads that found the pool full walked their islands again in k_classify */
+	uint64_t anc_pool_cap;     /* anchors the pool of k_anchor holds */
 } dsb_timing;
 
 /* load_idx (src/idx.c:1103-1160, src/bwt.c:68-104): read <dir>/deSAMBA.* into host memory */

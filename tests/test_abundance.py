@@ -9,6 +9,7 @@ import subprocess
 import pytest
 
 from conftest import GOLDEN, ROOT
+from reductions_lib import candidate_set, check_against, classes_of, em, sets_from_result
 
 CLI = os.path.join(ROOT, "desamba_amd", "bin", "deSAMBA")
 SYNTH = os.path.join(GOLDEN, "synth")
@@ -17,81 +18,6 @@ HEADER = b"#rname\ttaxid\tlength\tnumreads\tuniqreads\testreads\treadshare\tcopy
 
 
 # ---------------------------------------------------------------- the definition, in numpy
-
-def candidate_set(hits, n_ref, permille):
-    """hits: (ref_ID, AS) of one read -> its candidate set (sorted tuple; empty: the read takes no part)"""
-    hits = [(r, s) for r, s in hits if r < n_ref]
-    if not hits:
-        return ()
-    smax = max(s for _, s in hits)
-    return tuple(sorted({r for r, s in hits if s * 1000 >= smax * permille}))
-
-
-def classes_of(sets):
-    out = {}
-    for s in sets:
-        if s:
-            out[s] = out.get(s, 0) + 1
-    return out
-
-
-def em(classes, lens, max_iter=10000, tol=0.01):
-    """the EM of DESIGN 2.10 over {set: count}: (a, iterations, converged, last max change)"""
-    import numpy as np
-    n_ref = len(lens)
-    L = np.array([float(x) if x else 1.0 for x in lens])
-    keys = sorted(classes)
-    c = np.array([classes[k] for k in keys], dtype=np.float64)
-    N = c.sum()
-    a = np.zeros(n_ref)
-    if not keys:
-        return a, 0, True, 0.0
-    flat_ref = np.concatenate([np.array(k, dtype=np.int64) for k in keys])
-    flat_cls = np.concatenate([np.full(len(k), i, dtype=np.int64) for i, k in enumerate(keys)])
-    present = np.bincount(flat_ref, minlength=n_ref) > 0
-    a[present] = 1.0 / present.sum()
-    chg = 0.0
-    for it in range(1, max_iter + 1):
-        w = a / L
-        denom = np.bincount(flat_cls, weights=w[flat_ref], minlength=len(keys))
-        coef = np.where(denom > 0, c / np.where(denom > 0, denom, 1.0), 0.0)
-        t = np.bincount(flat_ref, weights=coef[flat_cls], minlength=n_ref)
-        an = w * t / N
-        chg = float(np.max(np.abs(an - a)) * N)
-        a = an
-        if chg < tol:
-            return a, it, True, chg
-    return a, max_iter, False, chg
-
-
-def counts_of(classes, n_ref):
-    numreads, uniq = [0] * n_ref, [0] * n_ref
-    for s, c in classes.items():
-        for r in s:
-            numreads[r] += c
-        if len(s) == 1:
-            uniq[s[0]] += c
-    return numreads, uniq
-
-
-def check_against(ab, summ, sets, lens, label=""):
-    """GPU result (max_iter=200, tol=0) against the numpy EM over the same candidate sets"""
-    import numpy as np
-    n_ref = len(lens)
-    cl = classes_of(sets)
-    nr, ur = counts_of(cl, n_ref)
-    assert list(ab["numreads"]) == nr, label
-    assert list(ab["uniqreads"]) == ur, label
-    assert summ["classified"] == sum(cl.values()), label
-    assert summ["classes"] == len(cl), label
-    a, it, _, _ = em(cl, lens, max_iter=200, tol=0.0)
-    assert summ["iterations"] == 200 and not summ["converged"], label
-    N = sum(cl.values())
-    exp = N * a
-    got = ab["est_reads"]
-    assert np.all(np.abs(got - exp) <= 1e-9 * np.maximum(np.abs(exp), 1e-300) + 1e-12), (label, np.max(np.abs(got - exp)))
-    assert np.all((got > 0) == (np.array(nr) > 0)), label
-
 
 def taxid_of(name):
     """the second '|' field as strtok / strtoul read it, 0 if absent"""
@@ -120,14 +46,6 @@ def table(names, lens, ab, summ):
 def ref_table(idx):
     n = idx.n_ref
     return [idx.ref_name(r) for r in range(n)], [idx.ref_len(r) for r in range(n)]
-
-
-def sets_from_result(res, n_reads, n_ref, permille):
-    out = []
-    for i in range(n_reads):
-        rr = res.reads[i]
-        out.append(candidate_set([(res.hits[rr.first + k].ref_ID, res.hits[rr.first + k].sum_score) for k in range(rr.n)], n_ref, permille))
-    return out
 
 
 # ---------------------------------------------------------------- host side (no GPU)

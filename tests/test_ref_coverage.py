@@ -8,6 +8,7 @@ import subprocess
 import pytest
 
 from conftest import GOLDEN, ROOT
+from reductions_lib import accumulate, counted_records
 
 CLI = os.path.join(ROOT, "desamba_amd", "bin", "deSAMBA")
 SYNTH = os.path.join(GOLDEN, "synth")
@@ -25,54 +26,6 @@ def table(names, lens, cov):
             out.append(b"%s\t1\t%d\t%d\t%d\t%s\t%s\t%s\n" % (names[r].encode(), L, nr, cb, (b"%g" % (100.0 * cb / L)),
                                                                   (b"%g" % (ab / L)), (b"%.1f" % (mq / nr))))
     return b"".join(out)
-
-
-def union_len(iv):
-    tot, cur_s, cur_e = 0, None, None
-    for s, e in sorted(iv):
-        if cur_e is None or s > cur_e:
-            if cur_e is not None:
-                tot += cur_e - cur_s
-            cur_s, cur_e = s, e
-        else:
-            cur_e = max(cur_e, e)
-    return tot + (cur_e - cur_s if cur_e is not None else 0)
-
-
-def accumulate(n_ref, records, lens):
-    """records: (ref, t_st, t_ed, mapq) of every counted record -> [(numreads, covbases, aligned_bases, mapq_sum)] per reference"""
-    iv = [[] for _ in range(n_ref)]
-    cnt = [[0, 0, 0] for _ in range(n_ref)]
-    for ref, ts, te, mq in records:
-        L = lens[ref]
-        s, e = min(ts, L), min(te, L)
-        cnt[ref][0] += 1; cnt[ref][2] += mq
-        if e > s:
-            iv[ref].append((s, e)); cnt[ref][1] += e - s
-    return [(c[0], union_len(iv[r]), c[1], c[2]) for r, c in enumerate(cnt)]
-
-
-def mapq_pri(h, n):
-    d = (h[0].sum_score - h[1].sum_score) & 0xffffffff if n > 1 else 0
-    if n == 1 or d > 5:
-        return 30
-    v = (d << 2) & 0xffffffff
-    return v - (1 << 32) if v >= 1 << 31 else v
-
-
-def counted_records(res, n_reads):
-    """the records dsb_format_sam prints without FLAG 0x100: the primary and the supplementary ones (pri_index 0)"""
-    out = []
-    for i in range(n_reads):
-        rr = res.reads[i]
-        if not rr.n:
-            continue
-        h = [res.hits[rr.first + k] for k in range(rr.n)]
-        mq = mapq_pri(h, rr.n)
-        for k, c in enumerate(h):
-            if k == 0 or c.pri_index == 0:
-                out.append((c.ref_ID, c.t_st, c.t_ed, mq if k == 0 else min(mq, 30)))
-    return out
 
 
 def ref_table(idx):

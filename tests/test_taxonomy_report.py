@@ -12,6 +12,7 @@ import zlib
 import pytest
 
 from conftest import GOLDEN, ROOT
+from reductions_lib import nodes_table, walk_golden_sam
 
 CLI = os.path.join(ROOT, "desamba_amd", "bin", "deSAMBA")
 ANA = os.path.join(GOLDEN, "analysis")
@@ -31,14 +32,6 @@ def analysis(sam_path, nodes, by_base):
     p = subprocess.run([CLI, "analysis", "ana_meta_base" if by_base else "ana_meta", sam_path, nodes], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     assert p.returncode == 0, p.stderr
     return strip_prefix(p.stdout)
-
-
-def nodes_table(path):
-    parent = {}
-    for line in open(path):
-        f = [x.strip() for x in line.split("|")]
-        parent[int(f[0])] = int(f[1])
-    return parent
 
 
 def trimmed_nodes(path):
@@ -234,41 +227,6 @@ def test_cli_report_equals_two_step_pipeline(demo, tmp_path):
     (tmp_path / "empty.fq").write_bytes(b"")
     out, r, rb = cli_run(tmp_path, [tmp_path / "empty.fq"], tag="empty")
     assert out.read_bytes() == b"" and r == b"" and rb == b""
-
-
-def walk_golden_sam(path, table, max_tid):
-    """the per-read taxon recomputed from the golden SAM: the walk over each read's own records"""
-    def tid_of(rname):
-        f = [x for x in rname.split(b"|") if x]
-        return int(f[1]) if len(f) > 1 else 0
-
-    def descends(t, held):
-        p = t
-        while True:
-            if p == held:
-                return True
-            if p < 1 or p == 0xffffffff or p > max_tid:
-                return False
-            p = 0 if p == 1 else table.get(p, 0xffffffff)
-    groups = []
-    for line in open(path, "rb").read().splitlines():
-        f = [x for x in line.split(b"\t") if x]
-        if groups and groups[-1][0] == f[0]:
-            groups[-1][1].append(f)
-        else:
-            groups.append((f[0], [f]))
-    out = []
-    for _, recs in groups:
-        f0 = recs[0]
-        if f0[2].startswith(b"*") or tid_of(f0[2]) > max_tid:
-            out.append(0); continue
-        tid, score = tid_of(f0[2]), int(f0[11].split(b":")[2])
-        for f in recs[1:] if score else []:
-            t = tid_of(f[2])
-            if int(f[11].split(b":")[2]) == score and t <= max_tid and descends(t, tid):
-                tid = t
-        out.append(tid)
-    return out
 
 
 @pytest.mark.gpu
