@@ -13,6 +13,7 @@
 //   refinfo      {seq_l, seq_offset} per reference
 //   qmem/qlv     MAPQ tables computed on the host with the reference's expression (src/cly_mt.c:413-437)
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #ifdef DSB_HOST_EMU
 struct uint2 { uint32_t x, y; };
@@ -79,6 +80,30 @@ struct DsbReadOut { uint32_t first, n; int32_t status; uint32_t fast; uint32_t n
 // per read, written by k_anchor (the anchor stage of a batch's main launch): where its anchors lie in the anchor pool, how many,
 // the loop steps the walk spent and whether k_classify takes them (use = 0: it walks the islands itself, as without k_anchor)
 struct DsbAncRec { uint32_t off, n, lsteps, use; };
+
+// ---- batch descriptors ----------------------------------------------------------------------
+struct DsbReadDesc {
+	uint64_t seq_off;      // into the ASCII blob
+	uint64_t bin_off;      // into the byte-strand blob (points at the 64-byte left pad)
+	uint64_t pk_off;       // into the packed blob, in u64 words: F words then R words (+1 pad word each)
+	uint64_t bit_off;      // into the hit-bit blob, in u64 words: F words then R words
+	uint32_t len;
+	uint32_t n_win;        // len - k + 1 (0 if len < 40)
+	uint32_t n_words;      // ceil(n_win / 64)
+	int32_t  hist_max;     // max read length over the reads before this one (oracle U4)
+	uint64_t seed_off;     // into the seed blob, in DsbSeed records: (len >> 1) + 64 per read, forward strand first, reverse at + (len >> 2)
+};
+struct DsbWordDesc { uint32_t read; uint32_t word; };   // word: bit 31 = strand R, low bits = word index
+
+// the wave slots' scratch of the classify kernels (dsb_gpu.hip: size_arena)
+struct DsbSlotArena {
+	uint8_t *base; size_t stride;                 // per-slot bytes
+	size_t off_seeds, off_anc, off_anc_tmp, off_hit, off_hit_tmp, off_sms, off_sc, off_mem, off_spset, off_scorev,
+	       off_sortkey, off_sortidx, off_win, off_lane_anc, off_lane_sp, off_top, off_round;
+	uint32_t max_len;                             // longest read the arena was sized for
+	uint32_t sms_cap;                             // entries of the match-node arena (off_sms)
+	uint32_t anc_cap, hit_cap;                    // entries of the anchor / chain arrays
+};
 
 // ---- arena sizes (per wave slot) ---------------------------------------------------------------
 #define DSB_QPAD_L 64

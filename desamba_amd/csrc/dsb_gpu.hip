@@ -7,6 +7,7 @@
 //                 src/cly.c:360-398), two hashed 1-bit probes (get_exist_kmer, src/cly.c:956-972),
 //                 one ballot -> one 64-bit word of hit bits per wave iteration.  HBM/L3-bound gather.
 //   k_classify    persistent, one read per wavefront, everything after the probes (dsb_classify_dev.h)
+// The run reductions that read a batch's hits after its last classify launch (taxa, coverage, abundance): dsb_reductions.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -29,23 +30,6 @@
 #undef DSB_NS
 #include "dsb_host.h"
 #include "dsb_sam_fields.h"
-#include "dsb_taxonomy.h"
-
-#define HIPCHK(e) do { hipError_t _e = (e); if (_e != hipSuccess) { fprintf(stderr, "[desamba_amd] HIP error %s at %s:%d\n", hipGetErrorString(_e), __FILE__, __LINE__); return DSB_ENODEV; } } while (0)
-
-// ---- batch descriptors ----------------------------------------------------------------------
-struct DsbReadDesc {
-	uint64_t seq_off;      // into the ASCII blob
-	uint64_t bin_off;      // into the byte-strand blob (points at the 64-byte left pad)
-	uint64_t pk_off;       // into the packed blob, in u64 words: F words then R words (+1 pad word each)
-	uint64_t bit_off;      // into the hit-bit blob, in u64 words: F words then R words
-	uint32_t len;
-	uint32_t n_win;        // len - k + 1 (0 if len < 40)
-	uint32_t n_words;      // ceil(n_win / 64)
-	int32_t  hist_max;     // max read length over the reads before this one (oracle U4)
-	uint64_t seed_off;     // into the seed blob, in DsbSeed records: (len >> 1) + 64 per read, forward strand first, reverse at + (len >> 2)
-};
-struct DsbWordDesc { uint32_t read; uint32_t word; };   // word: bit 31 = strand R, low bits = word index
 
 // Compilation units.  k_classify inlines every stage function (dsb_wave.h: a callee would save ~64 callee-saved vector registers per call and
 // lane -- 58 GB written per launch in round 3 -- and pin local state in scratch memory), which makes it, its two siblings and k_classify_heavy
@@ -440,15 +424,6 @@ __global__ void __launch_bounds__(1024) k_order(const uint32_t *score, uint32_t 
 #endif  // DSB_UNIT_HOST (the small kernels)
 
 // ---- classify kernel: persistent waves, one read each ------------------------------------------
-struct DsbSlotArena {
-	uint8_t *base; size_t stride;                 // per-slot bytes
-	size_t off_seeds, off_anc, off_anc_tmp, off_hit, off_hit_tmp, off_sms, off_sc, off_mem, off_spset, off_scorev,
-	       off_sortkey, off_sortidx, off_win, off_lane_anc, off_lane_sp, off_top, off_round;
-	uint32_t max_len;                             // longest read the arena was sized for
-	uint32_t sms_cap;                             // entries of the match-node arena (off_sms)
-	uint32_t anc_cap, hit_cap;                    // entries of the anchor / chain arrays
-};
-
 // Work items come from an atomic counter; with `list` == nullptr item k is read k, otherwise read list[k] (the
 // longest-processing-time-first order of k_order).
 #ifndef DSB_WAVES_PER_EU
@@ -819,342 +794,8 @@ __global__ void k_collect_retry(const DsbReadOut *rout, uint32_t n, uint32_t *li
 	(void)clear_n;
 }
 
-// One lane per read, after the batch's last classify work: the taxon of the read's own records as `deSAMBA analysis`
-// reads them back from the SAM (dsb_taxonomy.cpp, ana_get_tid src/analysis.c:1271-1330).  The records are the ones
-// dsb_format_sam prints -- the primary, the supplementary ones, the secondary ones up to max_sec -- taken where the classify
-// kernels left them (DsbReadOut / DsbHitOut); MAPQ and the CIGAR's length come from dsb_sam_fields.h, as the writer's do.
-// Each parent walk stops after `bound` steps (the deepest chain of the taxonomy + 2: the loader rejects cycles); a read the
-// host must walk itself is flagged DSB_TAXON_HOST: a first record with score 0 or a taxid above max_tid (the read ends
-// there and its other records become reads of their own), a reference whose name does not come back from the SAM as it
-// is, or a walk that ran out of steps.
-__global__ void __launch_bounds__(256) k_read_taxon(const DsbReadOut *__restrict__ rout, const DsbHitOut *__restrict__ hout, const unsigned int *__restrict__ counters,
-                                                    uint32_t cap_hout, const DsbReadDesc *__restrict__ rd, uint32_t n, const uint32_t *__restrict__ parent,
-                                                    const uint32_t *__restrict__ ref_tid, uint32_t n_ref, uint32_t max_tid, uint32_t bound, int max_sec, dsb_read_taxon *__restrict__ out)
-{
-	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-	if (i >= n) return;
-	const uint32_t nh = counters[1] < cap_hout ? counters[1] : cap_hout;
-	const DsbReadOut r = rout[i];
-	dsb_read_taxon t; t.taxid = 0; t.score = 0; t.len = 0; t.mapq = 0; t.flags = 0; t.pad = 0;
-	const uint32_t nrec = (uint64_t)r.first + r.n > nh ? 0u : r.n;   // (what dsb_batch_fetch hands out)
-	if (nrec) {
-		const dsb_hit *h = reinterpret_cast<const dsb_hit *>(hout + r.first);
-		const uint32_t read_l = rd[i].len;
-		const uint32_t t0 = h[0].ref_ID < n_ref ? ref_tid[h[0].ref_ID] : DSB_TID_NONE;
-		t.flags = DSB_TAXON_CLASSIFIED;
-		t.score = h[0].sum_score; t.len = dsb_sam_cigar_len(h, read_l, false); t.mapq = (uint8_t)dsb_sam_mapq_pri(h, nrec);
-		if (t0 == DSB_TID_NONE || t0 > max_tid || t.score == 0) { t.flags |= DSB_TAXON_HOST; t.taxid = t0 <= max_tid ? t0 : 0; }
-		else {
-			uint32_t tid = t0;
-			for (int pass = 0; pass <= 1 && !(t.flags & DSB_TAXON_HOST); pass++)
-				for (uint32_t k = 1; k < nrec; k++) {
-					const dsb_hit *c = h + k;
-					if (!dsb_sam_shown(c, pass, max_sec)) continue;
-					const uint32_t rt = c->ref_ID < n_ref ? ref_tid[c->ref_ID] : DSB_TID_NONE;
-					if (rt == DSB_TID_NONE) { t.flags |= DSB_TAXON_HOST; break; }
-					if (c->sum_score != t.score || rt > max_tid) continue;
-					uint32_t p = rt, steps = 0;
-					for (; steps < bound; steps++) {                                // is rt at or below the taxon held?
-						if (p == tid) { tid = rt; break; }
-						if (p < 1 || p == DSB_TID_NONE || p > max_tid) break;
-						p = parent[p];
-					}
-					if (steps == bound) { t.flags |= DSB_TAXON_HOST; break; }
-				}
-			t.taxid = tid;
-		}
-	}
-	out[i] = t;
-}
-
-// Per-reference coverage (dsb_ctx_enable_coverage).  One wavefront per read, after the batch's last classify work: each
-// record printed without FLAG 0x100 (dsb_sam_counted) adds to its reference's counters (lane 0) and sets the bits of its interval
-// [min(t_st, LN), min(t_ed, LN)), the lanes striding over its words.  The bits are set by agent-scope atomic ORs, never by plain
-// stores: two records may share a word, and their workgroups may sit on XCDs whose L2s are not coherent with each other.  A
-// reference's bits start at word word_off[ref]; bits at LN and beyond are never set.
-__global__ void __launch_bounds__(256) k_ref_cover(const DsbReadOut *__restrict__ rout, const DsbHitOut *__restrict__ hout, const unsigned int *__restrict__ counters,
-                                                   uint32_t cap_hout, uint32_t n, const uint64_t *__restrict__ ref_len, const uint64_t *__restrict__ word_off,
-                                                   uint32_t n_ref, uint64_t *bits, dsb_ref_coverage *cov)
-{
-	const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-	if (i >= n) return;
-	const uint32_t nh = counters[1] < cap_hout ? counters[1] : cap_hout;
-	const DsbReadOut r = rout[i];
-	const uint32_t nrec = (uint64_t)r.first + r.n > nh ? 0u : r.n;   // (what dsb_batch_fetch hands out)
-	if (!nrec) return;
-	const dsb_hit *h = reinterpret_cast<const dsb_hit *>(hout + r.first);
-	const int mq_pri = dsb_sam_mapq_pri(h, nrec);
-	for (uint32_t k = 0; k < nrec; k++) {
-		const dsb_hit *c = h + k;
-		if (!dsb_sam_counted(c, k) || c->ref_ID >= n_ref) continue;
-		const uint64_t ln = ref_len[c->ref_ID];
-		const uint64_t s = c->t_st < ln ? c->t_st : ln, e = c->t_ed < ln ? c->t_ed : ln;
-		if (lane == 0) {
-			dsb_ref_coverage *o = cov + c->ref_ID;
-			__hip_atomic_fetch_add(&o->numreads, (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-			if (e > s) __hip_atomic_fetch_add(&o->aligned_bases, e - s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-			const int mq = k ? dsb_sam_mapq_sup(mq_pri) : mq_pri;
-			if (mq) __hip_atomic_fetch_add(&o->mapq_sum, (uint64_t)mq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		}
-		if (e <= s) continue;
-		uint64_t *w = bits + word_off[c->ref_ID];
-		for (uint64_t q = (s >> 6) + lane; q <= ((e - 1) >> 6); q += 64) {
-			const uint64_t lo = q * 64 < s ? s - q * 64 : 0, hi = q * 64 + 64 > e ? e - q * 64 : 64;   // bits [lo, hi) of word q
-			const uint64_t m = (hi == 64 ? ~0ull : (1ull << hi) - 1) & (~0ull << lo);
-			__hip_atomic_fetch_or(w + q, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		}
-	}
-}
-
-// End of a run: covbases, a segmented popcount over words [w0, w0 + nw) of the bitmap (bits[q - w0] holds word q), balanced by words
-// rather than by reference.  Each wavefront takes DSB_COVER_CHUNK words, finds the reference of its first word by binary search in
-// the word offsets (empty references skipped: the last r with word_off[r] <= a) and adds one partial sum per reference it spans.
-#define DSB_COVER_CHUNK 1024
-__global__ void __launch_bounds__(256) k_cover_count(const uint64_t *__restrict__ bits, uint64_t w0, uint64_t nw, const uint64_t *__restrict__ word_off,
-                                                     uint32_t n_ref, dsb_ref_coverage *cov)
-{
-	const uint64_t a = w0 + ((uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * DSB_COVER_CHUNK, end = w0 + nw;
-	const uint32_t lane = threadIdx.x & 63;
-	if (a >= end) return;
-	const uint64_t b = a + DSB_COVER_CHUNK < end ? a + DSB_COVER_CHUNK : end;
-	uint32_t lo = 0, hi = n_ref;                           // word_off[lo] <= a < word_off[hi] (= the bitmap's size for hi = n_ref)
-	while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (word_off[mid] <= a) lo = mid; else hi = mid; }
-	for (uint32_t r = lo;; r++) {
-		const uint64_t s = word_off[r] > a ? word_off[r] : a, e = word_off[r + 1] < b ? word_off[r + 1] : b;
-		uint32_t sum = 0;                                  // (at most 64 bits x DSB_COVER_CHUNK words)
-		for (uint64_t q = s + lane; q < e; q += 64) sum += (uint32_t)__popcll(bits[q - w0]);
-		for (int o = 32; o; o >>= 1) sum += __shfl_xor(sum, o, 64);
-		if (lane == 0 && sum) __hip_atomic_fetch_add(&cov[r].covbases, (uint64_t)sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		if (e >= b) break;
-	}
-}
-
-// before a count: covbases = 0 (the other three counters stay)
-__global__ void __launch_bounds__(256) k_cover_clear(dsb_ref_coverage *cov, uint32_t n_ref)
-{
-	const uint32_t r = blockIdx.x * 256 + threadIdx.x;
-	if (r < n_ref) cov[r].covbases = 0;
-}
-
-// dsb_multi_coverage: dst |= src over nw words (the contexts' bitmaps merged before the count)
-__global__ void __launch_bounds__(256) k_cover_or(uint64_t *__restrict__ dst, const uint64_t *__restrict__ src, uint64_t nw)
-{
-	for (uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x; q < nw; q += (uint64_t)gridDim.x * 256) dst[q] |= src[q];
-}
-
-// ---- per-reference abundance by EM (dsb_ctx_enable_abundance) ----
-// A read's candidate set in the run-wide store: its references (ascending ref_ID) are elems[off .. off + len); hash is
-// dsb_em_mix over them, never 0.  An unclassified read has an empty record (len 0, hash 0).  Batch b's reads own records
-// [base_s, base_s + n) in input order and its elements lie at base_e + (the read's first hit in the hit buffer), so no two
-// reads share room and no atomics place them; the gaps (hits that are not candidates) cost 4 bytes per hit.
-struct DsbEmSet { uint64_t hash; uint32_t off, len; };
-// the store's counters: [0] records, [1] elements (gaps included), [2] nonzero = a set found no room (nothing written)
-#define DSB_EM_CNT 4
-__device__ __host__ inline uint64_t dsb_em_mix(uint64_t h, uint32_t r)
-{
-	h ^= (uint64_t)r + 0x9e3779b97f4a7c15ull + (h << 6) + (h >> 2);
-	h ^= h >> 31; h *= 0xbf58476d1ce4e5b9ull; h ^= h >> 29;
-	return h;
-}
-#define DSB_EM_HASH0 0x2545f4914f6cdd1dull
-
-__device__ inline uint32_t wave_min_u32(uint32_t v) { for (int o = 32; o; o >>= 1) { const uint32_t t = __shfl_xor(v, o, 64); v = t < v ? t : v; } return v; }
-__device__ inline uint32_t wave_max_u32(uint32_t v) { for (int o = 32; o; o >>= 1) { const uint32_t t = __shfl_xor(v, o, 64); v = t > v ? t : v; } return v; }
-
-// One wavefront per read, after the batch's last classify work (the hits dsb_batch_fetch hands out: k_ref_cover's nrec rule).
-// S_max = the largest AS over the read's hits on references < n_ref; the candidate set is the distinct ref_IDs of the hits with
-// AS * 1000 >= S_max * min_permille (a reference's best hit passes exactly when one of its hits does).  The set is formed in
-// ascending order by repeated selection: each round the lanes find the smallest qualifying ref_ID above the last one taken
-// (|C| + 1 rounds over the hits).  Lane j keeps element j for the first 64; a longer set is selected a second time as it is written.
-// The host reserved n records and cap_hout elements behind (base_s, base_e); thread 0 of the grid moves the counters past them.
-// hash_mask keeps the low DSB_EM_HASH_BITS of the hash (all 64 by default; a hash of 0 becomes 1 either way).
-__global__ void __launch_bounds__(256) k_em_collect(const DsbReadOut *__restrict__ rout, const DsbHitOut *__restrict__ hout, const unsigned int *__restrict__ counters,
-                                                    uint32_t cap_hout, uint32_t n, uint32_t n_ref, uint32_t min_permille, DsbEmSet *__restrict__ sets,
-                                                    uint32_t *__restrict__ elems, unsigned long long *em_cnt, uint64_t base_s, uint64_t base_e,
-                                                    uint64_t cap_sets, uint64_t cap_elems, uint64_t hash_mask)
-{
-	const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-	const uint32_t nh = counters[1] < cap_hout ? counters[1] : cap_hout;
-	if (blockIdx.x == 0 && threadIdx.x == 0) { em_cnt[0] = base_s + n; em_cnt[1] = base_e + nh; }
-	if (i >= n) return;
-	const DsbReadOut r = rout[i];
-	const uint32_t nrec = (uint64_t)r.first + r.n > nh ? 0u : r.n;
-	const uint64_t s = base_s + i, e = base_e + (nrec ? r.first : 0u);
-	if (s >= cap_sets) { if (lane == 0) atomicOr(em_cnt + 2, 1ull); return; }
-	const DsbHitOut *h = hout + r.first;
-	uint32_t smax = 0; bool valid = false;
-	for (uint32_t q = lane; q < nrec; q += 64) if (h[q].ref_ID < n_ref) { valid = true; smax = h[q].sum_score > smax ? h[q].sum_score : smax; }
-	if (!__ballot(valid)) {                                        // unclassified (or only hits on references beyond the index)
-		if (lane == 0) { DsbEmSet o; o.hash = 0; o.off = (uint32_t)e; o.len = 0; sets[s] = o; }
-		return;
-	}
-	smax = wave_max_u32(smax);
-	const uint64_t thr = (uint64_t)smax * min_permille;
-	uint32_t k = 0, mine = 0; int64_t last = -1; uint64_t hash = DSB_EM_HASH0;
-	for (;;) {
-		uint32_t best = 0xffffffffu;
-		for (uint32_t q = lane; q < nrec; q += 64) {
-			const uint32_t ref = h[q].ref_ID;
-			if (ref < n_ref && (int64_t)ref > last && ref < best && (uint64_t)h[q].sum_score * 1000u >= thr) best = ref;
-		}
-		best = wave_min_u32(best);
-		if (best == 0xffffffffu) break;
-		if (k == lane) mine = best;
-		hash = dsb_em_mix(hash, best); last = best; k++;
-	}
-	if (e + k > cap_elems) { if (lane == 0) atomicOr(em_cnt + 2, 1ull); return; }
-	hash &= hash_mask;                                            // (DSB_EM_HASH_BITS: collisions on purpose)
-	if (lane == 0) { DsbEmSet o; o.hash = hash ? hash : 1; o.off = (uint32_t)e; o.len = k; sets[s] = o; }
-	if (k <= 64) { if (lane < k) elems[e + lane] = mine; return; }
-	last = -1;
-	for (uint32_t j = 0; j < k; j++) {
-		uint32_t best = 0xffffffffu;
-		for (uint32_t q = lane; q < nrec; q += 64) {
-			const uint32_t ref = h[q].ref_ID;
-			if (ref < n_ref && (int64_t)ref > last && ref < best && (uint64_t)h[q].sum_score * 1000u >= thr) best = ref;
-		}
-		best = wave_min_u32(best);
-		if (lane == 0) elems[e + j] = best;
-		last = best;
-	}
-}
-
-// class build: the (hash, set index) keys of the store
-__global__ void __launch_bounds__(256) k_em_keys(const DsbEmSet *__restrict__ sets, uint32_t n, uint64_t *__restrict__ key, uint32_t *__restrict__ val)
-{
-	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-	if (i < n) { key[i] = sets[i].hash; val[i] = i; }
-}
-
-__device__ inline bool em_same_set(const DsbEmSet &a, const DsbEmSet &b, const uint32_t *elems)
-{
-	if (a.len != b.len) return false;
-	for (uint32_t j = 0; j < a.len; j++) if (elems[a.off + j] != elems[b.off + j]) return false;
-	return true;
-}
-
-// after the sort by hash: head[i] = 1 where a class starts (the empty records, hash 0, come first and start none).  Neighbours of one hash are compared element by element; two different
-// sets of one hash set *collide (the host then orders each run of one hash by the sets themselves and marks again).
-__global__ void __launch_bounds__(256) k_em_mark(const DsbEmSet *__restrict__ sets, const uint32_t *__restrict__ elems, const uint32_t *__restrict__ order,
-                                                 uint32_t n, uint32_t *__restrict__ head, unsigned int *collide)
-{
-	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-	if (i >= n) return;
-	uint32_t hd = sets[order[i]].len != 0;                        // (empty records: hash 0, sorted in front of every class)
-	if (i && hd) {
-		const DsbEmSet a = sets[order[i - 1]], b = sets[order[i]];
-		if (a.hash == b.hash) {
-			hd = em_same_set(a, b, elems) ? 0u : 1u;
-			if (hd) atomicOr(collide, 1u);
-		}
-	}
-	head[i] = hd;
-}
-
-// classes from the inclusive scan of head (cls[i] = class of sorted position i, plus one): the first position of each class and the
-// length of its set
-__global__ void __launch_bounds__(256) k_em_classes(const DsbEmSet *__restrict__ sets, const uint32_t *__restrict__ order, const uint32_t *__restrict__ head,
-                                                    const uint32_t *__restrict__ cls, uint32_t n, uint32_t *__restrict__ start, uint32_t *__restrict__ len)
-{
-	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-	if (i >= n || !head[i]) return;
-	const uint32_t k = cls[i] - 1;
-	start[k] = i;
-	len[k] = sets[order[i]].len;
-}
-
-// the class elements in class order (cref[coff[k] ..) = the set of class k, ascending) and the class of each (for the transposed CSR)
-__global__ void __launch_bounds__(256) k_em_fill(const DsbEmSet *__restrict__ sets, const uint32_t *__restrict__ elems, const uint32_t *__restrict__ order,
-                                                 const uint32_t *__restrict__ start, const uint32_t *__restrict__ coff, uint32_t K, uint32_t *__restrict__ cref,
-                                                 uint32_t *__restrict__ ccls)
-{
-	const uint32_t k = blockIdx.x * 256 + threadIdx.x;
-	if (k >= K) return;
-	const DsbEmSet s = sets[order[start[k]]];
-	for (uint32_t j = 0; j < s.len; j++) { cref[coff[k] + j] = elems[s.off + j]; ccls[coff[k] + j] = k; }
-}
-
-// per reference: the first entry of its classes in the (ref, class)-sorted pairs (lower bound; roff[n_ref] = the pair count)
-__global__ void __launch_bounds__(256) k_em_rowoff(const uint32_t *__restrict__ sref, uint32_t m, uint32_t n_ref, uint32_t *__restrict__ roff)
-{
-	const uint32_t r = blockIdx.x * 256 + threadIdx.x;
-	if (r > n_ref) return;
-	uint32_t lo = 0, hi = m;
-	while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (sref[mid] < r) lo = mid + 1; else hi = mid; }
-	roff[r] = lo;
-}
-
-// per reference: numreads, uniqreads, and the starting share (1 / R for a reference in some class, else 0)
-__global__ void __launch_bounds__(256) k_em_init(const uint32_t *__restrict__ roff, const uint32_t *__restrict__ scls, const uint32_t *__restrict__ start,
-                                                 const uint32_t *__restrict__ clen, uint32_t n_ref, double a0, double *__restrict__ a,
-                                                 unsigned long long *__restrict__ numreads, unsigned long long *__restrict__ uniqreads)
-{
-	const uint32_t r = blockIdx.x * 256 + threadIdx.x;
-	if (r >= n_ref) return;
-	unsigned long long nr = 0, ur = 0;
-	for (uint32_t q = roff[r]; q < roff[r + 1]; q++) {
-		const uint32_t k = scls[q], c = start[k + 1] - start[k];
-		nr += c;
-		if (clen[k] == 1) ur += c;
-	}
-	numreads[r] = nr; uniqreads[r] = ur;
-	a[r] = roff[r + 1] > roff[r] ? a0 : 0.0;
-}
-
-// EM state on the device: chg[it & 1] = max_r N |a'_r - a_r| of iteration it (as the bits of a non-negative double: their
-// unsigned order is the doubles' order); done / iters: the iteration after which the criterion held
-struct DsbEmState { unsigned long long chg[2]; unsigned int done, iters; };
-
-// iteration it, first half: per class k, denom = sum over its set (ascending ref_ID) of a_s / L_s, coef = c_k / denom (0 for a
-// denominator that underflowed to 0).  Every thread sees the same state: once iteration it - 1 met the criterion, all return.
-__global__ void __launch_bounds__(256) k_em_class(const uint32_t *__restrict__ cref, const uint32_t *__restrict__ coff, const uint32_t *__restrict__ start,
-                                                  uint32_t K, const double *__restrict__ a, const double *__restrict__ L, double tol, uint32_t it,
-                                                  DsbEmState *st, double *__restrict__ coef)
-{
-	if (st->done) return;
-	const uint32_t k = blockIdx.x * 256 + threadIdx.x;
-	if (it > 0 && __longlong_as_double((long long)st->chg[(it - 1) & 1]) < tol) {
-		if (k == 0) { st->done = 1; st->iters = it; }
-		return;
-	}
-	if (k == 0) st->chg[it & 1] = 0;
-	if (k >= K) return;
-	double d = 0.0;
-	for (uint32_t q = coff[k]; q < coff[k + 1]; q++) { const uint32_t s = cref[q]; d += a[s] / L[s]; }
-	coef[k] = d > 0.0 ? (double)(start[k + 1] - start[k]) / d : 0.0;
-}
-
-// second half: one wavefront per reference.  t = sum of coef over the reference's classes in class order -- lane j takes the
-// classes j, j + 64, ... in order, then a fixed butterfly over the 64 partial sums -- and a'_r = (a_r / L_r) t / N.
-__global__ void __launch_bounds__(256) k_em_ref(const uint32_t *__restrict__ roff, const uint32_t *__restrict__ scls, const double *__restrict__ coef,
-                                                uint32_t n_ref, const double *__restrict__ a, const double *__restrict__ L, double N, uint32_t it,
-                                                DsbEmState *st, double *__restrict__ an)
-{
-	if (st->done) return;
-	const uint32_t r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-	if (r >= n_ref) return;
-	const uint32_t q0 = roff[r], q1 = roff[r + 1];
-	if (q0 == q1) { if (lane == 0) an[r] = 0.0; return; }
-	double t = 0.0;
-	for (uint32_t q = q0 + lane; q < q1; q += 64) t += coef[scls[q]];
-	for (int o = 32; o; o >>= 1) t += __shfl_xor(t, o, 64);
-	if (lane) return;
-	const double v = (a[r] / L[r]) * t / N;
-	an[r] = v;
-	const double d = fabs(v - a[r]) * N;
-	atomicMax(&st->chg[it & 1], (unsigned long long)__double_as_longlong(d));
-}
-
-// dsb_multi_abundance: the offsets of a context's sets, moved behind the elements of the contexts before it
-__global__ void __launch_bounds__(256) k_em_rebase(DsbEmSet *sets, uint32_t n, uint32_t base)
-{
-	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-	if (i < n) sets[i].off += base;
-}
-
 // ================================== host side ====================================================
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
+#include "dsb_ctx.h"
 #include <mutex>
 #include <thread>
 #include <algorithm>
@@ -1256,34 +897,6 @@ static void stage_release(DsbStaged *s)
 	stage_free(s);
 }
 
-// ---- a staged input batch ("input slot"): what dsb_batch_upload* leaves in HBM ------------------------------
-struct InSlot {
-	DsbReadDesc *d_rd = nullptr; char *d_ascii = nullptr; size_t cap_rd = 0, cap_ascii = 0;
-	std::vector<DsbReadDesc> h_rd;
-	size_t n_reads = 0; uint64_t n_words_total = 0, total_bases = 0, total_windows = 0, seed_entries = 0; uint32_t max_len = 0, min_len = 0;
-	uint32_t *d_scan_order = nullptr; size_t cap_scan_order = 0;   // reads longest first (ragged batches only), for k_seed_scan
-	bool ragged = false;
-	uint64_t upload_bytes = 0;     // what the sequences of this batch took over PCIe
-	bool packed = false;           // d_ascii holds 2-bit packed sequences (dsb_batch_upload's gather), not text
-};
-
-// pinned staging of dsb_batch_upload: one per gather thread, two chunks each (one is filled while the other is on its way)
-struct UpStage { char *buf[2] = {nullptr, nullptr}; hipEvent_t ev[2] = {nullptr, nullptr}; bool used[2] = {false, false}; hipStream_t st = nullptr; };
-
-// Diagnostic and tuning switches of the environment, read ONCE per context (dsb_ctx_create; dsb_ctx_reload_env for tests that
-// change them on a living context): nothing on the per-batch path calls getenv.  -1 / 0 = not set.
-struct DsbKnobs {
-	bool upload_text = false;          // DSB_UPLOAD_TEXT: dsb_batch_upload gathers the sequences as text (round 3's form) instead of packing them
-	bool debug = false, upload_trace = false, no_turn = false, turn_whole_run = false, no_group = false, heavy_first_set = false;
-	long hout_cap = 0, sms_cap = 0, anc_cap_rt = 0, upload_chunk_kb = 0, step_limit_rt = 0, group_head = -1;
-	int upload_threads = 0, seed_scan = -1, heavy_mw = -1, heavy_first = 0;
-	bool heavy_preds_set = false; uint32_t heavy_preds = 0;
-	uint64_t em_hash_mask = ~0ull;     // DSB_EM_HASH_BITS=1..64: k_em_collect keeps only the low bits of a set's hash (tests of the collision path)
-	bool anchor_kernel = true; long anc_pool_rt = 0;   // DSB_ANCHOR_KERNEL=0: the anchor stage inside k_classify (no k_anchor); DSB_ANC_POOL_RT: anchors the pool holds (diagnostics)
-	bool scan_look_set = false; DsbScanLook scan_look;   // DSB_SCAN_LOOK=after_seed,back_fwd,fwd_n,stride_n: k_seed_scan's look-ahead (experiments; default dsb_scan_look_for)
-	std::string order_file;
-};
-static bool g_upload_trace = false;           // (the buffer helpers below have no context at hand: DSB_UPLOAD_TRACE of the last knobs_read)
 static void knobs_read(DsbKnobs &k)
 {
 	auto num = [](const char *name, long dflt) { const char *e = getenv(name); return e ? atol(e) : dflt; };
@@ -1314,52 +927,6 @@ static void knobs_read(DsbKnobs &k)
 	g_upload_trace = k.upload_trace;
 }
 
-struct dsb_ctx {
-	bool ek_dense = false;                         // filter tables more than ~4 % full (DsbStaged::ek_dense, or the synthetic tables' fill)
-	DsbKnobs knobs;
-	dsb_index *idx = nullptr; int device = 0; hipStream_t stream = nullptr;
-	DsbStaged *staged = nullptr; DsbDevIndex dx;
-	std::vector<InSlot> in; int cur = 0;          // input slots (dsb_ctx_select_slot); upload / run / fetch work on slot `cur`
-	// per-run buffers (grown on demand to the largest staged batch)
-	DsbWordDesc *d_wd = nullptr; uint8_t *d_bin = nullptr; uint64_t *d_pk = nullptr; uint64_t *d_bits = nullptr;
-	size_t cap_wd = 0, cap_bin = 0, cap_pk = 0, cap_bits = 0;
-	DsbReadOut *d_rout = nullptr; DsbHitOut *d_hout = nullptr; size_t cap_rout = 0, cap_hout = 0;
-	unsigned int *d_counters = nullptr;            // u32: [0] work, [1] hits, [2..3] u64 table-1 probes, [4] early work, [6] listed reads, [7] work of the second run, [8] third run list, [9] its work; u64 x 4 at +16 (main launch), +24 (early launch), +32 (second runs): occ, MEM searches, SA lookups, reference bases
-	DsbSlotArena arena; int n_slots = 0, n_extra = 0;   // n_extra: slots behind the n_slots of the main launch, for the early launch of the heaviest reads (batches of >= 4096 reads)
-	DsbSlotArena arena_big; int n_slots_big = 0;  // second run of reads that outgrew an arena or their loop budget
-	DsbSlotArena arena_anc; int n_slots_anc = 0;  // k_anchor's slots (only the island walk's scratch)
-	DsbAncRec *d_arec = nullptr; DsbAnchor *d_apool = nullptr; size_t cap_arec = 0, cap_apool = 0;   // k_anchor's per-read records and anchor pool
-	uint32_t hint_len = 0;                           // the read length the caller announced (dsb_opts.max_read_len): arenas are never built for less
-	unsigned mw_reads = 16; bool mw_grown = false; int mw_calm = 0;   // reads of the early launch that get eight wavefronts each: follows what the batches of this ctx show (end of dsb_batch_run)
-	uint32_t *d_score = nullptr, *d_order = nullptr, *d_heavy = nullptr; size_t cap_score = 0, cap_order = 0, cap_heavy = 0;
-	DsbSeed *d_seeds = nullptr; DsbSeedInfo *d_sinfo = nullptr; size_t cap_seeds = 0, cap_sinfo = 0;   // seed lists of the batch (k_seed_scan)
-	uint8_t *d_summ = nullptr; int summ_shift = 0;   // summary of exist table 0 in use (the staged index's, or none with synthetic tables)
-	uint8_t *syn0 = nullptr, *syn1 = nullptr; bool seed_only = false;   // dsb_ctx_use_synthetic_filter
-	bool bits_valid = false, seeds_valid = false;   // what the last run left on the device (stage dumps)
-	unsigned n_early = 0;                          // reads of the last run that went through the early launch
-	std::vector<DsbReadOut> h_rout; std::vector<DsbHitOut> h_hout;
-	std::vector<dsb_read_result> res_reads;
-	int hist_max = 0;
-	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; dsb_timing timing; unsigned long long p1 = 0;
-	hipStream_t stream3 = nullptr; hipEvent_t ev_heavy3 = nullptr;    // k_classify_heavy: several wavefronts on each of the very heaviest reads
-	hipStream_t stream2 = nullptr; hipEvent_t ev_order = nullptr, ev_heavy = nullptr, ev_hprobe = nullptr, ev_cls = nullptr, ev_cls_wait = nullptr;   // the heaviest reads run beside the seed probe
-	uint32_t *dbg_host = nullptr, *dbg_dev = nullptr;
-	std::vector<UpStage> up; size_t up_chunk = 0;     // pinned staging of dsb_batch_upload (upload_gather)
-	dsb_opts opts;
-	// taxonomy (dsb_ctx_set_taxonomy): the parent table and each reference's taxid in HBM, one k_read_taxon launch per batch
-	const dsb_taxonomy *tx = nullptr; uint32_t *d_parent = nullptr, *d_ref_tid = nullptr;
-	dsb_read_taxon *d_taxa = nullptr; size_t cap_taxa = 0; std::vector<dsb_read_taxon> h_taxa;
-	bool taxa_run = false, taxa_done = false;     // k_read_taxon ran for the batch of the current slot / its records are fetched and completed
-	// per-reference coverage (dsb_ctx_enable_coverage): a bitmap of one bit per reference base (each reference from a word boundary,
-	// cov_off: the prefix sum of ceil(LN / 64), n_ref + 1 words), the lengths, and the four counters per reference; one k_ref_cover launch per batch
-	uint64_t *d_cov_bits = nullptr, *d_cov_off = nullptr, *d_cov_len = nullptr; dsb_ref_coverage *d_cov = nullptr; uint64_t cov_words = 0;
-	// per-reference abundance (dsb_ctx_enable_abundance): the run's candidate sets (DsbEmSet + their elements, grown geometrically
-	// between batches), the store's counters, and the reads the batches held; one k_em_collect launch per batch
-	DsbEmSet *d_em_sets = nullptr; uint32_t *d_em_elems = nullptr; unsigned long long *d_em_cnt = nullptr;
-	size_t em_cap_sets = 0, em_cap_elems = 0, em_used_sets = 0, em_used_elems = 0; uint64_t em_reads = 0; uint32_t em_permille = 0;
-	dsb_ctx() { memset(&dx, 0, sizeof dx); memset(&arena, 0, sizeof arena); memset(&arena_big, 0, sizeof arena_big); memset(&arena_anc, 0, sizeof arena_anc); memset(&timing, 0, sizeof timing); memset(&opts, 0, sizeof opts); }
-};
-
 // HIP spreads the streams of a process over GPU_MAX_HW_QUEUES hardware queues.  Two contexts on a device have eight streams
 // between them (kernels x 3, uploads), and a transfer on a stream that shares its hardware queue with the other context's
 // persistent k_classify launch waits for that launch to end: measured, the upload of a batch beside the other batch's kernels
@@ -1374,7 +941,6 @@ extern "C" int dsb_device_count(void)
 }
 
 static int ensure_buffers(dsb_ctx *c, size_t n, uint32_t max_len, uint64_t bin_bytes, uint64_t pk_words, uint64_t bit_words, uint64_t seed_entries);
-template <class T> static int grow(T **p, size_t *cap, size_t need);
 struct SeqView { const char *p; uint32_t len; };
 static int upload_views(dsb_ctx *c, const SeqView *reads, size_t n, const char *ext_text = nullptr, size_t ext_len = 0, const uint64_t *ext_off = nullptr);
 static int upload_stages(dsb_ctx *c, int T);
@@ -1396,9 +962,7 @@ extern "C" void dsb_ctx_destroy(dsb_ctx *c)
 	if (c->stream2) hipStreamSynchronize(c->stream2);
 	for (InSlot &s : c->in) { hipFree(s.d_rd); hipFree(s.d_ascii); hipFree(s.d_scan_order); }
 	hipFree(c->d_wd); hipFree(c->d_bin); hipFree(c->d_pk); hipFree(c->d_bits);
-	hipFree(c->d_parent); hipFree(c->d_ref_tid); hipFree(c->d_taxa);
-	hipFree(c->d_cov_bits); hipFree(c->d_cov_off); hipFree(c->d_cov_len); hipFree(c->d_cov);
-	hipFree(c->d_em_sets); hipFree(c->d_em_elems); hipFree(c->d_em_cnt);
+	reductions_release(c);
 	hipFree(c->d_rout); hipFree(c->d_hout); hipFree(c->d_counters); hipFree(c->arena.base); hipFree(c->arena_big.base); hipFree(c->arena_anc.base); hipFree(c->d_arec); hipFree(c->d_apool); hipFree(c->d_score); hipFree(c->d_order); hipFree(c->d_heavy); hipFree(c->d_seeds); hipFree(c->d_sinfo); hipFree(c->syn0); hipFree(c->syn1);
 	if (c->dbg_host) hipHostFree(c->dbg_host);
 	for (UpStage &u : c->up) { if (u.st) { hipStreamSynchronize(u.st); hipStreamDestroy(u.st); } for (int k = 0; k < 2; k++) { if (u.ev[k]) hipEventDestroy(u.ev[k]); if (u.buf[k]) hipHostFree(u.buf[k]); } }
@@ -1566,20 +1130,6 @@ extern "C" void *dsb_host_alloc(size_t bytes)
 }
 extern "C" void dsb_host_free(void *p) { if (p) hipHostFree(p); }
 
-template <class T> static int grow(T **p, size_t *cap, size_t need)
-{
-	if (need <= *cap) return 0;
-	// (an allocation on the per-batch path: hipFree / hipMalloc wait for the device and were seen to stall a sibling context's
-	// batch for seconds -- the hints of dsb_ctx_create exist to keep this from happening; DSB_UPLOAD_TRACE shows each one)
-	const bool tr = g_upload_trace; struct timespec t0, t1; if (tr) clock_gettime(CLOCK_MONOTONIC, &t0);
-	const size_t old = *cap;
-	if (*p) hipFree(*p);
-	size_t n = need + need / 8 + 1024;
-	if (hipMalloc((void **)p, n * sizeof(T)) != hipSuccess) { *p = nullptr; *cap = 0; return DSB_ENOMEM; }
-	*cap = n;
-	if (tr) { clock_gettime(CLOCK_MONOTONIC, &t1); fprintf(stderr, "[upload] a device buffer grew from %zu to %zu elements of %zu bytes (needed: %zu) in %.3f s\n", old, n, sizeof(T), need, (t1.tv_sec - t0.tv_sec) + 1e-9 * (t1.tv_nsec - t0.tv_nsec)); }
-	return 0;
-}
 static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // slots [n_slots, n_slots + DSB_HEAVY_SLOTS) belong to the early launch of the heaviest reads (dsb_batch_run)
@@ -1954,7 +1504,6 @@ static void launch_classify(K kern, dsb_ctx *c, hipStream_t st, unsigned grid, c
 }
 
 static int batch_run_locked(dsb_ctx *c, std::unique_lock<std::mutex> *turn);
-static int em_reserve(dsb_ctx *c, size_t n_sets, size_t n_elems);
 extern "C" int dsb_batch_run(dsb_ctx *c)
 {
 	if (!c) return DSB_EINVAL;
@@ -1971,7 +1520,7 @@ static int batch_run_locked(dsb_ctx *c, std::unique_lock<std::mutex> *turn)
 	size_t n = s.n_reads;
 	memset(&c->timing, 0, sizeof c->timing);
 	c->timing.upload_bytes = s.upload_bytes;
-	c->taxa_run = c->tx != nullptr && n == 0; c->taxa_done = false;
+	c->taxa.run = c->taxa.tx != nullptr && n == 0; c->taxa.done = false;
 	if (n == 0) return DSB_OK;
 	HIPCHK(hipMemsetAsync(c->d_counters, 0, 256, c->stream));
 	HIPCHK(hipEventRecord(c->ev[0], c->stream));
@@ -2142,33 +1691,9 @@ static int batch_run_locked(dsb_ctx *c, std::unique_lock<std::mutex> *turn)
 			c->timing.n_regrow = n3;
 		}
 	}
-	if (c->tx) {
-		// the per-read taxa: after every classify launch of the batch (the second runs and the run after a regrown hit buffer included)
-		if (grow(&c->d_taxa, &c->cap_taxa, n)) return DSB_ENOMEM;
-		const uint32_t bound = c->tx->max_depth + 2;
-		hipLaunchKernelGGL(k_read_taxon, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const DsbReadOut *)c->d_rout, (const DsbHitOut *)c->d_hout,
-		                   (const unsigned int *)c->d_counters, (uint32_t)c->cap_hout, (const DsbReadDesc *)s.d_rd, (uint32_t)n, (const uint32_t *)c->d_parent,
-		                   (const uint32_t *)c->d_ref_tid, (uint32_t)dsb_index_n_ref(c->idx), c->tx->max_tid, bound, c->opts.max_sec_N, c->d_taxa);
-		c->taxa_run = true;
-	}
-	if (c->d_cov) {
-		// the per-reference coverage, after the same launches, whether or not a taxonomy is attached
-		hipLaunchKernelGGL(k_ref_cover, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, (const DsbReadOut *)c->d_rout, (const DsbHitOut *)c->d_hout,
-		                   (const unsigned int *)c->d_counters, (uint32_t)c->cap_hout, (uint32_t)n, (const uint64_t *)c->d_cov_len, (const uint64_t *)c->d_cov_off,
-		                   (uint32_t)dsb_index_n_ref(c->idx), c->d_cov_bits, c->d_cov);
-	}
-	if (c->d_em_cnt) {
-		// the candidate sets of the batch's reads, after the same launches.  Room for n records and for every hit the buffer can
-		// hold (a read's set lies in the room of its hits) is made first: the store's counters are read here, where the stream
-		// has already run everything before this batch's second run (ev[3]) and nothing of this batch touched them.
-		int rc = em_reserve(c, n, c->cap_hout);
-		if (rc) return rc;
-		c->em_reads += n;
-		hipLaunchKernelGGL(k_em_collect, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, (const DsbReadOut *)c->d_rout, (const DsbHitOut *)c->d_hout,
-		                   (const unsigned int *)c->d_counters, (uint32_t)c->cap_hout, (uint32_t)n, (uint32_t)dsb_index_n_ref(c->idx), c->em_permille,
-		                   c->d_em_sets, c->d_em_elems, c->d_em_cnt, (uint64_t)c->em_used_sets, (uint64_t)c->em_used_elems, (uint64_t)c->em_cap_sets,
-		                   (uint64_t)c->em_cap_elems, (uint64_t)c->knobs.em_hash_mask);
-	}
+	// the run reductions (dsb_reductions.hip), after every classify launch of the batch
+	const DsbBatchView hits = {c->stream, c->d_rout, c->d_hout, c->d_counters, c->cap_hout, s.d_rd, (uint32_t)n};
+	if (int rc = reductions_run(c, hits)) return rc;
 	if (dbg) {
 		static const char *nm[10] = {"seed_vector", "fast_classify", "resolve_tree", "slow+resolve", "hash_build", "sdp_middle", "sdp_right", "sdp_left", "sort/filter", "primary"};
 		double tot[10] = {0}, all = 0; unsigned sl = (unsigned)c->n_slots; if (sl > n) sl = (unsigned)n;
@@ -2240,12 +1765,9 @@ extern "C" int dsb_batch_fetch(dsb_ctx *c, dsb_result *out)
 		HIPCHK(hipMemcpyAsync(c->h_rout.data(), c->d_rout, n * sizeof(DsbReadOut), hipMemcpyDeviceToHost, c->stream));
 		HIPCHK(hipStreamSynchronize(c->stream));
 	}
-	const size_t nh = cnt[1] < c->cap_hout ? cnt[1] : c->cap_hout;
+	const size_t nh = dsb_hits_out(cnt[1], c->cap_hout);
 	c->h_hout.resize(nh);
 	if (nh) HIPCHK(hipMemcpyAsync(c->h_hout.data(), c->d_hout, nh * sizeof(DsbHitOut), hipMemcpyDeviceToHost, c->stream));
-	c->taxa_done = false;
-	if (c->taxa_run) { c->h_taxa.resize(n); if (n) HIPCHK(hipMemcpyAsync(c->h_taxa.data(), c->d_taxa, n * sizeof(dsb_read_taxon), hipMemcpyDeviceToHost, c->stream)); }
-	if (nh || (c->taxa_run && n)) HIPCHK(hipStreamSynchronize(c->stream));
 	// The hits of a read lie together in the device's hit buffer, in the order the reads finished; dsb_hit has the
 	// layout of the device record, so nothing is repacked: the per-read `first` points into the buffer as fetched.
 	static_assert(sizeof(DsbHitOut) == sizeof(dsb_hit), "dsb_hit mirrors DsbHitOut");
@@ -2256,341 +1778,11 @@ extern "C" int dsb_batch_fetch(dsb_ctx *c, dsb_result *out)
 		o.first = r.first; o.n = r.n; o.fast = r.fast & 1u; o.device_us = r.fast >> 1; o.n_anc = r.n_anc;
 		o.status = r.status ? (DSB_ECAP * 256 - r.status) : 0;
 		if (r.status) worst = DSB_ECAP;
-		if ((size_t)r.first + r.n > nh) { o.n = 0; o.first = 0; }
+		if (dsb_hits_cut(r.first, r.n, nh)) { o.n = 0; o.first = 0; }
 	}
+	if (int rc = reductions_fetch(c, n, nh != 0)) return rc;   // (the taxa, and the one wait for the copies)
 	out->reads = c->res_reads.data(); out->hits = reinterpret_cast<const dsb_hit *>(c->h_hout.data()); out->n_hits = nh;
-	if (c->taxa_run) {
-		// the reads the device left to the host get their taxon here (rare: see k_read_taxon)
-		const dsb_hit *H = reinterpret_cast<const dsb_hit *>(c->h_hout.data());
-		const InSlot &s = c->in[c->cur];
-		for (size_t i = 0; i < n; i++)
-			if (c->h_taxa[i].flags & DSB_TAXON_HOST)
-				c->h_taxa[i].taxid = dsb_read_taxid_host(c->tx, c->idx, s.h_rd[i].len, H + c->res_reads[i].first, c->res_reads[i].n, c->opts.max_sec_N);
-		c->taxa_done = true;
-	}
 	return worst;
-}
-
-// ---- taxonomy ----
-extern "C" int dsb_ctx_set_taxonomy(dsb_ctx *c, const dsb_taxonomy *tx)
-{
-	if (!c) return DSB_EINVAL;
-	if (tx && !tx->acyclic) return DSB_EINVAL;                 // (dsb_taxonomy_load_any: the device's walks need the bound)
-	HIPCHK(hipSetDevice(c->device));
-	HIPCHK(hipStreamSynchronize(c->stream));
-	hipFree(c->d_parent); hipFree(c->d_ref_tid); c->d_parent = c->d_ref_tid = nullptr;
-	c->tx = nullptr; c->taxa_run = c->taxa_done = false;
-	if (!tx) { hipFree(c->d_taxa); c->d_taxa = nullptr; c->cap_taxa = 0; return DSB_OK; }
-	const size_t n_ref = (size_t)dsb_index_n_ref(c->idx);
-	std::vector<uint32_t> rt(n_ref ? n_ref : 1);
-	for (size_t r = 0; r < n_ref; r++) rt[r] = dsb_ref_taxid(dsb_index_ref_name(c->idx, (uint32_t)r));
-	if (hipMalloc((void **)&c->d_parent, ((size_t)tx->max_tid + 1) * 4) != hipSuccess || hipMalloc((void **)&c->d_ref_tid, rt.size() * 4) != hipSuccess) {
-		hipFree(c->d_parent); c->d_parent = nullptr; return DSB_ENOMEM;
-	}
-	HIPCHK(hipMemcpy(c->d_parent, tx->parent, ((size_t)tx->max_tid + 1) * 4, hipMemcpyHostToDevice));
-	HIPCHK(hipMemcpy(c->d_ref_tid, rt.data(), rt.size() * 4, hipMemcpyHostToDevice));
-	// the per-read records for the batches the ctx was sized for now, not inside a batch (grow() waits for the device)
-	if (grow(&c->d_taxa, &c->cap_taxa, std::max(c->cap_rout, (size_t)c->opts.max_batch_reads))) return DSB_ENOMEM;
-	c->tx = tx;
-	return DSB_OK;
-}
-
-extern "C" int dsb_batch_taxa(dsb_ctx *c, const dsb_read_taxon **out)
-{
-	if (!c || !out || !c->tx || !c->taxa_run) return DSB_EINVAL;
-	if (!c->taxa_done) { dsb_result r; int rc = dsb_batch_fetch(c, &r); if (rc && rc != DSB_ECAP) return rc; }
-	*out = c->h_taxa.data();
-	return DSB_OK;
-}
-
-// ---- per-reference coverage ----
-static void cover_free(dsb_ctx *c)
-{
-	hipFree(c->d_cov_bits); hipFree(c->d_cov_off); hipFree(c->d_cov_len); hipFree(c->d_cov);
-	c->d_cov_bits = c->d_cov_off = c->d_cov_len = nullptr; c->d_cov = nullptr; c->cov_words = 0;
-}
-
-extern "C" int dsb_ctx_reset_coverage(dsb_ctx *c)
-{
-	if (!c || !c->d_cov) return DSB_EINVAL;
-	HIPCHK(hipSetDevice(c->device));
-	const size_t n_ref = (size_t)dsb_index_n_ref(c->idx);
-	HIPCHK(hipMemsetAsync(c->d_cov_bits, 0, (c->cov_words ? c->cov_words : 1) * 8, c->stream));
-	HIPCHK(hipMemsetAsync(c->d_cov, 0, (n_ref ? n_ref : 1) * sizeof(dsb_ref_coverage), c->stream));
-	HIPCHK(hipStreamSynchronize(c->stream));
-	return DSB_OK;
-}
-
-extern "C" int dsb_ctx_enable_coverage(dsb_ctx *c, int on)
-{
-	if (!c) return DSB_EINVAL;
-	HIPCHK(hipSetDevice(c->device));
-	HIPCHK(hipStreamSynchronize(c->stream));
-	if (on && c->d_cov) return dsb_ctx_reset_coverage(c);
-	cover_free(c);
-	if (!on) return DSB_OK;
-	const size_t n_ref = (size_t)dsb_index_n_ref(c->idx);
-	std::vector<uint64_t> off(n_ref + 1, 0), len(n_ref ? n_ref : 1, 0);
-	for (size_t r = 0; r < n_ref; r++) { len[r] = dsb_index_ref_len(c->idx, (uint32_t)r); off[r + 1] = off[r] + (len[r] + 63) / 64; }
-	const uint64_t nw = off[n_ref];
-	if (hipMalloc((void **)&c->d_cov_bits, (nw ? nw : 1) * 8) != hipSuccess || hipMalloc((void **)&c->d_cov_off, off.size() * 8) != hipSuccess ||
-	    hipMalloc((void **)&c->d_cov_len, len.size() * 8) != hipSuccess || hipMalloc((void **)&c->d_cov, (n_ref ? n_ref : 1) * sizeof(dsb_ref_coverage)) != hipSuccess) {
-		cover_free(c); (void)hipGetLastError(); return DSB_ENOMEM;
-	}
-	c->cov_words = nw;
-	HIPCHK(hipMemcpy(c->d_cov_off, off.data(), off.size() * 8, hipMemcpyHostToDevice));
-	HIPCHK(hipMemcpy(c->d_cov_len, len.data(), len.size() * 8, hipMemcpyHostToDevice));
-	return dsb_ctx_reset_coverage(c);
-}
-
-// covbases of words [w0, w0 + nw) of the bitmap, held in bits[0 .. nw), added to c's counters
-static void cover_count(dsb_ctx *c, const uint64_t *bits, uint64_t w0, uint64_t nw, hipStream_t st)
-{
-	if (!nw) return;
-	const uint64_t waves = (nw + DSB_COVER_CHUNK - 1) / DSB_COVER_CHUNK;
-	hipLaunchKernelGGL(k_cover_count, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, bits, w0, nw, (const uint64_t *)c->d_cov_off,
-	                   (uint32_t)dsb_index_n_ref(c->idx), c->d_cov);
-}
-
-extern "C" int dsb_ctx_coverage(dsb_ctx *c, dsb_ref_coverage *out)
-{
-	if (!c || !out || !c->d_cov) return DSB_EINVAL;
-	HIPCHK(hipSetDevice(c->device));
-	const uint32_t n_ref = (uint32_t)dsb_index_n_ref(c->idx);
-	if (!n_ref) return DSB_OK;
-	// on the ctx's stream: after the batches it has run (k_ref_cover leaves covbases alone, so a batch behind it changes nothing here)
-	hipLaunchKernelGGL(k_cover_clear, dim3((n_ref + 255) / 256), dim3(256), 0, c->stream, c->d_cov, n_ref);
-	cover_count(c, c->d_cov_bits, 0, c->cov_words, c->stream);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpyAsync(out, c->d_cov, n_ref * sizeof(dsb_ref_coverage), hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipStreamSynchronize(c->stream));
-	return DSB_OK;
-}
-
-// ---- per-reference abundance ----
-static void em_free(dsb_ctx *c)
-{
-	hipFree(c->d_em_sets); hipFree(c->d_em_elems); hipFree(c->d_em_cnt);
-	c->d_em_sets = nullptr; c->d_em_elems = nullptr; c->d_em_cnt = nullptr; c->em_cap_sets = c->em_cap_elems = 0; c->em_reads = 0;
-}
-
-// a store array grown to hold `need` entries (at least twice what it held), its first `used` entries kept
-template <class T> static int em_grow(T **p, size_t *cap, size_t used, size_t need)
-{
-	if (need <= *cap) return DSB_OK;
-	const size_t nc = std::max(need, 2 * *cap);
-	T *q = nullptr;
-	if (hipMalloc((void **)&q, nc * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); return DSB_ENOMEM; }
-	if (used && hipMemcpy(q, *p, used * sizeof(T), hipMemcpyDeviceToDevice) != hipSuccess) { hipFree(q); return DSB_ENODEV; }
-	hipFree(*p); *p = q; *cap = nc;
-	return DSB_OK;
-}
-
-// room for n_sets more sets and n_elems more elements.  The device must be done with the store (no k_em_collect pending).
-static int em_reserve(dsb_ctx *c, size_t n_sets, size_t n_elems)
-{
-	unsigned long long cnt[DSB_EM_CNT];
-	HIPCHK(hipMemcpy(cnt, c->d_em_cnt, sizeof cnt, hipMemcpyDeviceToHost));
-	if (cnt[2]) return DSB_ENOMEM;                             // (a set found no room: cannot happen after a reservation)
-	const size_t need_s = (size_t)cnt[0] + n_sets, need_e = (size_t)cnt[1] + n_elems;
-	if (need_s > 0xffffffffu || need_e > 0xffffffffu) return DSB_ENOMEM;   // (record indices and element offsets are 32-bit)
-	int rc = em_grow(&c->d_em_sets, &c->em_cap_sets, (size_t)cnt[0], need_s);
-	if (!rc) rc = em_grow(&c->d_em_elems, &c->em_cap_elems, (size_t)cnt[1], need_e);
-	c->em_used_sets = (size_t)cnt[0]; c->em_used_elems = (size_t)cnt[1];
-	return rc;
-}
-
-extern "C" int dsb_ctx_reset_abundance(dsb_ctx *c)
-{
-	if (!c || !c->d_em_cnt) return DSB_EINVAL;
-	HIPCHK(hipSetDevice(c->device));
-	HIPCHK(hipMemsetAsync(c->d_em_cnt, 0, DSB_EM_CNT * sizeof(unsigned long long), c->stream));
-	HIPCHK(hipStreamSynchronize(c->stream));
-	c->em_reads = 0;
-	return DSB_OK;
-}
-
-extern "C" int dsb_ctx_enable_abundance(dsb_ctx *c, int on, uint32_t min_permille)
-{
-	if (!c || (on && (min_permille < 1 || min_permille > 1000))) return DSB_EINVAL;
-	HIPCHK(hipSetDevice(c->device));
-	HIPCHK(hipStreamSynchronize(c->stream));
-	if (on && c->d_em_cnt) { c->em_permille = min_permille; return dsb_ctx_reset_abundance(c); }
-	em_free(c);
-	if (!on) return DSB_OK;
-	if (hipMalloc((void **)&c->d_em_cnt, DSB_EM_CNT * sizeof(unsigned long long)) != hipSuccess) { (void)hipGetLastError(); c->d_em_cnt = nullptr; return DSB_ENOMEM; }
-	c->em_permille = min_permille;
-	return dsb_ctx_reset_abundance(c);
-}
-
-// device buffers of one solve, freed together
-struct EmTmp {
-	std::vector<void *> p;
-	~EmTmp() { for (void *q : p) hipFree(q); }
-	template <class T> T *get(size_t n)
-	{
-		void *q = nullptr;
-		if (hipMalloc(&q, (n ? n : 1) * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-		p.push_back(q); return (T *)q;
-	}
-};
-#define EMCK(e) do { if ((e) != hipSuccess) { (void)hipGetLastError(); return DSB_ENODEV; } } while (0)
-#define EM_ITER_BLOCK 16
-
-static int em_opts(const dsb_em_opts *o, dsb_em_opts *v)
-{
-	v->max_iter = 10000; v->reserved = 0; v->tol = 0.01;
-	if (!o) return DSB_OK;
-	if (o->max_iter < 1 || !(o->tol >= 0.0)) return DSB_EINVAL;
-	*v = *o; v->reserved = 0;
-	return DSB_OK;
-}
-
-// The classes of n records (elements in elems[0 .. n_elems); the empty records of unclassified reads take no part) and the EM over them, on the current device, on stream st.
-//   classes: radix sort of (hash, set index); k_em_mark compares neighbours of one hash element by element (a collision: the host
-//            orders each run of one hash by the sets themselves); an inclusive scan of the class heads numbers the classes.
-//   CSR:     the (ref, class) pairs of every class's set, written in class order and radix-sorted by ref -- stably, so each
-//            reference's classes stay in class order; the row offsets by binary search.
-//   EM:      k_em_class + k_em_ref per iteration, EM_ITER_BLOCK iterations per host round trip; the device's done word makes the
-//            result the state after the first iteration that met tol, whatever the block.
-static int em_solve(hipStream_t st, const dsb_index *idx, const DsbEmSet *sets, const uint32_t *elems, uint32_t n, uint32_t n_elems, uint64_t reads,
-                    uint32_t permille, const dsb_em_opts &o, dsb_ref_abundance *out, dsb_abundance_summary *sum)
-{
-	const uint32_t n_ref = (uint32_t)dsb_index_n_ref(idx);
-	memset(out, 0, (size_t)n_ref * sizeof *out); memset(sum, 0, sizeof *sum);
-	sum->reads = reads; sum->min_permille = permille; sum->converged = 1;
-	if (!n || !n_ref) return DSB_OK;
-	EmTmp T;
-	uint64_t *key = T.get<uint64_t>(n), *key_s = T.get<uint64_t>(n);
-	uint32_t *val = T.get<uint32_t>(n), *order = T.get<uint32_t>(n), *head = T.get<uint32_t>(n), *cls = T.get<uint32_t>(n);
-	unsigned int *flag = T.get<unsigned int>(1);
-	if (!key || !key_s || !val || !order || !head || !cls || !flag) return DSB_ENOMEM;
-	const dim3 gn((n + 255) / 256), b256(256);
-	hipLaunchKernelGGL(k_em_keys, gn, b256, 0, st, sets, n, key, val);
-	size_t tb = 0;
-	EMCK(rocprim::radix_sort_pairs(nullptr, tb, key, key_s, val, order, n, 0, 64, st));
-	void *tmp = T.get<uint8_t>(tb);
-	if (!tmp) return DSB_ENOMEM;
-	EMCK(rocprim::radix_sort_pairs(tmp, tb, key, key_s, val, order, n, 0, 64, st));
-	EMCK(hipMemsetAsync(flag, 0, 4, st));
-	hipLaunchKernelGGL(k_em_mark, gn, b256, 0, st, sets, elems, (const uint32_t *)order, n, head, flag);
-	unsigned int collide = 0;
-	EMCK(hipMemcpyAsync(&collide, flag, 4, hipMemcpyDeviceToHost, st));
-	EMCK(hipStreamSynchronize(st));
-	if (collide) {
-		// different sets of one 64-bit hash (rare): order by (hash, length, elements) on the host, then mark again
-		std::vector<DsbEmSet> hs(n); std::vector<uint32_t> ho(n), he(n_elems ? n_elems : 1);
-		EMCK(hipMemcpy(hs.data(), sets, (size_t)n * sizeof(DsbEmSet), hipMemcpyDeviceToHost));
-		EMCK(hipMemcpy(he.data(), elems, (size_t)n_elems * 4, hipMemcpyDeviceToHost));
-		for (uint32_t i = 0; i < n; i++) ho[i] = i;
-		std::sort(ho.begin(), ho.end(), [&](uint32_t x, uint32_t y) {
-			const DsbEmSet &a = hs[x], &b = hs[y];
-			if (a.hash != b.hash) return a.hash < b.hash;
-			if (a.len != b.len) return a.len < b.len;
-			return std::lexicographical_compare(he.begin() + a.off, he.begin() + a.off + a.len, he.begin() + b.off, he.begin() + b.off + b.len);
-		});
-		EMCK(hipMemcpy(order, ho.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-		EMCK(hipMemsetAsync(flag, 0, 4, st));
-		hipLaunchKernelGGL(k_em_mark, gn, b256, 0, st, sets, elems, (const uint32_t *)order, n, head, flag);
-	}
-	EMCK(rocprim::inclusive_scan(nullptr, tb, head, cls, n, rocprim::plus<uint32_t>(), st));
-	if (!(tmp = T.get<uint8_t>(tb))) return DSB_ENOMEM;
-	EMCK(rocprim::inclusive_scan(tmp, tb, head, cls, n, rocprim::plus<uint32_t>(), st));
-	uint32_t K = 0;
-	EMCK(hipMemcpyAsync(&K, cls + (n - 1), 4, hipMemcpyDeviceToHost, st));
-	EMCK(hipStreamSynchronize(st));
-	if (!K) return DSB_OK;                                     // (no read classified)
-	uint32_t *start = T.get<uint32_t>((size_t)K + 1), *clen = T.get<uint32_t>((size_t)K + 1), *coff = T.get<uint32_t>((size_t)K + 1);
-	if (!start || !clen || !coff) return DSB_ENOMEM;
-	EMCK(hipMemsetAsync(clen + K, 0, 4, st));
-	EMCK(hipMemcpyAsync(start + K, &n, 4, hipMemcpyHostToDevice, st));
-	hipLaunchKernelGGL(k_em_classes, gn, b256, 0, st, sets, (const uint32_t *)order, (const uint32_t *)head, (const uint32_t *)cls, n, start, clen);
-	EMCK(rocprim::exclusive_scan(nullptr, tb, clen, coff, 0u, (size_t)K + 1, rocprim::plus<uint32_t>(), st));
-	if (!(tmp = T.get<uint8_t>(tb))) return DSB_ENOMEM;
-	EMCK(rocprim::exclusive_scan(tmp, tb, clen, coff, 0u, (size_t)K + 1, rocprim::plus<uint32_t>(), st));
-	uint32_t M = 0, start0 = 0;                                 // (the records before start[0] are the empty ones)
-	EMCK(hipMemcpyAsync(&M, coff + K, 4, hipMemcpyDeviceToHost, st));
-	EMCK(hipMemcpyAsync(&start0, start, 4, hipMemcpyDeviceToHost, st));
-	EMCK(hipStreamSynchronize(st));
-	sum->classified = n - start0;
-	uint32_t *cref = T.get<uint32_t>(M), *ccls = T.get<uint32_t>(M), *sref = T.get<uint32_t>(M), *scls = T.get<uint32_t>(M), *roff = T.get<uint32_t>((size_t)n_ref + 1);
-	if (!cref || !ccls || !sref || !scls || !roff) return DSB_ENOMEM;
-	const dim3 gk((K + 255) / 256), gr((n_ref + 256) / 256), gw((n_ref + 3) / 4);
-	hipLaunchKernelGGL(k_em_fill, gk, b256, 0, st, sets, elems, (const uint32_t *)order, (const uint32_t *)start, (const uint32_t *)coff, K, cref, ccls);
-	unsigned bits = 1;
-	while (bits < 32 && (1ull << bits) < n_ref) bits++;
-	EMCK(rocprim::radix_sort_pairs(nullptr, tb, cref, sref, ccls, scls, M, 0, bits, st));
-	if (!(tmp = T.get<uint8_t>(tb))) return DSB_ENOMEM;
-	EMCK(rocprim::radix_sort_pairs(tmp, tb, cref, sref, ccls, scls, M, 0, bits, st));
-	hipLaunchKernelGGL(k_em_rowoff, gr, b256, 0, st, (const uint32_t *)sref, M, n_ref, roff);
-	std::vector<uint32_t> hroff((size_t)n_ref + 1);
-	EMCK(hipMemcpyAsync(hroff.data(), roff, hroff.size() * 4, hipMemcpyDeviceToHost, st));
-	EMCK(hipStreamSynchronize(st));
-	uint32_t R = 0;
-	for (uint32_t r = 0; r < n_ref; r++) R += hroff[r + 1] > hroff[r];
-	std::vector<double> hL(n_ref);
-	for (uint32_t r = 0; r < n_ref; r++) { const uint64_t l = dsb_index_ref_len(idx, r); hL[r] = l ? (double)l : 1.0; }
-	double *L = T.get<double>(n_ref), *a[2] = {T.get<double>(n_ref), T.get<double>(n_ref)}, *coef = T.get<double>(K);
-	unsigned long long *nr = T.get<unsigned long long>(n_ref), *ur = T.get<unsigned long long>(n_ref);
-	DsbEmState *est = T.get<DsbEmState>(1);
-	if (!L || !a[0] || !a[1] || !coef || !nr || !ur || !est) return DSB_ENOMEM;
-	EMCK(hipMemcpyAsync(L, hL.data(), (size_t)n_ref * 8, hipMemcpyHostToDevice, st));
-	EMCK(hipMemsetAsync(est, 0, sizeof(DsbEmState), st));
-	hipLaunchKernelGGL(k_em_init, gr, b256, 0, st, (const uint32_t *)roff, (const uint32_t *)scls, (const uint32_t *)start, (const uint32_t *)clen, n_ref,
-	                   1.0 / (double)R, a[0], nr, ur);
-	const double N = (double)(n - start0);
-	DsbEmState hs; memset(&hs, 0, sizeof hs);
-	for (uint32_t it = 0; it < o.max_iter;) {
-		const uint32_t end = o.max_iter - it < EM_ITER_BLOCK ? o.max_iter : it + EM_ITER_BLOCK;
-		for (; it < end; it++) {
-			hipLaunchKernelGGL(k_em_class, gk, b256, 0, st, (const uint32_t *)cref, (const uint32_t *)coff, (const uint32_t *)start, K, (const double *)a[it & 1],
-			                   (const double *)L, o.tol, it, est, coef);
-			hipLaunchKernelGGL(k_em_ref, gw, b256, 0, st, (const uint32_t *)roff, (const uint32_t *)scls, (const double *)coef, n_ref, (const double *)a[it & 1],
-			                   (const double *)L, N, it, est, a[(it + 1) & 1]);
-		}
-		EMCK(hipGetLastError());
-		EMCK(hipMemcpyAsync(&hs, est, sizeof hs, hipMemcpyDeviceToHost, st));
-		EMCK(hipStreamSynchronize(st));
-		if (hs.done) break;
-	}
-	const uint32_t iters = hs.done ? hs.iters : o.max_iter;
-	double chg = 0.0;
-	memcpy(&chg, &hs.chg[(iters - 1) & 1], 8);
-	std::vector<double> ha(n_ref); std::vector<unsigned long long> hnr(n_ref), hur(n_ref);
-	EMCK(hipMemcpyAsync(ha.data(), a[iters & 1], (size_t)n_ref * 8, hipMemcpyDeviceToHost, st));
-	EMCK(hipMemcpyAsync(hnr.data(), nr, (size_t)n_ref * 8, hipMemcpyDeviceToHost, st));
-	EMCK(hipMemcpyAsync(hur.data(), ur, (size_t)n_ref * 8, hipMemcpyDeviceToHost, st));
-	EMCK(hipStreamSynchronize(st));
-	double W = 0.0;                                            // (in ref_ID order)
-	for (uint32_t r = 0; r < n_ref; r++) W += ha[r] / hL[r];
-	for (uint32_t r = 0; r < n_ref; r++) {
-		dsb_ref_abundance &x = out[r];
-		x.numreads = hnr[r]; x.uniqreads = hur[r];
-		x.est_reads = N * ha[r]; x.read_share = ha[r];
-		x.copy_share = W > 0.0 ? (ha[r] / hL[r]) / W : 0.0;
-	}
-	sum->classes = K; sum->iterations = iters; sum->max_change = chg;
-	sum->converged = hs.done || chg < o.tol;
-	return DSB_OK;
-}
-
-// the store's counters, read on the ctx's stream (after the batches it holds)
-static int em_counts(dsb_ctx *c, unsigned long long cnt[DSB_EM_CNT])
-{
-	HIPCHK(hipMemcpyAsync(cnt, c->d_em_cnt, DSB_EM_CNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipStreamSynchronize(c->stream));
-	return cnt[2] ? DSB_ENOMEM : DSB_OK;
-}
-
-extern "C" int dsb_ctx_abundance(dsb_ctx *c, const dsb_em_opts *opts, dsb_ref_abundance *out, dsb_abundance_summary *summary)
-{
-	dsb_em_opts o;
-	if (!c || !out || !summary || !c->d_em_cnt || em_opts(opts, &o)) return DSB_EINVAL;
-	HIPCHK(hipSetDevice(c->device));
-	unsigned long long cnt[DSB_EM_CNT];
-	int rc = em_counts(c, cnt);
-	if (rc) return rc;
-	return em_solve(c->stream, c->idx, c->d_em_sets, c->d_em_elems, (uint32_t)cnt[0], (uint32_t)cnt[1], c->em_reads, c->em_permille, o, out, summary);
 }
 
 extern "C" int dsb_classify_batch(dsb_ctx *c, const dsb_read *reads, size_t n, dsb_result *out)
@@ -2700,14 +1892,6 @@ extern "C" int dsb_shard_plan(const uint32_t *lengths, size_t n, int world, uint
 	return (out && k > cap) ? DSB_EINVAL : DSB_OK;
 }
 
-struct dsb_multi {
-	dsb_index *idx = nullptr; std::vector<dsb_ctx *> ctx; uint32_t hist = 0;
-	uint32_t chunk_reads_env = 0;                 // DSB_SHARD_CHUNK_READS, read when the contexts are made (tests: many small chunks)
-	std::vector<uint32_t> last_calls;             // dsb_classify_batch calls each context made in the last dsb_multi_classify_batch
-	std::vector<dsb_read_result> reads; std::vector<dsb_hit> hits;
-	const dsb_taxonomy *tx = nullptr; std::vector<dsb_read_taxon> taxa; bool taxa_ok = false;   // dsb_multi_set_taxonomy / dsb_multi_taxa
-};
-
 extern "C" void dsb_multi_destroy(dsb_multi *m)
 {
 	if (!m) return;
@@ -2809,132 +1993,5 @@ extern "C" int dsb_multi_classify_batch(dsb_multi *m, const dsb_read *reads, siz
 	out->reads = m->reads.data(); out->hits = m->hits.data(); out->n_hits = m->hits.size();
 	m->taxa_ok = m->tx != nullptr;
 	return worst;
-}
-
-extern "C" int dsb_multi_set_taxonomy(dsb_multi *m, const dsb_taxonomy *tx)
-{
-	if (!m) return DSB_EINVAL;
-	m->tx = nullptr; m->taxa_ok = false;
-	for (dsb_ctx *c : m->ctx) { int rc = dsb_ctx_set_taxonomy(c, tx); if (rc) { for (dsb_ctx *d : m->ctx) dsb_ctx_set_taxonomy(d, nullptr); return rc; } }
-	m->tx = tx;
-	return DSB_OK;
-}
-extern "C" int dsb_multi_taxa(dsb_multi *m, const dsb_read_taxon **out)
-{
-	if (!m || !out || !m->tx || !m->taxa_ok) return DSB_EINVAL;
-	*out = m->taxa.data();
-	return DSB_OK;
-}
-
-extern "C" int dsb_multi_enable_coverage(dsb_multi *m, int on)
-{
-	if (!m) return DSB_EINVAL;
-	for (dsb_ctx *c : m->ctx) { int rc = dsb_ctx_enable_coverage(c, on); if (rc) { for (dsb_ctx *d : m->ctx) dsb_ctx_enable_coverage(d, 0); return rc; } }
-	return DSB_OK;
-}
-
-// The contexts' coverage merged: the counters are added on the host; the bitmaps are ORed chunk by chunk into a buffer on the first
-// context's device -- read in place where a context shares that device, copied over (hipMemcpyPeerAsync) where it does not -- and
-// each chunk is counted there.  The contexts' own bitmaps are left as they are.
-extern "C" int dsb_multi_coverage(dsb_multi *m, dsb_ref_coverage *out)
-{
-	if (!m || !out || m->ctx.empty()) return DSB_EINVAL;
-	for (dsb_ctx *c : m->ctx) if (!c->d_cov) return DSB_EINVAL;
-	dsb_ctx *c0 = m->ctx[0];
-	if (m->ctx.size() == 1) return dsb_ctx_coverage(c0, out);
-	const uint32_t n_ref = (uint32_t)dsb_index_n_ref(m->idx);
-	if (!n_ref) return DSB_OK;
-	memset(out, 0, n_ref * sizeof *out);
-	std::vector<dsb_ref_coverage> part(n_ref);
-	bool remote = false;
-	for (dsb_ctx *c : m->ctx) {
-		HIPCHK(hipSetDevice(c->device));
-		HIPCHK(hipStreamSynchronize(c->stream));
-		HIPCHK(hipMemcpy(part.data(), c->d_cov, n_ref * sizeof(dsb_ref_coverage), hipMemcpyDeviceToHost));
-		for (uint32_t r = 0; r < n_ref; r++) { out[r].numreads += part[r].numreads; out[r].aligned_bases += part[r].aligned_bases; out[r].mapq_sum += part[r].mapq_sum; }
-		remote |= c->device != c0->device;
-	}
-	HIPCHK(hipSetDevice(c0->device));
-	const uint64_t nw = c0->cov_words, chunk = nw < (4ull << 20) ? nw : (4ull << 20);   // (32 MiB of words per chunk)
-	uint64_t *acc = nullptr, *buf = nullptr;
-	if (nw && (hipMalloc((void **)&acc, chunk * 8) != hipSuccess || (remote && hipMalloc((void **)&buf, chunk * 8) != hipSuccess))) {
-		hipFree(acc); (void)hipGetLastError(); return DSB_ENOMEM;
-	}
-	const hipStream_t st = c0->stream;
-	hipLaunchKernelGGL(k_cover_clear, dim3((n_ref + 255) / 256), dim3(256), 0, st, c0->d_cov, n_ref);
-	int rc = DSB_OK;
-	for (uint64_t w0 = 0; w0 < nw && !rc; w0 += chunk) {
-		const uint64_t k = nw - w0 < chunk ? nw - w0 : chunk;
-		const unsigned grid = (unsigned)std::min<uint64_t>((k + 255) / 256, 8192);
-		if (hipMemcpyAsync(acc, c0->d_cov_bits + w0, k * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) rc = DSB_ENODEV;
-		for (size_t i = 1; i < m->ctx.size() && !rc; i++) {
-			const dsb_ctx *c = m->ctx[i];
-			const uint64_t *src = c->d_cov_bits + w0;
-			if (c->device != c0->device) {
-				if (hipMemcpyPeerAsync(buf, c0->device, c->d_cov_bits + w0, c->device, k * 8, st) != hipSuccess) { rc = DSB_ENODEV; break; }
-				src = buf;
-			}
-			hipLaunchKernelGGL(k_cover_or, dim3(grid), dim3(256), 0, st, acc, src, k);
-		}
-		if (!rc) cover_count(c0, acc, w0, k, st);
-	}
-	if (!rc && hipGetLastError() != hipSuccess) rc = DSB_ENODEV;
-	if (!rc && hipMemcpyAsync(part.data(), c0->d_cov, n_ref * sizeof(dsb_ref_coverage), hipMemcpyDeviceToHost, st) != hipSuccess) rc = DSB_ENODEV;
-	if (hipStreamSynchronize(st) != hipSuccess) rc = DSB_ENODEV;
-	hipFree(acc); hipFree(buf);
-	if (rc) return rc;
-	for (uint32_t r = 0; r < n_ref; r++) out[r].covbases = part[r].covbases;
-	return DSB_OK;
-}
-extern "C" int dsb_multi_enable_abundance(dsb_multi *m, int on, uint32_t min_permille)
-{
-	if (!m) return DSB_EINVAL;
-	for (dsb_ctx *c : m->ctx) { int rc = dsb_ctx_enable_abundance(c, on, min_permille); if (rc) { for (dsb_ctx *d : m->ctx) dsb_ctx_enable_abundance(d, 0, 0); return rc; } }
-	return DSB_OK;
-}
-
-// The contexts' stores one after the other on the first context's device -- copied within a device, peer-copied from another --
-// each context's element offsets moved behind the elements before it, then the solve of one context.  The classes, their
-// order and every sum depend only on the multiset of sets, so the result is bitwise that of one context.
-extern "C" int dsb_multi_abundance(dsb_multi *m, const dsb_em_opts *opts, dsb_ref_abundance *out, dsb_abundance_summary *summary)
-{
-	dsb_em_opts o;
-	if (!m || !out || !summary || m->ctx.empty() || em_opts(opts, &o)) return DSB_EINVAL;
-	dsb_ctx *c0 = m->ctx[0];
-	for (dsb_ctx *c : m->ctx) if (!c->d_em_cnt || c->em_permille != c0->em_permille) return DSB_EINVAL;
-	if (m->ctx.size() == 1) return dsb_ctx_abundance(c0, opts, out, summary);
-	std::vector<unsigned long long> ns(m->ctx.size()), ne(m->ctx.size());
-	uint64_t S = 0, E = 0, reads = 0;
-	for (size_t i = 0; i < m->ctx.size(); i++) {
-		dsb_ctx *c = m->ctx[i];
-		HIPCHK(hipSetDevice(c->device));
-		unsigned long long cnt[DSB_EM_CNT];
-		int rc = em_counts(c, cnt);
-		if (rc) return rc;
-		ns[i] = cnt[0]; ne[i] = cnt[1]; S += cnt[0]; E += cnt[1]; reads += c->em_reads;
-	}
-	if (S > 0xffffffffu || E > 0xffffffffu) return DSB_ENOMEM;
-	HIPCHK(hipSetDevice(c0->device));
-	const hipStream_t st = c0->stream;
-	EmTmp T;
-	DsbEmSet *sets = T.get<DsbEmSet>(S); uint32_t *elems = T.get<uint32_t>(E);
-	if (!sets || !elems) return DSB_ENOMEM;
-	uint64_t s0 = 0, e0 = 0;
-	for (size_t i = 0; i < m->ctx.size(); i++) {
-		const dsb_ctx *c = m->ctx[i];
-		if (ns[i]) {
-			if (c->device == c0->device) {
-				EMCK(hipMemcpyAsync(sets + s0, c->d_em_sets, ns[i] * sizeof(DsbEmSet), hipMemcpyDeviceToDevice, st));
-				if (ne[i]) EMCK(hipMemcpyAsync(elems + e0, c->d_em_elems, ne[i] * 4, hipMemcpyDeviceToDevice, st));
-			} else {
-				EMCK(hipMemcpyPeerAsync(sets + s0, c0->device, c->d_em_sets, c->device, ns[i] * sizeof(DsbEmSet), st));
-				if (ne[i]) EMCK(hipMemcpyPeerAsync(elems + e0, c0->device, c->d_em_elems, c->device, ne[i] * 4, st));
-			}
-			if (e0) hipLaunchKernelGGL(k_em_rebase, dim3((unsigned)((ns[i] + 255) / 256)), dim3(256), 0, st, sets + s0, (uint32_t)ns[i], (uint32_t)e0);
-		}
-		s0 += ns[i]; e0 += ne[i];
-	}
-	EMCK(hipGetLastError());
-	return em_solve(st, m->idx, sets, elems, (uint32_t)S, (uint32_t)E, reads, c0->em_permille, o, out, summary);
 }
 #endif  // DSB_UNIT_HOST

@@ -1,0 +1,49 @@
+// The run reductions of classify: per-read taxa (dsb_ctx_set_taxonomy), per-reference coverage (dsb_ctx_enable_coverage,
+// DESIGN 2.9) and per-reference abundance by EM (dsb_ctx_enable_abundance).  Each reads a batch's hit buffer
+// after its last classify launch, keeps state for the whole run and is merged across the contexts of a dsb_multi
+// (dsb_reductions.hip).  Internal: the public surface is include/desamba_amd.h.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <vector>
+#include "../../include/desamba_amd.h"
+#include "dsb_device.h"
+
+struct DsbEmSet;
+
+// taxonomy: the parent table and each reference's taxid in HBM, one k_read_taxon launch per batch
+struct DsbTaxa {
+	const dsb_taxonomy *tx = nullptr; uint32_t *d_parent = nullptr, *d_ref_tid = nullptr;
+	dsb_read_taxon *d_taxa = nullptr; size_t cap_taxa = 0; std::vector<dsb_read_taxon> h_taxa;
+	bool run = false, done = false;               // k_read_taxon ran for the batch of the current slot / its records are fetched and completed
+};
+
+// coverage: a bitmap of one bit per reference base (each reference from a word boundary; off: the prefix sum of ceil(LN / 64),
+// n_ref + 1 words), the lengths, and the four counters per reference; one k_ref_cover launch per batch
+struct DsbCover {
+	uint64_t *d_bits = nullptr, *d_off = nullptr, *d_len = nullptr; dsb_ref_coverage *d_cov = nullptr; uint64_t words = 0;
+};
+
+// abundance: the run's candidate sets (DsbEmSet + their elements, grown geometrically between batches), the store's counters,
+// and the reads the batches held; one k_em_collect launch per batch
+struct DsbEmStore {
+	DsbEmSet *d_sets = nullptr; uint32_t *d_elems = nullptr; unsigned long long *d_cnt = nullptr;
+	size_t cap_sets = 0, cap_elems = 0, used_sets = 0, used_elems = 0; uint64_t reads = 0; uint32_t permille = 0;
+};
+
+// a batch's results on the device after its last classify launch (the second runs and the run after a regrown hit buffer included)
+struct DsbBatchView {
+	hipStream_t st;
+	const DsbReadOut *rout; const DsbHitOut *hout; const unsigned int *counters; size_t cap_hout;
+	const DsbReadDesc *rd; uint32_t n;
+};
+
+struct dsb_ctx;
+// dsb_batch_run: the launches of the reductions that are on, on b.st
+int reductions_run(dsb_ctx *c, const DsbBatchView &b);
+// dsb_batch_fetch, once the copies of the batch's reads and hits are queued on c's stream: queues the copy of the batch's taxa,
+// waits for all of them (one synchronisation, skipped when nothing was queued) and gives the reads the device left to the host
+// their taxon
+int reductions_fetch(dsb_ctx *c, size_t n, bool queued);
+// dsb_ctx_destroy
+void reductions_release(dsb_ctx *c);

@@ -1,6 +1,6 @@
 // The fields of output_one_result_sam (src/cly_mt.c:245-344) that the taxonomy report reads back: which records are
 // printed, the MAPQ of each, and the read length `deSAMBA analysis` takes from a printed CIGAR.  One definition for the
-// SAM writer (dsb_format_sam, dsb_index.cpp) and for k_read_taxon (dsb_gpu.hip), so that the two cannot drift apart.
+// SAM writer (dsb_format_sam, dsb_index.cpp) and for k_read_taxon (dsb_reductions.hip), so that the two cannot drift apart.
 #pragma once
 #include <stdint.h>
 #include "../../include/desamba_amd.h"
@@ -10,6 +10,12 @@
 #else
 #define DSB_HD static inline
 #endif
+
+// The records dsb_batch_fetch hands out: the first nh = dsb_hits_out(hits counted, the hit buffer's capacity) of the buffer, and
+// of a read only records that lie among them -- a read whose records reach further (dsb_hits_cut) gets none.  One rule for the
+// fetch and for the kernels that read a batch's hits after its last classify launch (dsb_reductions.hip).
+DSB_HD uint32_t dsb_hits_out(uint32_t counted, uint64_t cap) { return counted < cap ? counted : (uint32_t)cap; }
+DSB_HD bool dsb_hits_cut(uint32_t first, uint32_t n, uint64_t nh) { return (uint64_t)first + n > nh; }
 
 // MAPQ of the primary record; supplementary records print min(it, 30), secondary ones 0.  (Unsigned difference, as
 // the reference computes it: the hits are in score order, so it does not wrap.)

@@ -7,7 +7,7 @@ name=$1; shift
 mkdir -p ab/obj_$name
 F="-O3 -fno-strict-aliasing --offload-arch=gfx950 -fPIC -std=c++17 -Wno-unused-value -Iinclude $*"
 rm -f ab/obj_$name/*.o
-for u in dsb_index.cpp dsb_taxonomy.cpp dsb_build.hip; do /opt/rocm/bin/hipcc $F -c desamba_amd/csrc/$u -o ab/obj_$name/$u.o & done
+for u in dsb_reductions.hip dsb_index.cpp dsb_taxonomy.cpp dsb_build.hip; do /opt/rocm/bin/hipcc $F -c desamba_amd/csrc/$u -o ab/obj_$name/$u.o & done
 for k in 0 1 2 3 4 5; do /opt/rocm/bin/hipcc $F -DDSB_KUNIT=$k -c desamba_amd/csrc/dsb_gpu.hip -o ab/obj_$name/dsb_gpu.hip.k$k.o & done     # (six units side by side: dsb_gpu.hip)
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ab/$name.so ab/obj_$name/*.o -lz
