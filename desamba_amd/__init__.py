@@ -88,6 +88,23 @@ class DsbAbundanceSummary(C.Structure):
 ABUNDANCE_DTYPE = [("numreads", "<u8"), ("uniqreads", "<u8"), ("est_reads", "<f8"), ("read_share", "<f8"), ("copy_share", "<f8")]
 
 
+class DsbReadLca(C.Structure):
+    _fields_ = [("taxid", C.c_uint32), ("score", C.c_uint32), ("n_pass", C.c_uint32), ("depth", C.c_uint16), ("flags", C.c_uint8), ("pad", C.c_uint8)]
+
+
+DSB_LCA_CLASSIFIED, DSB_LCA_NO_TAXON, DSB_LCA_AMBIGUOUS = 1, 2, 4
+LCA_DTYPE = [("taxid", "<u4"), ("score", "<u4"), ("n_pass", "<u4"), ("depth", "<u2"), ("flags", "u1"), ("pad", "u1")]
+TAXON_COUNT_DTYPE = [("taxid", "<u4"), ("pad", "<u4"), ("clade_reads", "<u8"), ("direct_reads", "<u8")]
+
+
+class DsbLcaSummary(C.Structure):
+    _fields_ = [("reads", C.c_uint64), ("classified", C.c_uint64), ("no_taxon", C.c_uint64), ("ambiguous", C.c_uint64),
+                ("min_permille", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+LCA_SUMMARY_FIELDS = ("reads", "classified", "no_taxon", "ambiguous", "min_permille")
+
+
 class DsbChunk(C.Structure):
     _fields_ = [("start", C.c_uint64), ("end", C.c_uint64), ("hist_max_before", C.c_uint32), ("rank", C.c_int32)]
 
@@ -103,7 +120,9 @@ EXPORTS = ["dsb_index_open", "dsb_index_close", "dsb_index_n_ref", "dsb_index_re
            "dsb_report_create", "dsb_report_add", "dsb_report_add_sam", "dsb_report_format", "dsb_report_destroy",
            "dsb_ctx_enable_coverage", "dsb_ctx_reset_coverage", "dsb_ctx_coverage", "dsb_multi_enable_coverage", "dsb_multi_coverage",
            "dsb_coverage_format", "dsb_ctx_enable_abundance", "dsb_ctx_reset_abundance", "dsb_ctx_abundance", "dsb_multi_enable_abundance",
-           "dsb_multi_abundance", "dsb_abundance_format"]
+           "dsb_multi_abundance", "dsb_abundance_format",
+           "dsb_ctx_enable_lca", "dsb_ctx_reset_lca", "dsb_batch_lca", "dsb_ctx_lca_counts", "dsb_multi_enable_lca", "dsb_multi_lca",
+           "dsb_multi_lca_counts", "dsb_taxnames_load", "dsb_taxnames_close", "dsb_format_kraken", "dsb_lca_report_format"]
 
 _lib = None
 
@@ -184,6 +203,17 @@ def lib():
     L.dsb_multi_enable_abundance.argtypes = [C.c_void_p, C.c_int, C.c_uint32]
     L.dsb_multi_abundance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.dsb_abundance_format.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]; L.dsb_abundance_format.restype = C.c_long
+    L.dsb_ctx_enable_lca.argtypes = [C.c_void_p, C.c_int, C.c_uint32]
+    L.dsb_ctx_reset_lca.argtypes = [C.c_void_p]
+    L.dsb_batch_lca.argtypes = [C.c_void_p, C.POINTER(C.POINTER(DsbReadLca))]
+    L.dsb_ctx_lca_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
+    L.dsb_multi_enable_lca.argtypes = [C.c_void_p, C.c_int, C.c_uint32]
+    L.dsb_multi_lca.argtypes = [C.c_void_p, C.POINTER(C.POINTER(DsbReadLca))]
+    L.dsb_multi_lca_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
+    L.dsb_taxnames_load.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
+    L.dsb_taxnames_close.argtypes = [C.c_void_p]; L.dsb_taxnames_close.restype = None
+    L.dsb_format_kraken.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]; L.dsb_format_kraken.restype = C.c_long
+    L.dsb_lca_report_format.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_char_p, C.c_size_t]; L.dsb_lca_report_format.restype = C.c_long
     L.dsb_strerror.argtypes = [C.c_int]; L.dsb_strerror.restype = C.c_char_p
     L.dsb_version.restype = C.c_char_p
     _lib = L
@@ -410,6 +440,30 @@ class Ctx:
         """EM over everything since enable / reset: (numpy structured array of n_ref rows, ABUNDANCE_DTYPE; summary dict)"""
         return _abundance(lib().dsb_ctx_abundance, self.h, self.index.n_ref, max_iter, tol, "dsb_ctx_abundance")
 
+    def enable_lca(self, on=True, min_frac=0.95):
+        """per-read classification by the LCA of the near-best hits from now on (needs a Taxonomy attached), or off (freed).  min_frac: a
+        hit takes part when its AS is at least min_frac x the read's best AS (0 < min_frac <= 1, in steps of 0.001)"""
+        rc = lib().dsb_ctx_enable_lca(self.h, 1 if on else 0, _permille(min_frac) if on else 0)
+        if rc != 0:
+            raise DsbError(rc, "dsb_ctx_enable_lca")
+
+    def reset_lca(self):
+        rc = lib().dsb_ctx_reset_lca(self.h)
+        if rc != 0:
+            raise DsbError(rc, "dsb_ctx_reset_lca")
+
+    def lca(self):
+        """the LCA record of each read of the last batch: numpy structured array (LCA_DTYPE)"""
+        p = C.POINTER(DsbReadLca)()
+        rc = lib().dsb_batch_lca(self.h, C.byref(p))
+        if rc != 0:
+            raise DsbError(rc, "dsb_batch_lca")
+        return _lca(p, self.in_last_batch())
+
+    def lca_counts(self):
+        """everything since enable / reset: (the taxa with clade_reads > 0 in ascending taxid, TAXON_COUNT_DTYPE; summary dict)"""
+        return _lca_counts(lib().dsb_ctx_lca_counts, self.h, "dsb_ctx_lca_counts")
+
     def in_last_batch(self):
         return self.ran[1]
 
@@ -498,6 +552,29 @@ class Multi:
         """Ctx.abundance over the contexts' reads together"""
         return _abundance(lib().dsb_multi_abundance, self.h, self.index.n_ref, max_iter, tol, "dsb_multi_abundance")
 
+    def enable_lca(self, on=True, min_frac=0.95):
+        rc = lib().dsb_multi_enable_lca(self.h, 1 if on else 0, _permille(min_frac) if on else 0)
+        if rc != 0:
+            raise DsbError(rc, "dsb_multi_enable_lca")
+
+    def reset_lca(self):
+        for i in range(int(lib().dsb_multi_n(self.h))):
+            rc = lib().dsb_ctx_reset_lca(lib().dsb_multi_ctx(self.h, i))
+            if rc != 0:
+                raise DsbError(rc, "dsb_ctx_reset_lca")
+
+    def lca(self):
+        """Ctx.lca for the last classify(), in input order"""
+        p = C.POINTER(DsbReadLca)()
+        rc = lib().dsb_multi_lca(self.h, C.byref(p))
+        if rc != 0:
+            raise DsbError(rc, "dsb_multi_lca")
+        return _lca(p, getattr(self, "n_last", 0))
+
+    def lca_counts(self):
+        """Ctx.lca_counts over the contexts' reads together"""
+        return _lca_counts(lib().dsb_multi_lca_counts, self.h, "dsb_multi_lca_counts")
+
     def taxa(self, records=False):
         """Ctx.taxa for the last classify(), in input order"""
         p = C.POINTER(DsbReadTaxon)()
@@ -579,6 +656,75 @@ def format_coverage(index, cov):
         if n >= 0:
             return buf.raw[:n]
         cap *= 4
+
+
+def _lca(p, n):
+    import numpy as np
+    out = np.zeros(n, dtype=LCA_DTYPE)
+    if n:
+        C.memmove(out.ctypes.data, p, n * C.sizeof(DsbReadLca))
+    return out
+
+
+def _lca_counts(fn, h, what):
+    import numpy as np
+    n, s = C.c_size_t(0), DsbLcaSummary()
+    rc = fn(h, None, 0, C.byref(n), C.byref(s))
+    if rc != 0:
+        raise DsbError(rc, what)
+    out = np.zeros(n.value, dtype=TAXON_COUNT_DTYPE)
+    if n.value:
+        rc = fn(h, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n), C.byref(s))
+        if rc != 0:
+            raise DsbError(rc, what)
+    return out, {f: getattr(s, f) for f in LCA_SUMMARY_FIELDS}
+
+
+def format_kraken(reads, lca):
+    """dsb_format_kraken over a batch: Kraken's per-read lines (bytes) of make_reads()'s array and Ctx/Multi.lca()'s records"""
+    import numpy as np
+    lca = np.ascontiguousarray(lca, dtype=LCA_DTYPE)
+    if len(lca) != len(reads):
+        raise ValueError("format_kraken: %d records for %d reads" % (len(lca), len(reads)))
+    out = []
+    for i in range(len(reads)):
+        cap = 256
+        while True:
+            buf = C.create_string_buffer(cap)
+            n = lib().dsb_format_kraken(C.byref(reads[i]), lca[i:i + 1].ctypes.data_as(C.c_void_p), buf, cap)
+            if n >= 0:
+                out.append(buf.raw[:n]); break
+            cap *= 4
+    return b"".join(out)
+
+
+def format_lca_report(taxonomy, rows, summary, names=None):
+    """dsb_lca_report_format: Kraken's report (bytes) of Ctx/Multi.lca_counts()'s rows and summary dict; names: a TaxNames or None"""
+    import numpy as np
+    rows = np.ascontiguousarray(rows, dtype=TAXON_COUNT_DTYPE)
+    s = DsbLcaSummary(**{f: summary[f] for f in LCA_SUMMARY_FIELDS})
+    cap = 1 << 16
+    while True:
+        buf = C.create_string_buffer(cap)
+        n = lib().dsb_lca_report_format(taxonomy.h, names.h if names is not None else None, rows.ctypes.data_as(C.c_void_p), len(rows), C.byref(s), buf, cap)
+        if n >= 0:
+            return buf.raw[:n]
+        cap *= 4
+
+
+class TaxNames:
+    """names.dmp: the "scientific name" of each taxid (for format_lca_report); DsbError DSB_EIO on a file that cannot be read"""
+
+    def __init__(self, path):
+        self.h = C.c_void_p()
+        rc = lib().dsb_taxnames_load(os.fsencode(path), C.byref(self.h))
+        if rc != 0:
+            raise DsbError(rc, "dsb_taxnames_load(%s)" % path)
+        self.path = path
+
+    def close(self):
+        if self.h:
+            lib().dsb_taxnames_close(self.h); self.h = C.c_void_p()
 
 
 class Taxonomy:

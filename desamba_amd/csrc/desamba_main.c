@@ -61,6 +61,7 @@ typedef struct {
 	gzbuf_t **gzb; int n_gzb, cap_gzb;                /* inflated blocks the reads point into */
 	dsb_read_result *rr; dsb_hit *hits; size_t cap_rr, cap_hits, n_hits;
 	dsb_read_taxon *taxa; size_t cap_taxa;            /* --report: the device's per-read taxa of the batch */
+	dsb_read_lca *lca; size_t cap_lca;                /* --kraken-out / --kraken-report: the device's per-read LCA records of the batch */
 } batch_t;
 
 typedef struct { batch_t *slot[N_BATCH + 2]; int head, n, closed; pthread_mutex_t mu; pthread_cond_t cv; } queue_t;
@@ -132,6 +133,8 @@ typedef struct {
 	gzbuf_t *gz_free; pthread_mutex_t gz_mu;
 	/* --taxonomy / --report / --report-base: the abundance report of `analysis ana_meta[_base]`, fed by the writer in input order */
 	dsb_taxonomy *tx; dsb_report *rep; FILE *rep_out[2];
+	/* --kraken-out / --kraken-report: LCA classification on; the per-read lines are written by the writer in input order */
+	int lca_on; FILE *kr_out;
 } app_t;
 
 /* ================================================================ gzip input: inflate ahead of the parser ==========
@@ -759,6 +762,12 @@ static void *gpu_main(void *arg)
 				if (b->n > b->cap_taxa) { b->cap_taxa = b->n * 2; b->taxa = xrealloc(b->taxa, b->cap_taxa * sizeof *b->taxa); }
 				memcpy(b->taxa, t, b->n * sizeof *b->taxa);
 			}
+			if (a->lca_on) {
+				const dsb_read_lca *t; int rt = dsb_batch_lca(ctx, &t);
+				if (rt) { fprintf(stderr, "[dsb_batch_lca] %s\n", dsb_strerror(rt)); exit(1); }
+				if (b->n > b->cap_lca) { b->cap_lca = b->n * 2; b->lca = xrealloc(b->lca, b->cap_lca * sizeof *b->lca); }
+				memcpy(b->lca, t, b->n * sizeof *b->lca);
+			}
 			t_idle = now();
 		}
 		q_push(&a->done_q, b);
@@ -820,6 +829,17 @@ static void *writer_main(void *arg)
 			int rc = dsb_report_add(a->rep, a->idx, b->reads, &res, b->taxa, b->n, a->o.max_sec_N);
 			if (rc) { fprintf(stderr, "[dsb_report_add] %s\n", dsb_strerror(rc)); exit(1); }
 		}
+		if (a->kr_out) {
+			/* Kraken's per-read lines of the batch, from the device's records, in input order */
+			static char *kb; static size_t kcap;
+			for (size_t i = 0; i < b->n; i++) {
+				const size_t need = strlen(b->reads[i].name) + 64;
+				if (need > kcap) { kcap = need * 2; kb = xrealloc(kb, kcap); }
+				long w = dsb_format_kraken(&b->reads[i], &b->lca[i], kb, kcap);
+				if (w < 0) die("[dsb_format_kraken] buffer too small");
+				if (fwrite(kb, 1, (size_t)w, a->kr_out) != (size_t)w) die("[classify] cannot write the per-read classifications");
+			}
+		}
 		if (a->trace) fprintf(stderr, "[writer] batch %ld written at %.3f s\n", b->seqno, now() - a->t0);
 		a->total += b->n;
 		next++;
@@ -849,7 +869,13 @@ static void usage(void)
 	fprintf(stderr, "    --report-base FILE  the same for `analysis ana_meta_base` (bases weighted by MAPQ)\n");
 	fprintf(stderr, "    --coverage FILE  write the coverage of every reference the run touched into FILE (columns of `samtools coverage`)\n");
 	fprintf(stderr, "    --abundance FILE  write the reads and shares per reference, estimated by EM over each read's near-best references, into FILE\n");
-	fprintf(stderr, "    --abundance-min-frac F  a read's candidates: references whose AS is at least F x its best AS, 0 < F <= 1 [0.95]\n\n");
+	fprintf(stderr, "    --abundance-min-frac F  a read's candidates: references whose AS is at least F x its best AS, 0 < F <= 1 [0.95]\n");
+	fprintf(stderr, "    --kraken-out FILE  classify each read by the lowest common ancestor of its near-best hits (needs --taxonomy) and write Kraken's\n");
+	fprintf(stderr, "                     per-read lines into FILE: C|U, read name, taxid, read length, then <best AS>:<near-best hits> (Kraken\n");
+	fprintf(stderr, "                     puts its k-mer string in that fifth column; the first four are Kraken's)\n");
+	fprintf(stderr, "    --kraken-report FILE  write the reads per taxon of that classification into FILE in the format of `kraken2 --report` (needs --taxonomy)\n");
+	fprintf(stderr, "    --names FILE     names.dmp: the report prints scientific names instead of taxids\n");
+	fprintf(stderr, "    --lca-min-frac F  near-best: hits whose AS is at least F x the read's best AS, 0 < F <= 1 [0.95]\n\n");
 }
 
 static double now(void) { struct timeval tv; gettimeofday(&tv, NULL); return tv.tv_sec + tv.tv_usec * 1e-6; }
@@ -901,6 +927,15 @@ static void trace_summary(const app_t *a, double sec)
 		        t->run_s[k], t->fetch_s[k], t->idle_s[k], sec, 100.0 * (t->up_s[k] + t->run_s[k] + t->fetch_s[k]) / (sec > 0 ? sec : 1));
 }
 
+/* --names: names.dmp, or the message of the failure */
+static int rc_names(const char *path, dsb_taxnames **names)
+{
+	int rt = dsb_taxnames_load(path, names);
+	if (rt == DSB_EIO) fprintf(stderr, "[classify] fail to open file '%s'\n", path);
+	else if (rt) fprintf(stderr, "[classify] --names %s: %s\n", path, dsb_strerror(rt));
+	return rt;
+}
+
 static int classify_main(int argc, char **argv)
 {
 	static app_t a; int c;
@@ -908,9 +943,11 @@ static int classify_main(int argc, char **argv)
 	a.o.L_min_matching = 170; a.o.min_score = 64; a.o.max_sec_N = 5; a.o.n_slots = 0; a.out = stdout;
 	static const struct option long_opts[] = {{"taxonomy", required_argument, NULL, 1}, {"report", required_argument, NULL, 2}, {"report-base", required_argument, NULL, 3},
 	                                              {"coverage", required_argument, NULL, 4}, {"abundance", required_argument, NULL, 5},
-	                                              {"abundance-min-frac", required_argument, NULL, 6}, {NULL, 0, NULL, 0}};
-	const char *tax_path = NULL, *rep_path[2] = {NULL, NULL}, *cov_path = NULL, *ab_path = NULL;
-	uint32_t ab_permille = 950;
+	                                              {"abundance-min-frac", required_argument, NULL, 6}, {"kraken-out", required_argument, NULL, 7},
+	                                              {"kraken-report", required_argument, NULL, 8}, {"names", required_argument, NULL, 9},
+	                                              {"lca-min-frac", required_argument, NULL, 10}, {NULL, 0, NULL, 0}};
+	const char *tax_path = NULL, *rep_path[2] = {NULL, NULL}, *cov_path = NULL, *ab_path = NULL, *kr_path = NULL, *krep_path = NULL, *names_path = NULL;
+	uint32_t ab_permille = 950, lca_permille = 950; int lca_frac_set = 0;
 	while ((c = getopt_long(argc, argv, "ht:l:r:f:o:s:g:", long_opts, NULL)) >= 0) {
 		if (c == 'h') { usage(); return 0; }
 		else if (c == 1) tax_path = optarg;
@@ -921,6 +958,14 @@ static int classify_main(int argc, char **argv)
 			char *e; const double f = strtod(optarg, &e);
 			if (e == optarg || *e || !(f > 0 && f <= 1) || f * 1000 + 0.5 < 1) die("[classify] --abundance-min-frac takes a number F with 0 < F <= 1 (steps of 0.001)");
 			ab_permille = (uint32_t)(f * 1000 + 0.5);
+		}
+		else if (c == 7) kr_path = optarg;
+		else if (c == 8) krep_path = optarg;
+		else if (c == 9) names_path = optarg;
+		else if (c == 10) {
+			char *e; const double f = strtod(optarg, &e);
+			if (e == optarg || *e || !(f > 0 && f <= 1) || f * 1000 + 0.5 < 1) die("[classify] --lca-min-frac takes a number F with 0 < F <= 1 (steps of 0.001)");
+			lca_permille = (uint32_t)(f * 1000 + 0.5); lca_frac_set = 1;
 		}
 		else if (c == 't') { /* thread count: accepted for compatibility, unused */ }
 		else if (c == 'l') a.o.L_min_matching = atoi(optarg);
@@ -955,6 +1000,9 @@ static int classify_main(int argc, char **argv)
 		if (strcmp(argv[i], "-") != 0 && access(argv[i], R_OK) != 0) { fprintf(stderr, "[xzopen] fail to open file '%s'\n", argv[i]); exit(1); }
 	}
 	if ((rep_path[0] || rep_path[1]) && !tax_path) die("[classify] --report and --report-base need --taxonomy nodes.dmp");
+	if ((kr_path || krep_path || names_path || lca_frac_set) && !tax_path) die("[classify] --kraken-out, --kraken-report, --names and --lca-min-frac need --taxonomy nodes.dmp");
+	a.lca_on = kr_path || krep_path;
+	dsb_taxnames *names = NULL;
 	if (tax_path) {
 		int rt = dsb_taxonomy_load(tax_path, &a.tx);
 		if (rt == DSB_EIO) { fprintf(stderr, "[classify] fail to open file '%s'\n", tax_path); exit(1); }
@@ -963,6 +1011,10 @@ static int classify_main(int argc, char **argv)
 			if (rep_path[k] && !(a.rep_out[k] = fopen(rep_path[k], "w"))) { fprintf(stderr, "[xopen] fail to open file '%s'\n", rep_path[k]); exit(1); }
 		if ((rep_path[0] || rep_path[1]) && dsb_report_create(a.tx, &a.rep)) die("[classify] out of memory");
 	}
+	FILE *krep_out = NULL;
+	if (names_path && (rc_names(names_path, &names))) exit(1);
+	if (kr_path && !(a.kr_out = fopen(kr_path, "w"))) { fprintf(stderr, "[xopen] fail to open file '%s'\n", kr_path); exit(1); }
+	if (krep_path && !(krep_out = fopen(krep_path, "w"))) { fprintf(stderr, "[xopen] fail to open file '%s'\n", krep_path); exit(1); }
 	FILE *cov_out = NULL;
 	if (cov_path && !(cov_out = fopen(cov_path, "w"))) { fprintf(stderr, "[xopen] fail to open file '%s'\n", cov_path); exit(1); }
 	FILE *ab_out = NULL;
@@ -981,9 +1033,10 @@ static int classify_main(int argc, char **argv)
 	rc = dsb_ctx_create_multi(a.idx, ids, a.n_ctx, &a.o, &a.multi);
 	if (rc) { fprintf(stderr, "\n[dsb_ctx_create] %s\n", dsb_strerror(rc)); exit(1); }
 	for (int k = 0; k < a.n_ctx; k++) a.ctx[k] = dsb_multi_ctx(a.multi, k);
-	if (a.rep && (rc = dsb_multi_set_taxonomy(a.multi, a.tx))) { fprintf(stderr, "\n[dsb_ctx_set_taxonomy] %s\n", dsb_strerror(rc)); exit(1); }
+	if ((a.rep || a.lca_on) && (rc = dsb_multi_set_taxonomy(a.multi, a.tx))) { fprintf(stderr, "\n[dsb_ctx_set_taxonomy] %s\n", dsb_strerror(rc)); exit(1); }
 	if (cov_out && (rc = dsb_multi_enable_coverage(a.multi, 1))) { fprintf(stderr, "\n[dsb_ctx_enable_coverage] %s\n", dsb_strerror(rc)); exit(1); }
 	if (ab_out && (rc = dsb_multi_enable_abundance(a.multi, 1, ab_permille))) { fprintf(stderr, "\n[dsb_ctx_enable_abundance] %s\n", dsb_strerror(rc)); exit(1); }
+	if (a.lca_on && (rc = dsb_multi_enable_lca(a.multi, 1, lca_permille))) { fprintf(stderr, "\n[dsb_ctx_enable_lca] %s\n", dsb_strerror(rc)); exit(1); }
 	double t0 = now(), cpu0 = cputime(); a.t0 = t0;
 	a.thr0 = a.trace ? throttled_usec() : -1;
 	fprintf(stderr, "Start classify\n");
@@ -1035,6 +1088,22 @@ static int classify_main(int argc, char **argv)
 		if (fwrite(buf, 1, (size_t)w, ab_out) != (size_t)w || fclose(ab_out)) die("[classify] cannot write the abundance table");
 		free(buf); free(ab);
 	}
+	if (a.kr_out && fclose(a.kr_out)) die("[classify] cannot write the per-read classifications");
+	if (krep_out) {
+		/* --kraken-report: the run's reads per taxon, the contexts' counts added and rolled up on the device */
+		size_t n_rows = 0; dsb_lca_summary sum;
+		const double tl = now();
+		if ((rc = dsb_multi_lca_counts(a.multi, NULL, 0, &n_rows, &sum))) { fprintf(stderr, "[dsb_multi_lca_counts] %s\n", dsb_strerror(rc)); exit(1); }
+		dsb_taxon_count *rows = xrealloc(NULL, (n_rows ? n_rows : 1) * sizeof *rows);
+		if (n_rows && (rc = dsb_multi_lca_counts(a.multi, rows, n_rows, &n_rows, &sum))) { fprintf(stderr, "[dsb_multi_lca_counts] %s\n", dsb_strerror(rc)); exit(1); }
+		fprintf(stderr, "[classify] lca: %llu of %llu reads classified (%llu ambiguous, %llu without a taxon), %zu taxa, roll-up %.1f ms\n", (unsigned long long)sum.classified,
+		        (unsigned long long)sum.reads, (unsigned long long)sum.ambiguous, (unsigned long long)sum.no_taxon, n_rows, 1e3 * (now() - tl));
+		size_t cap = 1 << 16; char *buf = NULL; long w;
+		do { cap *= 4; buf = xrealloc(buf, cap); w = dsb_lca_report_format(a.tx, names, rows, n_rows, &sum, buf, cap); } while (w < 0);
+		if (fwrite(buf, 1, (size_t)w, krep_out) != (size_t)w || fclose(krep_out)) die("[classify] cannot write the report");
+		free(buf); free(rows);
+	}
+	dsb_taxnames_close(names);
 	dsb_report_destroy(a.rep);
 	dsb_multi_destroy(a.multi);
 	dsb_taxonomy_close(a.tx);

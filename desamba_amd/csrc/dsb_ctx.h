@@ -74,7 +74,7 @@ struct dsb_ctx {
 	uint32_t *dbg_host = nullptr, *dbg_dev = nullptr;
 	std::vector<UpStage> up; size_t up_chunk = 0;     // pinned staging of dsb_batch_upload (upload_gather)
 	dsb_opts opts;
-	DsbTaxa taxa; DsbCover cover; DsbEmStore em;   // the run reductions (dsb_reductions.h)
+	DsbTaxa taxa; DsbCover cover; DsbEmStore em; DsbLca lca;   // the run reductions (dsb_reductions.h)
 	dsb_ctx() { memset(&dx, 0, sizeof dx); memset(&arena, 0, sizeof arena); memset(&arena_big, 0, sizeof arena_big); memset(&arena_anc, 0, sizeof arena_anc); memset(&timing, 0, sizeof timing); memset(&opts, 0, sizeof opts); }
 };
 
@@ -84,6 +84,7 @@ struct dsb_multi {
 	std::vector<uint32_t> last_calls;             // dsb_classify_batch calls each context made in the last dsb_multi_classify_batch
 	std::vector<dsb_read_result> reads; std::vector<dsb_hit> hits;
 	const dsb_taxonomy *tx = nullptr; std::vector<dsb_read_taxon> taxa; bool taxa_ok = false;   // dsb_multi_set_taxonomy / dsb_multi_taxa
+	std::vector<dsb_read_lca> lca; bool lca_on = false, lca_ok = false;                          // dsb_multi_enable_lca / dsb_multi_lca
 };
 
 // a device buffer grown to hold at least `need` elements (its contents are not kept)

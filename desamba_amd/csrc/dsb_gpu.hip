@@ -7,7 +7,7 @@
 //                 src/cly.c:360-398), two hashed 1-bit probes (get_exist_kmer, src/cly.c:956-972),
 //                 one ballot -> one 64-bit word of hit bits per wave iteration.  HBM/L3-bound gather.
 //   k_classify    persistent, one read per wavefront, everything after the probes (dsb_classify_dev.h)
-// The run reductions that read a batch's hits after its last classify launch (taxa, coverage, abundance): dsb_reductions.hip.
+// The run reductions that read a batch's hits after its last classify launch (taxa, coverage, abundance, LCA): dsb_reductions.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -1521,6 +1521,7 @@ static int batch_run_locked(dsb_ctx *c, std::unique_lock<std::mutex> *turn)
 	memset(&c->timing, 0, sizeof c->timing);
 	c->timing.upload_bytes = s.upload_bytes;
 	c->taxa.run = c->taxa.tx != nullptr && n == 0; c->taxa.done = false;
+	c->lca.run = c->lca.d_direct != nullptr && n == 0; c->lca.done = false;
 	if (n == 0) return DSB_OK;
 	HIPCHK(hipMemsetAsync(c->d_counters, 0, 256, c->stream));
 	HIPCHK(hipEventRecord(c->ev[0], c->stream));
@@ -1945,6 +1946,7 @@ extern "C" int dsb_multi_classify_batch(dsb_multi *m, const dsb_read *reads, siz
 	dsb_shard_plan(len.data(), n, W, chunk_bases, chunk_reads, plan.data(), nc, &nc);
 	m->reads.assign(n, dsb_read_result());
 	m->taxa_ok = false; if (m->tx) m->taxa.assign(n, dsb_read_taxon());
+	m->lca_ok = false; if (m->lca_on) m->lca.assign(n, dsb_read_lca());
 	std::vector<std::vector<dsb_hit>> chunk_hits(nc);
 	std::vector<int> rcs(W, DSB_OK);
 	const uint32_t hist0 = m->hist;
@@ -1966,6 +1968,11 @@ extern "C" int dsb_multi_classify_batch(dsb_multi *m, const dsb_read *reads, siz
 				const dsb_read_taxon *t = nullptr;
 				if ((rc = dsb_batch_taxa(c, &t))) { rcs[w] = rc; return; }
 				std::copy(t, t + (ch.end - ch.start), m->taxa.begin() + (ptrdiff_t)ch.start);
+			}
+			if (m->lca_on) {
+				const dsb_read_lca *t = nullptr;
+				if ((rc = dsb_batch_lca(c, &t))) { rcs[w] = rc; return; }
+				std::copy(t, t + (ch.end - ch.start), m->lca.begin() + (ptrdiff_t)ch.start);
 			}
 			std::vector<dsb_hit> &H = chunk_hits[k];
 			for (uint64_t i = ch.start; i < ch.end; i++) {
@@ -1991,7 +1998,7 @@ extern "C" int dsb_multi_classify_batch(dsb_multi *m, const dsb_read *reads, siz
 	}
 	for (size_t i = 0; i < n; i++) if (len[i] > m->hist) m->hist = len[i];
 	out->reads = m->reads.data(); out->hits = m->hits.data(); out->n_hits = m->hits.size();
-	m->taxa_ok = m->tx != nullptr;
+	m->taxa_ok = m->tx != nullptr; m->lca_ok = m->lca_on;
 	return worst;
 }
 #endif  // DSB_UNIT_HOST

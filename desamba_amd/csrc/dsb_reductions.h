@@ -1,5 +1,6 @@
 // The run reductions of classify: per-read taxa (dsb_ctx_set_taxonomy), per-reference coverage (dsb_ctx_enable_coverage,
-// DESIGN 2.9) and per-reference abundance by EM (dsb_ctx_enable_abundance).  Each reads a batch's hit buffer
+// DESIGN 2.9), per-reference abundance by EM (dsb_ctx_enable_abundance) and per-read LCA classification
+// (dsb_ctx_enable_lca).  Each reads a batch's hit buffer
 // after its last classify launch, keeps state for the whole run and is merged across the contexts of a dsb_multi
 // (dsb_reductions.hip).  Internal: the public surface is include/desamba_amd.h.
 #pragma once
@@ -31,6 +32,17 @@ struct DsbEmStore {
 	size_t cap_sets = 0, cap_elems = 0, used_sets = 0, used_elems = 0; uint64_t reads = 0; uint32_t permille = 0;
 };
 
+// LCA classification: a depth table beside DsbTaxa's parent table (u16, DSB_DEPTH_UNROOTED for an unrooted taxid), the
+// batch's per-read records, and the run's counts -- direct[t] = reads whose LCA is t (max_tid + 1 u64), sum = {reads, classified,
+// no_taxon, ambiguous}; clade is the roll-up's table, zeroed and filled by every dsb_ctx_lca_counts.  One k_read_lca and one
+// k_lca_count launch per batch.  On exactly when d_direct is set.
+struct DsbLca {
+	uint16_t *d_depth = nullptr; unsigned long long *d_direct = nullptr, *d_clade = nullptr, *d_sum = nullptr;
+	dsb_read_lca *d_rec = nullptr; size_t cap_rec = 0; std::vector<dsb_read_lca> h_rec;
+	uint32_t permille = 0;
+	bool run = false, done = false;               // as DsbTaxa's
+};
+
 // a batch's results on the device after its last classify launch (the second runs and the run after a regrown hit buffer included)
 struct DsbBatchView {
 	hipStream_t st;
@@ -41,7 +53,7 @@ struct DsbBatchView {
 struct dsb_ctx;
 // dsb_batch_run: the launches of the reductions that are on, on b.st
 int reductions_run(dsb_ctx *c, const DsbBatchView &b);
-// dsb_batch_fetch, once the copies of the batch's reads and hits are queued on c's stream: queues the copy of the batch's taxa,
+// dsb_batch_fetch, once the copies of the batch's reads and hits are queued on c's stream: queues the copy of the batch's taxa and LCA records,
 // waits for all of them (one synchronisation, skipped when nothing was queued) and gives the reads the device left to the host
 // their taxon
 int reductions_fetch(dsb_ctx *c, size_t n, bool queued);

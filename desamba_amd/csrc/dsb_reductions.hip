@@ -1,5 +1,5 @@
 // The run reductions of classify (dsb_reductions.h): per-read taxa, per-reference coverage and per-reference
-// abundance by EM -- their kernels, the launches after a batch's last classify launch (reductions_run), the
+// abundance by EM, per-read LCA classification -- their kernels, the launches after a batch's last classify launch (reductions_run), the
 // host side of each, and their merges over the contexts of a dsb_multi.
 #include <algorithm>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -341,6 +341,148 @@ __global__ void __launch_bounds__(256) k_em_rebase(DsbEmSet *sets, uint32_t n, u
 	if (i < n) sets[i].off += base;
 }
 
+// ---- per-read LCA classification (dsb_ctx_enable_lca) ----
+// The lowest common ancestor of two rooted taxids, 0 standing for "nothing yet" (the neutral value: taxid 0 is never rooted).  The
+// deeper node is lifted to the other's depth, then both are lifted until they meet -- at taxid 1 at the latest, since both chains
+// reach it.  *d follows the result's depth.  Every walk stops after `bound` steps (max_depth + 2, as k_read_taxon's).
+__device__ inline uint32_t lca_join(uint32_t a, uint32_t da, uint32_t b, uint32_t db, const uint32_t *__restrict__ parent, uint32_t bound, uint32_t *d)
+{
+	if (!a) { *d = db; return b; }
+	if (!b) { *d = da; return a; }
+	for (uint32_t s = 0; da > db && s < bound; s++) { a = parent[a]; da--; }
+	for (uint32_t s = 0; db > da && s < bound; s++) { b = parent[b]; db--; }
+	for (uint32_t s = 0; a != b && da && s < bound; s++) { a = parent[a]; b = parent[b]; da--; }
+	*d = da;
+	return a;
+}
+
+// One wavefront per read, after the batch's last classify work (the hits dsb_batch_fetch hands out: dsb_hits_out, dsb_hits_cut), for
+// the reason k_em_collect gives: a strain-dense read has hundreds of hits.  Pass 1: S_max by wave-max over the hits on references
+// < n_ref.  Pass 2: lane j takes the hits j, j + 64, ...; a passing hit (AS * 1000 >= S_max * min_permille) whose reference's taxid is
+// rooted (depth table) is folded into the lane's LCA; n_pass is the sum of the rounds' ballots.  Then a 6-step xor butterfly with
+// lca_join as the operator -- it is associative, commutative and idempotent, so every lane ends with the LCA of all.  AMBIGUOUS: a
+// lane saw two taxids, or a ballot finds a lane whose first taxid is not the first lane's.  Lane 0 writes the record.
+__global__ void __launch_bounds__(256) k_read_lca(const DsbReadOut *__restrict__ rout, const DsbHitOut *__restrict__ hout, const unsigned int *__restrict__ counters,
+                                                  uint32_t cap_hout, uint32_t n, const uint32_t *__restrict__ parent, const uint16_t *__restrict__ depth,
+                                                  const uint32_t *__restrict__ ref_tid, uint32_t n_ref, uint32_t max_tid, uint32_t bound, uint32_t min_permille,
+                                                  dsb_read_lca *__restrict__ out)
+{
+	const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+	if (i >= n) return;
+	const uint32_t nh = dsb_hits_out(counters[1], cap_hout);
+	const DsbReadOut r = rout[i];
+	const uint32_t nrec = dsb_hits_cut(r.first, r.n, nh) ? 0u : r.n;
+	const DsbHitOut *h = hout + r.first;
+	dsb_read_lca o; o.taxid = 0; o.score = 0; o.n_pass = 0; o.depth = 0; o.flags = 0; o.pad = 0;
+	uint32_t smax = 0; bool valid = false;
+	for (uint32_t q = lane; q < nrec; q += 64) if (h[q].ref_ID < n_ref) { valid = true; smax = h[q].sum_score > smax ? h[q].sum_score : smax; }
+	if (!__ballot(valid)) { if (lane == 0) out[i] = o; return; }   // unclassified (or only hits on references beyond the index)
+	smax = wave_max_u32(smax);
+	const uint64_t thr = (uint64_t)smax * min_permille;
+	uint32_t mine = 0, mine_d = 0, first = 0, n_pass = 0; bool two = false;
+	for (uint32_t q0 = 0; q0 < nrec; q0 += 64) {
+		const uint32_t q = q0 + lane;
+		const bool pass = q < nrec && h[q].ref_ID < n_ref && (uint64_t)h[q].sum_score * 1000u >= thr;
+		n_pass += (uint32_t)__popcll(__ballot(pass));
+		if (!pass) continue;
+		const uint32_t t = ref_tid[h[q].ref_ID];
+		if (t < 1 || t > max_tid) continue;                       // (DSB_TID_NONE included)
+		const uint32_t d = depth[t];
+		if (d == DSB_DEPTH_UNROOTED) continue;
+		if (!first) first = t; else if (t != first) two = true;
+		mine = lca_join(mine, mine_d, t, d, parent, bound, &mine_d);
+	}
+	const uint64_t have = __ballot(first != 0);
+	bool amb = false;
+	if (have) {
+		const uint32_t lead = __shfl(first, __ffsll((unsigned long long)have) - 1, 64);
+		amb = __ballot(two || (first != 0 && first != lead)) != 0;
+	}
+	for (int s = 32; s; s >>= 1) {
+		const uint32_t t = __shfl_xor(mine, s, 64), d = __shfl_xor(mine_d, s, 64);
+		mine = lca_join(mine, mine_d, t, d, parent, bound, &mine_d);
+	}
+	if (lane) return;
+	o.taxid = mine; o.score = smax; o.n_pass = n_pass; o.depth = (uint16_t)(mine ? mine_d : 0);
+	o.flags = (uint8_t)(DSB_LCA_CLASSIFIED | (mine ? 0 : DSB_LCA_NO_TAXON) | (amb ? DSB_LCA_AMBIGUOUS : 0));
+	out[i] = o;
+}
+
+// One lane per read, behind k_read_lca on the same stream: the run's direct counts and summary.  Most reads of a sample share a
+// few taxa, and one atomic per read on a hot line is what k_em_collect's first version paid for: equal taxids are
+// grouped inside the wavefront first -- the taxid of the first lane still waiting, a ballot of the lanes that hold it, one atomicAdd
+// of the group's size by that lane -- so a wavefront issues one add per distinct taxid.  The summary the same way: one add per
+// counter and wavefront.  Integer adds only: the sums do not depend on the order.  sum: [0] reads, [1] classified (taxid != 0),
+// [2] NO_TAXON, [3] AMBIGUOUS.
+__global__ void __launch_bounds__(256) k_lca_count(const dsb_read_lca *__restrict__ rec, uint32_t n, uint32_t max_tid, unsigned long long *direct,
+                                                   unsigned long long *sum)
+{
+	const uint32_t i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+	const bool live = i < n;
+	dsb_read_lca r; r.taxid = 0; r.flags = 0;
+	if (live) r = rec[i];
+	const uint32_t tid = r.taxid <= max_tid ? r.taxid : 0;         // (k_read_lca writes no taxid above max_tid)
+	uint64_t left = __ballot(live && tid != 0);
+	const unsigned long long n_cls = (unsigned long long)__popcll(left);
+	while (left) {
+		const int src = __ffsll((unsigned long long)left) - 1;
+		const uint32_t t = __shfl(tid, src, 64);
+		const uint64_t m = __ballot(live && tid == t);
+		if ((int)lane == src) atomicAdd(direct + t, (unsigned long long)__popcll(m));
+		left &= ~m;
+	}
+	const unsigned long long n_live = (unsigned long long)__popcll(__ballot(live));
+	const unsigned long long n_not = (unsigned long long)__popcll(__ballot(live && (r.flags & DSB_LCA_NO_TAXON)));
+	const unsigned long long n_amb = (unsigned long long)__popcll(__ballot(live && (r.flags & DSB_LCA_AMBIGUOUS)));
+	if (lane == 0) {
+		if (n_live) atomicAdd(sum + 0, n_live);
+		if (n_cls) atomicAdd(sum + 1, n_cls);
+		if (n_not) atomicAdd(sum + 2, n_not);
+		if (n_amb) atomicAdd(sum + 3, n_amb);
+	}
+}
+
+// The roll-up of dsb_ctx_lca_counts, reading direct only.  cnt: [0] listed taxids, [1] nodes with clade > 0.
+// k_lca_list: the taxids with direct > 0 (in any order: only integer sums follow)
+__global__ void __launch_bounds__(256) k_lca_list(const unsigned long long *__restrict__ direct, uint32_t max_tid, uint32_t *__restrict__ list, unsigned int *cnt)
+{
+	const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	if (t >= 1 && t <= max_tid && direct[t]) list[atomicAdd(cnt, 1u)] = (uint32_t)t;
+}
+
+// one lane per listed taxid: its count is added to clade[] of every node from it to taxid 1 (few nodes times depth: contention does
+// not matter here); the lane that finds a node at 0 lists it (a count is never 0, so exactly one does).  Listed taxids are rooted.
+__global__ void __launch_bounds__(256) k_lca_rollup(const unsigned long long *__restrict__ direct, const uint32_t *__restrict__ list, uint32_t n_list,
+                                                    const uint32_t *__restrict__ parent, uint32_t max_tid, uint32_t bound, unsigned long long *clade,
+                                                    uint32_t *__restrict__ nodes, uint32_t cap_nodes, unsigned int *cnt)
+{
+	const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+	if (k >= n_list) return;
+	const unsigned long long c = direct[list[k]];
+	uint32_t p = list[k];
+	for (uint32_t s = 0; s < bound && p >= 1 && p <= max_tid; s++) {
+		if (atomicAdd(clade + p, c) == 0) { const uint32_t at = atomicAdd(cnt + 1, 1u); if (at < cap_nodes) nodes[at] = p; }
+		if (p == 1) break;
+		p = parent[p];
+	}
+}
+
+// the rows of the nodes (sorted by taxid before this)
+__global__ void __launch_bounds__(256) k_lca_rows(const uint32_t *__restrict__ nodes, uint32_t n, const unsigned long long *__restrict__ clade,
+                                                  const unsigned long long *__restrict__ direct, dsb_taxon_count *__restrict__ rows)
+{
+	const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+	if (k >= n) return;
+	dsb_taxon_count o; o.taxid = nodes[k]; o.pad = 0; o.clade_reads = clade[o.taxid]; o.direct_reads = direct[o.taxid];
+	rows[k] = o;
+}
+
+// dsb_multi_lca_counts: dst += src over n counters
+__global__ void __launch_bounds__(256) k_lca_add(unsigned long long *__restrict__ dst, const unsigned long long *__restrict__ src, uint64_t n)
+{
+	for (uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x; q < n; q += (uint64_t)gridDim.x * 256) dst[q] += src[q];
+}
+
 // ================================== host side ====================================================
 // temporary device buffers of one call (em_solve, the merges of a dsb_multi), freed together when it returns
 struct DevScratch {
@@ -355,12 +497,14 @@ struct DevScratch {
 };
 
 // ---- taxonomy ----
+static void lca_free(dsb_ctx *c);
 extern "C" int dsb_ctx_set_taxonomy(dsb_ctx *c, const dsb_taxonomy *tx)
 {
 	if (!c) return DSB_EINVAL;
 	if (tx && !tx->acyclic) return DSB_EINVAL;                 // (dsb_taxonomy_load_any: the device's walks need the bound)
 	HIPCHK(hipSetDevice(c->device));
 	HIPCHK(hipStreamSynchronize(c->stream));
+	lca_free(c);                                               // (LCA reads this taxonomy's tables: a ctx whose LCA is on leaves it here)
 	hipFree(c->taxa.d_parent); hipFree(c->taxa.d_ref_tid); c->taxa.d_parent = c->taxa.d_ref_tid = nullptr;
 	c->taxa.tx = nullptr; c->taxa.run = c->taxa.done = false;
 	if (!tx) { hipFree(c->taxa.d_taxa); c->taxa.d_taxa = nullptr; c->taxa.cap_taxa = 0; return DSB_OK; }
@@ -665,6 +809,115 @@ extern "C" int dsb_ctx_abundance(dsb_ctx *c, const dsb_em_opts *opts, dsb_ref_ab
 	return em_solve(c->stream, c->idx, c->em.d_sets, c->em.d_elems, (uint32_t)cnt[0], (uint32_t)cnt[1], c->em.reads, c->em.permille, o, out, summary);
 }
 
+// ---- per-read LCA classification ----
+#define DSB_LCA_SUM 4
+static void lca_free(dsb_ctx *c)
+{
+	hipFree(c->lca.d_depth); hipFree(c->lca.d_direct); hipFree(c->lca.d_clade); hipFree(c->lca.d_sum); hipFree(c->lca.d_rec);
+	c->lca = DsbLca();
+}
+
+extern "C" int dsb_ctx_reset_lca(dsb_ctx *c)
+{
+	if (!c || !c->lca.d_direct) return DSB_EINVAL;
+	HIPCHK(hipSetDevice(c->device));
+	HIPCHK(hipMemsetAsync(c->lca.d_direct, 0, ((size_t)c->taxa.tx->max_tid + 1) * 8, c->stream));
+	HIPCHK(hipMemsetAsync(c->lca.d_sum, 0, DSB_LCA_SUM * 8, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	return DSB_OK;
+}
+
+extern "C" int dsb_ctx_enable_lca(dsb_ctx *c, int on, uint32_t min_permille)
+{
+	if (!c || (on && (min_permille < 1 || min_permille > 1000))) return DSB_EINVAL;
+	const dsb_taxonomy *tx = c->taxa.tx;
+	if (on && (!tx || !tx->depth || tx->max_depth + 2 >= DSB_DEPTH_UNROOTED)) return DSB_EINVAL;
+	HIPCHK(hipSetDevice(c->device));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	if (on && c->lca.d_direct) { c->lca.permille = min_permille; return dsb_ctx_reset_lca(c); }
+	lca_free(c);
+	if (!on) return DSB_OK;
+	const size_t nt = (size_t)tx->max_tid + 1;
+	if (hipMalloc((void **)&c->lca.d_depth, nt * 2) != hipSuccess || hipMalloc((void **)&c->lca.d_direct, nt * 8) != hipSuccess ||
+	    hipMalloc((void **)&c->lca.d_clade, nt * 8) != hipSuccess || hipMalloc((void **)&c->lca.d_sum, DSB_LCA_SUM * 8) != hipSuccess ||
+	    grow(&c->lca.d_rec, &c->lca.cap_rec, std::max(c->cap_rout, (size_t)c->opts.max_batch_reads))) {
+		lca_free(c); (void)hipGetLastError(); return DSB_ENOMEM;
+	}
+	HIPCHK(hipMemcpy(c->lca.d_depth, tx->depth, nt * 2, hipMemcpyHostToDevice));
+	c->lca.permille = min_permille;
+	return dsb_ctx_reset_lca(c);
+}
+
+extern "C" int dsb_batch_lca(dsb_ctx *c, const dsb_read_lca **out)
+{
+	if (!c || !out || !c->lca.d_direct || !c->lca.run) return DSB_EINVAL;
+	if (!c->lca.done) { dsb_result r; int rc = dsb_batch_fetch(c, &r); if (rc && rc != DSB_ECAP) return rc; }
+	*out = c->lca.h_rec.data();
+	return DSB_OK;
+}
+
+// The roll-up over a direct table on c's device, on stream st (after the batches it counted), reading it only: the taxids with
+// direct > 0 are listed, each adds its count along its chain to taxid 1 into c's clade table (zeroed first), the nodes that got a
+// count are sorted by taxid and their (taxid, clade, direct) rows are copied: the tables themselves never cross PCIe.
+static int lca_rollup(dsb_ctx *c, const unsigned long long *direct, hipStream_t st, dsb_taxon_count *out, size_t cap, size_t *n)
+{
+	const dsb_taxonomy *tx = c->taxa.tx;
+	const uint32_t max_tid = tx->max_tid, bound = tx->max_depth + 2;
+	DevScratch T;
+	uint32_t *list = T.get<uint32_t>((size_t)max_tid + 1);
+	unsigned int *cnt = T.get<unsigned int>(2);
+	if (!list || !cnt) return DSB_ENOMEM;
+	EMCK(hipMemsetAsync(cnt, 0, 8, st));
+	EMCK(hipMemsetAsync(c->lca.d_clade, 0, ((size_t)max_tid + 1) * 8, st));
+	hipLaunchKernelGGL(k_lca_list, dim3((unsigned)(((size_t)max_tid + 256) / 256)), dim3(256), 0, st, direct, max_tid, list, cnt);
+	unsigned int h[2] = {0, 0};
+	EMCK(hipMemcpyAsync(h, cnt, 4, hipMemcpyDeviceToHost, st));
+	EMCK(hipStreamSynchronize(st));
+	*n = 0;
+	if (!h[0]) return DSB_OK;
+	const size_t cap_nodes = std::min((size_t)h[0] * ((size_t)tx->max_depth + 1), (size_t)max_tid);
+	uint32_t *nodes = T.get<uint32_t>(cap_nodes), *sorted = T.get<uint32_t>(cap_nodes);
+	if (!nodes || !sorted) return DSB_ENOMEM;
+	hipLaunchKernelGGL(k_lca_rollup, dim3((h[0] + 255) / 256), dim3(256), 0, st, direct, (const uint32_t *)list, (uint32_t)h[0], (const uint32_t *)c->taxa.d_parent,
+	                   max_tid, bound, c->lca.d_clade, nodes, (uint32_t)cap_nodes, cnt);
+	EMCK(hipGetLastError());
+	EMCK(hipMemcpyAsync(h, cnt, 8, hipMemcpyDeviceToHost, st));
+	EMCK(hipStreamSynchronize(st));
+	if (h[1] > cap_nodes) return DSB_ENODEV;                   // (cannot happen: a node is listed once)
+	const uint32_t nn = h[1];
+	size_t tb = 0;
+	EMCK(rocprim::radix_sort_keys(nullptr, tb, nodes, sorted, nn, 0, 32, st));
+	void *tmp = T.get<uint8_t>(tb);
+	dsb_taxon_count *rows = T.get<dsb_taxon_count>(nn);
+	if (!tmp || !rows) return DSB_ENOMEM;
+	EMCK(rocprim::radix_sort_keys(tmp, tb, nodes, sorted, nn, 0, 32, st));
+	hipLaunchKernelGGL(k_lca_rows, dim3((nn + 255) / 256), dim3(256), 0, st, (const uint32_t *)sorted, nn, (const unsigned long long *)c->lca.d_clade, direct, rows);
+	EMCK(hipGetLastError());
+	*n = nn;
+	const size_t take = out ? std::min(cap, (size_t)nn) : 0;
+	if (take) EMCK(hipMemcpyAsync(out, rows, take * sizeof(dsb_taxon_count), hipMemcpyDeviceToHost, st));
+	EMCK(hipStreamSynchronize(st));
+	return out && cap < nn ? DSB_ECAP : DSB_OK;
+}
+
+// the summary counters of a context, read on its stream
+static int lca_sums(dsb_ctx *c, unsigned long long s[DSB_LCA_SUM])
+{
+	HIPCHK(hipSetDevice(c->device));
+	HIPCHK(hipMemcpyAsync(s, c->lca.d_sum, DSB_LCA_SUM * 8, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	return DSB_OK;
+}
+
+extern "C" int dsb_ctx_lca_counts(dsb_ctx *c, dsb_taxon_count *out, size_t cap, size_t *n, dsb_lca_summary *summary)
+{
+	if (!c || !n || !c->lca.d_direct) return DSB_EINVAL;
+	unsigned long long s[DSB_LCA_SUM];
+	if (int rc = lca_sums(c, s)) return rc;
+	if (summary) { summary->reads = s[0]; summary->classified = s[1]; summary->no_taxon = s[2]; summary->ambiguous = s[3]; summary->min_permille = c->lca.permille; summary->reserved = 0; }
+	return lca_rollup(c, c->lca.d_direct, c->stream, out, cap, n);
+}
+
 // ---- the seam with the classify driver (dsb_gpu.hip) ----
 // the hit buffer's arguments of k_read_taxon, k_ref_cover and k_em_collect
 #define DSB_BATCH_HITS(b) (b).rout, (b).hout, (b).counters, (uint32_t)(b).cap_hout
@@ -695,6 +948,15 @@ int reductions_run(dsb_ctx *c, const DsbBatchView &b)
 		                   c->em.d_sets, c->em.d_elems, c->em.d_cnt, (uint64_t)c->em.used_sets, (uint64_t)c->em.used_elems, (uint64_t)c->em.cap_sets,
 		                   (uint64_t)c->em.cap_elems, (uint64_t)c->knobs.em_hash_mask);
 	}
+	if (c->lca.d_direct) {
+		// the per-read LCA records of the batch and, behind them, the run's counts: after the same launches, never in a graph
+		if (grow(&c->lca.d_rec, &c->lca.cap_rec, b.n)) return DSB_ENOMEM;
+		const dsb_taxonomy *tx = c->taxa.tx;
+		hipLaunchKernelGGL(k_read_lca, dim3((b.n + 3) / 4), dim3(256), 0, b.st, DSB_BATCH_HITS(b), b.n, (const uint32_t *)c->taxa.d_parent, (const uint16_t *)c->lca.d_depth,
+		                   (const uint32_t *)c->taxa.d_ref_tid, n_ref, tx->max_tid, tx->max_depth + 2, c->lca.permille, c->lca.d_rec);
+		hipLaunchKernelGGL(k_lca_count, dim3((b.n + 255) / 256), dim3(256), 0, b.st, (const dsb_read_lca *)c->lca.d_rec, b.n, tx->max_tid, c->lca.d_direct, c->lca.d_sum);
+		c->lca.run = true;
+	}
 	return DSB_OK;
 }
 
@@ -702,7 +964,10 @@ int reductions_fetch(dsb_ctx *c, size_t n, bool queued)
 {
 	c->taxa.done = false;
 	if (c->taxa.run) { c->taxa.h_taxa.resize(n); if (n) HIPCHK(hipMemcpyAsync(c->taxa.h_taxa.data(), c->taxa.d_taxa, n * sizeof(dsb_read_taxon), hipMemcpyDeviceToHost, c->stream)); }
-	if (queued || (c->taxa.run && n)) HIPCHK(hipStreamSynchronize(c->stream));
+	c->lca.done = false;
+	if (c->lca.run) { c->lca.h_rec.resize(n); if (n) HIPCHK(hipMemcpyAsync(c->lca.h_rec.data(), c->lca.d_rec, n * sizeof(dsb_read_lca), hipMemcpyDeviceToHost, c->stream)); }
+	if (queued || ((c->taxa.run || c->lca.run) && n)) HIPCHK(hipStreamSynchronize(c->stream));
+	c->lca.done = c->lca.run;
 	if (!c->taxa.run) return DSB_OK;
 	// the reads the device left to the host get their taxon here (rare: see k_read_taxon)
 	const dsb_hit *H = reinterpret_cast<const dsb_hit *>(c->h_hout.data());
@@ -716,7 +981,7 @@ int reductions_fetch(dsb_ctx *c, size_t n, bool queued)
 
 void reductions_release(dsb_ctx *c)
 {
-	hipFree(c->taxa.d_parent); hipFree(c->taxa.d_ref_tid); hipFree(c->taxa.d_taxa); cover_free(c); em_free(c);
+	hipFree(c->taxa.d_parent); hipFree(c->taxa.d_ref_tid); hipFree(c->taxa.d_taxa); cover_free(c); em_free(c); lca_free(c);
 }
 
 // ---- several contexts (dsb_multi) ----
@@ -737,6 +1002,7 @@ extern "C" int dsb_multi_set_taxonomy(dsb_multi *m, const dsb_taxonomy *tx)
 {
 	if (!m) return DSB_EINVAL;
 	m->tx = nullptr; m->taxa_ok = false;
+	m->lca_on = m->lca_ok = false;                              // (dsb_ctx_set_taxonomy turns each context's LCA off)
 	int rc = multi_enable(m, [&](dsb_ctx *c, bool on) { return dsb_ctx_set_taxonomy(c, on ? tx : nullptr); });
 	if (rc) return rc;
 	m->tx = tx;
@@ -850,4 +1116,56 @@ extern "C" int dsb_multi_abundance(dsb_multi *m, const dsb_em_opts *opts, dsb_re
 	}
 	EMCK(hipGetLastError());
 	return em_solve(st, m->idx, sets, elems, (uint32_t)S, (uint32_t)E, reads, c0->em.permille, o, out, summary);
+}
+
+extern "C" int dsb_multi_enable_lca(dsb_multi *m, int on, uint32_t min_permille)
+{
+	if (!m) return DSB_EINVAL;
+	m->lca_on = m->lca_ok = false;
+	int rc = multi_enable(m, [&](dsb_ctx *c, bool en) { return dsb_ctx_enable_lca(c, en ? on : 0, en ? min_permille : 0); });
+	if (rc) return rc;
+	m->lca_on = on != 0;
+	return DSB_OK;
+}
+extern "C" int dsb_multi_lca(dsb_multi *m, const dsb_read_lca **out)
+{
+	if (!m || !out || !m->lca_on || !m->lca_ok) return DSB_EINVAL;
+	*out = m->lca.data();
+	return DSB_OK;
+}
+
+// The contexts' direct tables added into a table on the first context's device -- copied over (copy_to) where a context sits on
+// another device -- then the roll-up of one context over the sum; the summary counters are added on the host.  The contexts' own
+// tables are left as they are.  Integer sums: what one context would have counted.
+extern "C" int dsb_multi_lca_counts(dsb_multi *m, dsb_taxon_count *out, size_t cap, size_t *n, dsb_lca_summary *summary)
+{
+	if (!m || !n || m->ctx.empty()) return DSB_EINVAL;
+	dsb_ctx *c0 = m->ctx[0];
+	for (dsb_ctx *c : m->ctx) if (!c->lca.d_direct || c->lca.permille != c0->lca.permille || c->taxa.tx != c0->taxa.tx) return DSB_EINVAL;
+	if (m->ctx.size() == 1) return dsb_ctx_lca_counts(c0, out, cap, n, summary);
+	unsigned long long tot[DSB_LCA_SUM] = {0, 0, 0, 0};
+	bool remote = false;
+	for (dsb_ctx *c : m->ctx) {
+		unsigned long long s[DSB_LCA_SUM];
+		if (int rc = lca_sums(c, s)) return rc;                // (waits for the context's stream: its table is final)
+		for (int k = 0; k < DSB_LCA_SUM; k++) tot[k] += s[k];
+		remote |= c->device != c0->device;
+	}
+	if (summary) { summary->reads = tot[0]; summary->classified = tot[1]; summary->no_taxon = tot[2]; summary->ambiguous = tot[3]; summary->min_permille = c0->lca.permille; summary->reserved = 0; }
+	HIPCHK(hipSetDevice(c0->device));
+	const size_t nt = (size_t)c0->taxa.tx->max_tid + 1;
+	const hipStream_t st = c0->stream;
+	DevScratch T;
+	unsigned long long *acc = T.get<unsigned long long>(nt), *buf = remote ? T.get<unsigned long long>(nt) : nullptr;
+	if (!acc || (remote && !buf)) return DSB_ENOMEM;
+	EMCK(copy_to(acc, c0->device, c0->lca.d_direct, c0->device, nt * 8, st));
+	const unsigned grid = (unsigned)std::min<size_t>((nt + 255) / 256, 8192);
+	for (size_t i = 1; i < m->ctx.size(); i++) {
+		const dsb_ctx *c = m->ctx[i];
+		const unsigned long long *src = c->lca.d_direct;
+		if (c->device != c0->device) { EMCK(copy_to(buf, c0->device, src, c->device, nt * 8, st)); src = buf; }
+		hipLaunchKernelGGL(k_lca_add, dim3(grid), dim3(256), 0, st, acc, src, (uint64_t)nt);
+	}
+	EMCK(hipGetLastError());
+	return lca_rollup(c0, acc, st, out, cap, n);
 }

@@ -21,6 +21,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <new>
 #include <string>
 #include <vector>
@@ -123,13 +124,28 @@ static int load(const char *path, bool check, dsb_taxonomy **out)
 			for (size_t k = path.size(); k-- > 0;) { depth[path[k]] = ++d; if ((uint32_t)d > T->max_depth) T->max_depth = (uint32_t)d; }
 		}
 		T->acyclic = true;
+		// the depth is kept for the rooted taxids: a chain that stops at taxid 1 (parent[1] = 0) counted its links to
+		// it; a chain that stopped anywhere else is unrooted, and so is every taxid above it.  Parents come before children here
+		// only along a chain, so rootedness is settled by a second pass in ascending depth order: a node is rooted when it is 1 or
+		// its parent is.
+		T->depth = (uint16_t *)malloc(((size_t)max_tid + 1) * 2);
+		if (!T->depth) { dsb_taxonomy_close(T); return DSB_ENOMEM; }
+		std::vector<std::vector<uint32_t>> by_depth((size_t)T->max_depth + 1);
+		for (uint32_t t = 1; t <= max_tid; t++) by_depth[(size_t)depth[t]].push_back(t);
+		T->depth[0] = DSB_DEPTH_UNROOTED;
+		for (uint32_t d = 0; d <= T->max_depth; d++)
+			for (uint32_t t : by_depth[d]) {
+				const uint32_t p = T->parent[t];
+				const bool rooted = d < DSB_DEPTH_UNROOTED && (t == 1 || (d > 0 && valid(p) && T->depth[p] != DSB_DEPTH_UNROOTED));
+				T->depth[t] = rooted ? (uint16_t)d : (uint16_t)DSB_DEPTH_UNROOTED;
+			}
 	}
 	*out = T;
 	return DSB_OK;
 }
 extern "C" int dsb_taxonomy_load(const char *path, dsb_taxonomy **tx) { return load(path, true, tx); }
 extern "C" int dsb_taxonomy_load_any(const char *path, dsb_taxonomy **tx) { return load(path, false, tx); }
-extern "C" void dsb_taxonomy_close(dsb_taxonomy *T) { if (T) { free(T->parent); free(T->rank); free(T); } }
+extern "C" void dsb_taxonomy_close(dsb_taxonomy *T) { if (T) { free(T->parent); free(T->rank); free(T->depth); free(T); } }
 extern "C" uint32_t dsb_taxonomy_max_tid(const dsb_taxonomy *T) { return T ? T->max_tid : 0; }
 extern "C" uint32_t dsb_taxonomy_parent(const dsb_taxonomy *T, uint32_t tid) { return (T && tid <= T->max_tid) ? T->parent[tid] : DSB_TID_NONE; }
 
@@ -390,4 +406,106 @@ extern "C" long dsb_abundance_format(const dsb_index *x, const dsb_ref_abundance
 	}
 #undef EMIT
 	return (long)o;
+}
+
+// ---- names.dmp, Kraken's per-read line and Kraken's report for the LCA classification ----
+extern "C" int dsb_taxnames_load(const char *path, dsb_taxnames **out)
+{
+	if (!path || !out) return DSB_EINVAL;
+	FILE *f = fopen(path, "r");
+	if (!f) return DSB_EIO;
+	dsb_taxnames *N = new dsb_taxnames;
+	std::vector<std::pair<uint32_t, std::string>> rows;
+	char *line = NULL; size_t m = 0;
+	while (getline(&line, &m, f) > 0) {
+		// taxid \t|\t name \t|\t unique name \t|\t name class \t|
+		std::string fld[4]; int k = 0;
+		for (const char *s = line; k < 4;) {
+			const char *e = strstr(s, "\t|");
+			if (!e) break;
+			fld[k++].assign(s, (size_t)(e - s));
+			s = e + 2; if (*s == '\t') s++;
+		}
+		if (k < 4 || fld[3] != "scientific name" || fld[0].empty()) continue;
+		rows.emplace_back((uint32_t)strtoul(fld[0].c_str(), NULL, 10), fld[1]);
+	}
+	free(line); fclose(f);
+	std::stable_sort(rows.begin(), rows.end(), [](const std::pair<uint32_t, std::string> &a, const std::pair<uint32_t, std::string> &b) { return a.first < b.first; });
+	for (const auto &r : rows) if (N->tid.empty() || N->tid.back() != r.first) { N->tid.push_back(r.first); N->name.push_back(r.second); }   // (the first of a taxid's lines)
+	*out = N;
+	return DSB_OK;
+}
+extern "C" void dsb_taxnames_close(dsb_taxnames *N) { delete N; }
+
+extern "C" long dsb_format_kraken(const dsb_read *rd, const dsb_read_lca *l, char *buf, size_t cap)
+{
+	if (!rd || !rd->name || !l || !buf) return -1;
+	const int w = snprintf(buf, cap, "%c\t%s\t%u\t%u\t%u:%u\n", l->taxid ? 'C' : 'U', rd->name, l->taxid, rd->len, l->score, l->n_pass);
+	return (w < 0 || (size_t)w >= cap) ? -1 : (long)w;
+}
+
+// the letter of a rank that has one in Kraken's report, else 0
+static char rank_letter(const char *r)
+{
+	static const struct { const char *rank; char c; } tab[] = {{"superkingdom", 'D'}, {"domain", 'D'}, {"kingdom", 'K'}, {"phylum", 'P'}, {"class", 'C'},
+	                                                           {"order", 'O'}, {"family", 'F'}, {"genus", 'G'}, {"species", 'S'}};
+	for (const auto &e : tab) if (!strcmp(r, e.rank)) return e.c;
+	return 0;
+}
+
+extern "C" long dsb_lca_report_format(const dsb_taxonomy *T, const dsb_taxnames *names, const dsb_taxon_count *rows, size_t n, const dsb_lca_summary *sum,
+                                      char *buf, size_t cap)
+{
+	if (!T || !sum || (!rows && n) || !buf) return -1;
+	std::string o;
+	if (sum->reads) {
+		const double reads = (double)sum->reads;
+		if (sum->reads > sum->classified) {
+			const unsigned long long u = sum->reads - sum->classified;
+			put(o, "%6.2f\t%llu\t%llu\tU\t0\tunclassified\n", 100.0 * (double)u / reads, u, u);
+		}
+		// the rows by taxid (they come ascending from dsb_ctx_lca_counts; hand-filled ones need not), the children of each
+		std::vector<uint32_t> by(n);
+		for (size_t i = 0; i < n; i++) by[i] = (uint32_t)i;
+		std::sort(by.begin(), by.end(), [&](uint32_t a, uint32_t b) { return rows[a].taxid < rows[b].taxid; });
+		auto find = [&](uint32_t tid) -> long {
+			size_t lo = 0, hi = n;
+			while (lo < hi) { const size_t mid = (lo + hi) / 2; if (rows[by[mid]].taxid < tid) lo = mid + 1; else hi = mid; }
+			return lo < n && rows[by[lo]].taxid == tid ? (long)lo : -1;
+		};
+		std::vector<std::vector<uint32_t>> kids(n);              // (positions in `by`)
+		for (size_t k = 0; k < n; k++) {
+			const dsb_taxon_count &r = rows[by[k]];
+			if (!r.clade_reads || r.taxid <= 1 || r.taxid > T->max_tid) continue;
+			const long p = find(T->parent[r.taxid]);
+			if (p >= 0) kids[(size_t)p].push_back((uint32_t)k);
+		}
+		for (auto &v : kids)
+			std::sort(v.begin(), v.end(), [&](uint32_t a, uint32_t b) {
+				const dsb_taxon_count &x = rows[by[a]], &y = rows[by[b]];
+				return x.clade_reads != y.clade_reads ? x.clade_reads > y.clade_reads : x.taxid < y.taxid;
+			});
+		struct Frame { uint32_t k, depth, num; char letter; };
+		std::vector<Frame> st;
+		const long root = find(1);
+		if (root >= 0 && rows[by[(size_t)root]].clade_reads) st.push_back(Frame{(uint32_t)root, 0, 0, 'R'});
+		while (!st.empty()) {
+			const Frame f = st.back(); st.pop_back();
+			const dsb_taxon_count &r = rows[by[f.k]];
+			put(o, "%6.2f\t%llu\t%llu\t%c", 100.0 * (double)r.clade_reads / reads, (unsigned long long)r.clade_reads, (unsigned long long)r.direct_reads, f.letter);
+			if (f.num) put(o, "%u", f.num);
+			put(o, "\t%u\t%*s", r.taxid, (int)(2 * f.depth), "");
+			const std::string *nm = nullptr;
+			if (names) { auto it = std::lower_bound(names->tid.begin(), names->tid.end(), r.taxid); if (it != names->tid.end() && *it == r.taxid) nm = &names->name[(size_t)(it - names->tid.begin())]; }
+			if (nm) { o += *nm; o += '\n'; } else put(o, "%u\n", r.taxid);
+			const std::vector<uint32_t> &v = kids[f.k];
+			for (size_t j = v.size(); j-- > 0;) {                   // (pushed in reverse: the first child is printed first)
+				const char c = rank_letter(T->rank[rows[by[v[j]]].taxid]);
+				st.push_back(c ? Frame{v[j], f.depth + 1, 0, c} : Frame{v[j], f.depth + 1, f.num + 1, f.letter});
+			}
+		}
+	}
+	if (o.size() >= cap) return -1;
+	memcpy(buf, o.data(), o.size()); buf[o.size()] = 0;
+	return (long)o.size();
 }

@@ -345,6 +345,51 @@ int  dsb_multi_abundance(dsb_multi *m, const dsb_em_opts *opts, dsb_ref_abundanc
  * formats).  Same return convention as dsb_format_sam. */
 long dsb_abundance_format(const dsb_index *idx, const dsb_ref_abundance *ab, const dsb_abundance_summary *summary, char *buf, size_t cap);
 
+/* ---- per-read classification by the lowest common ancestor (LCA) of the near-best hits, on the GPU.
+ * Per read (reads are not joined by name): its hits are those dsb_batch_fetch hands out, whatever max_sec_N is; hits with
+ * ref_ID >= n_ref are skipped, and a read with no hit left is unclassified (record all zero).  S_max is the largest AS; a hit
+ * passes when AS * 1000 >= S_max * min_permille (64-bit); n_pass counts passing hits, not references.  A taxid is rooted when it
+ * lies in 1 .. max_tid and its parent links reach taxid 1; depth = links to taxid 1.  A passing hit whose reference's taxid (the
+ * second '|' field of its name) is not rooted is left out.  taxid = the deepest node that is an ancestor-or-self of every
+ * remaining passing hit's taxid; none remaining: taxid 0 and DSB_LCA_NO_TAXON; more than one distinct taxid among them:
+ * DSB_LCA_AMBIGUOUS.  The result does not depend on hit order, duplicates, batch split, input slot or context. */
+typedef struct { uint32_t taxid, score, n_pass; uint16_t depth; uint8_t flags, pad; } dsb_read_lca;   /* score = S_max */
+#define DSB_LCA_CLASSIFIED 1   /* the read has hits */
+#define DSB_LCA_NO_TAXON   2   /* ... but no passing hit with a rooted taxid: taxid 0 */
+#define DSB_LCA_AMBIGUOUS  4   /* passing hits of more than one taxid */
+/* run-wide: direct_reads = reads whose taxid is this one, clade_reads = the same summed over the taxon and its descendants */
+typedef struct { uint32_t taxid, pad; uint64_t clade_reads, direct_reads; } dsb_taxon_count;
+typedef struct { uint64_t reads, classified /* taxid != 0 */, no_taxon, ambiguous; uint32_t min_permille, reserved; } dsb_lca_summary;
+/* on: every batch from now on ends with k_read_lca and k_lca_count (a depth table beside the parent table, one u64 per taxid for
+ * the run's counts); needs a taxonomy from dsb_taxonomy_load attached (dsb_ctx_set_taxonomy), else DSB_EINVAL; min_permille outside
+ * 1 .. 1000: DSB_EINVAL.  On again: new threshold, counts zeroed.  off: freed; nothing is allocated or launched while off.
+ * dsb_ctx_set_taxonomy on a ctx whose LCA is on turns it off. */
+int  dsb_ctx_enable_lca(dsb_ctx *ctx, int on, uint32_t min_permille);
+int  dsb_ctx_reset_lca(dsb_ctx *ctx);                          /* zero the counts, keep the allocation */
+int  dsb_batch_lca(dsb_ctx *ctx, const dsb_read_lca **out);    /* the records of the last batch (n reads), valid until the next */
+/* everything since enable / reset (fetching changes nothing): the taxa with clade_reads > 0 in ascending taxid, rolled up on the
+ * device; only these rows are copied.  *n = the number of rows; out gets the first min(cap, *n) of them (out NULL: count only);
+ * DSB_ECAP when out is given and cap < *n.  summary may be NULL. */
+int  dsb_ctx_lca_counts(dsb_ctx *ctx, dsb_taxon_count *out, size_t cap, size_t *n, dsb_lca_summary *summary);
+int  dsb_multi_enable_lca(dsb_multi *m, int on, uint32_t min_permille);
+int  dsb_multi_lca(dsb_multi *m, const dsb_read_lca **out);    /* the last dsb_multi_classify_batch, in input order */
+/* the contexts' counts added on the first context's device, then the same roll-up: what one context would give */
+int  dsb_multi_lca_counts(dsb_multi *m, dsb_taxon_count *out, size_t cap, size_t *n, dsb_lca_summary *summary);
+typedef struct dsb_taxnames dsb_taxnames;                       /* names.dmp: the "scientific name" of each taxid */
+int  dsb_taxnames_load(const char *names_dmp, dsb_taxnames **names);   /* DSB_EIO: cannot be read */
+void dsb_taxnames_close(dsb_taxnames *names);
+/* Kraken's per-read line: C|U \t QNAME \t taxid \t read length \t S_max:n_pass \n -- C iff taxid != 0, QNAME as dsb_format_sam
+ * prints it; columns 1 to 4 are Kraken's, column 5 stands where Kraken puts its k-mer string.  Return as dsb_format_sam. */
+long dsb_format_kraken(const dsb_read *read, const dsb_read_lca *lca, char *buf, size_t cap);
+/* Kraken's report (`kraken2 --report`) of the rows of dsb_*_lca_counts: a line for the reads - classified unclassified reads (code
+ * U, taxid 0) when there are any, then the tree from taxid 1 depth first, children by clade_reads descending then taxid
+ * ascending; each line  %6.2f \t clade \t direct \t code \t taxid \t  + two spaces per depth + name (names NULL or without the
+ * taxid: the decimal taxid).  Code: R for taxid 1, D K P C O F G S for superkingdom / domain, kingdom, phylum, class, order, family,
+ * genus, species; any other rank takes its parent's letter and the parent's number plus one (S, S1, S2; R1 under the root).
+ * Zero reads: empty.  Return as dsb_format_sam. */
+long dsb_lca_report_format(const dsb_taxonomy *tx, const dsb_taxnames *names, const dsb_taxon_count *rows, size_t n,
+                           const dsb_lca_summary *summary, char *buf, size_t cap);
+
 const char *dsb_strerror(int code);
 const char *dsb_version(void);
 
