@@ -2890,11 +2890,11 @@ DN int sdp_middle_M2(WCtxL &w, int32_t c_a, const uint8_t *q_str, int tbl, int k
 			const int n_mch = (int)n.pl, n_tlen = (int)(n.ct - ((n.pt - 3) + (uint32_t)n_mch) + 3);
 			if (n_tlen > 12 && n_tlen < 2000) {
 				const uint64_t n_toff = (uint64_t)(int64_t)(int)(n.pt - 3) + t_offset + (uint64_t)(int64_t)n_mch;
-				const int32_t n_qlo = (int32_t)(n.pq + (uint32_t)n_mch - 8) - 16, n_qhi = (int32_t)(n.cq - 1) + 80;
+				const int32_t n_qlo = (int32_t)(n.pq + (uint32_t)n_mch - 8) - 16, n_qhi = (int32_t)(n.cq - 1) + MAXV(80, n_tlen + 4);   // (as q_hi below)
 				if ((int64_t)n_toff >= 0 && n_toff < x->ref_bases && 8 * lane < n_tlen) pf_t = dsb_g32u(x->refbin + ((n_toff + (uint32_t)(8 * lane)) >> 2));
 				pf_toff = n_toff; pf_has_t = (int64_t)n_toff >= 0 && n_toff < x->ref_bases;
 				if (n_qhi > n_qlo && n_qlo >= -(int32_t)DSB_QPAD_L + 8) {
-					if (8 * lane < ((n_qhi - n_qlo + 7) & ~7)) pf_q = ld_u64(q_str + n_qlo + 8 * lane);
+					if (8 * lane < ((n_qhi - n_qlo + 7) & ~7)) pf_q = ld_u64(q_str + MINV(n_qlo + 8 * lane, (int32_t)((w.bin + 2 * (size_t)L + DSB_QPAD_R) - q_str) - 8));
 					pf_qlo = n_qlo; pf_has_q = true;
 				}
 			}
@@ -2915,16 +2915,20 @@ DN int sdp_middle_M2(WCtxL &w, int32_t c_a, const uint8_t *q_str, int tbl, int k
 			const uint8_t *qs = q_str; const uint8_t *lq_st = nullptr;
 			// Small gap (the usual case): the reference window and the stretch of the read the match can touch live
 			// in LDS behind the window's hash table, so the k-mer builds and exact-match extensions of sdp_match
-			// are LDS reads instead of global round trips.  Forward matching reads q in [q_bg - 8, q_ed + 66].
+			// are LDS reads instead of global round trips.  Forward matching reads q in [q_bg - 8, q_ed + 66] -- except from
+			// q_pos == q_ed, where the reference's unsigned `q_ed - q_pos - 1` wraps and only the end of the window stops the
+			// extension: it then reads up to q_ed + t_len + 3 (a tandem repeat that runs from the gap into the anchor behind it).
 			const uint32_t n_q = sdp_nq(L, q_bg, q_ed), slots = wtab_size(n_q);
-			const int32_t q_lo = (int32_t)q_bg - 16, q_hi = (int32_t)q_ed + 80;
+			const int32_t q_lo = (int32_t)q_bg - 16, q_hi = (int32_t)q_ed + MAXV(80, total_ref_len + 4);
 			const uint32_t q_bytes = q_hi > q_lo ? (uint32_t)(q_hi - q_lo + 7) & ~7u : 0u, t_bytes = ((uint32_t)total_ref_len + 64 + 7) & ~7u;
 			const uint32_t tbase = w.pk[tbl] ? MAXV(slots, (DSB_INV_WORDS + 3u) & ~3u) : slots;   // words of the window's table, whichever way round it is built
 			if (n_q > 0 && q_bytes && q_lo >= -(int32_t)DSB_QPAD_L + 8 && 4 * tbase + q_bytes + 8 + t_bytes + 8 + 1024 <= 4 * DSB_WTAB_SLOTS) {
 				uint8_t *lq = reinterpret_cast<uint8_t *>(wtab + tbase), *lt = lq + q_bytes + 8;
 				lnodes = reinterpret_cast<uint4 *>(lt + t_bytes + (((4 * tbase + q_bytes + t_bytes) & 8u) ? 0 : 8));   // 16-byte aligned: the table starts 16-aligned
 				const bool use_pf = cur_has_q && cur_qlo == q_lo;
-				for (uint32_t k = 8 * lane; k < q_bytes; k += 8 * DSB_WAVE) *reinterpret_cast<uint64_t *>(lq + k) = (use_pf && k < 8 * DSB_WAVE) ? cur_q : ld_u64(q_str + q_lo + (int32_t)k);
+				// (a long window at the end of the reverse strand: what would lie behind the strand's pad is read as pad -- neither matches anything)
+				const int32_t q_last = (int32_t)((w.bin + 2 * (size_t)L + DSB_QPAD_R) - q_str) - 8;
+				for (uint32_t k = 8 * lane; k < q_bytes; k += 8 * DSB_WAVE) *reinterpret_cast<uint64_t *>(lq + k) = (use_pf && k < 8 * DSB_WAVE) ? cur_q : ld_u64(q_str + MINV(q_lo + (int32_t)k, q_last));
 				ref = lt; qs = nullptr; lq_st = lq;
 			}
 			if (cur_has_t && cur_toff == ref_offset) get_ref_wave_pf(x->refbin, lane, ref, (int64_t)ref_offset, total_ref_len, cur_t);

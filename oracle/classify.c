@@ -61,6 +61,7 @@ struct ora_ctx {
 	sdir_t sd[2]; uint32_t read_len;
 	uint64_t cnt[8];      /* P0,P1,OCC,SA,RW,MEMS */
 	uint64_t ref_bases;   /* bases of the 2-bit reference text (U6) */
+	uint32_t *gap_nodes; uint32_t n_gap_nodes;   /* ora_gap_stage: match nodes sdp_match produced per gap of sdp_middle_M2 (null: not recorded) */
 	void *sort_tmp; size_t m_sort_tmp;
 };
 
@@ -919,6 +920,7 @@ static int sdp_middle_M2(ora_ctx_t *cx, const ora_idx_t *x, int32_t c_a, const u
 				sdp_match(cx, A[pre_a].index_in_read + pre_mch - 8, A[c_a].index_in_read - 1, q_str, ref, total_ref_len, key_len, sa_hash,
 				          pre_refoffset + pre_mch, true);
 			}
+			if (cx->gap_nodes) cx->gap_nodes[cx->n_gap_nodes++] = cx->n_sms - 1;   /* (stage report only) */
 			p = push_sms(cx);
 			p->q_pos = A[c_a].index_in_read; p->t_pos = A[c_a].ref_offset; p->len = A[c_a].a_m.mtch_len - 9 + 1;
 			if (cx->n_sms > 1) {
@@ -950,6 +952,67 @@ static int sdp_middle_M2(ora_ctx_t *cx, const ora_idx_t *x, int32_t c_a, const u
 		c_a = pre_a;
 	}
 	return score - 10000;
+}
+
+/* ---- a-12 on its own (tests/test_stage_sdp.py) ------------------------------------------ */
+/* the read laid out as get_island lays it out (U1), one chain of the given strand so that build_hash_table_M2 hashes that strand */
+static const uint8_t *stage_read(ora_ctx_t *c, const char *seq, uint32_t L, int strand)
+{
+	uint32_t need = QPAD_L + 2 * L + QPAD_R;
+	if (need > c->m_bin) { c->m_bin = need + 64; c->bin_base = realloc(c->bin_base, c->m_bin); }
+	memset(c->bin_base, 0, QPAD_L);
+	c->bin_read = c->bin_base + QPAD_L;
+	memset(c->bin_read + 2 * L, QPAD_R_VAL, QPAD_R);
+	uint8_t *F = c->bin_read, *R = c->bin_read + L;
+	for (uint32_t k = 0; k < L; ++k) F[k] = cly_bit((unsigned char)seq[k]);
+	for (uint32_t k = 0; k < L; ++k) R[L - k - 1] = 3 - F[k];
+	memset(c->sd, 0, sizeof c->sd);
+	c->sd[0].bin_read = F; c->sd[0].direction = FORWARD; c->sd[1].bin_read = R; c->sd[1].direction = REVERSE;
+	c->n_hit = 0; c->read_len = L;
+	push_hit(c)->direction = (uint8_t)strand;
+	return strand == FORWARD ? F : R;
+}
+/* sdp_match on one window.  t_str points into a buffer that holds what the caller of sdp_match has around the window: at least
+ * 64 readable bytes in front of it (for the backward form the 50 bases the left extension fetches before t_str are the last of
+ * them), and behind t_len whatever the caller loaded there followed by TPAD_VAL, 128 bytes in all.  -> number of nodes;
+ * out[3 i ..] = t_pos, q_pos, len of node i, in order (the first max_out of them) */
+int ora_sdp_match_stage(ora_ctx_t *c, const char *seq, uint32_t L, int strand, uint32_t q_bg, uint32_t q_ed,
+                        const uint8_t *t_str, uint32_t t_len, uint32_t t_st, int is_forward, uint32_t *out, int max_out)
+{
+	const uint8_t *q_str = stage_read(c, seq, L, strand);
+	int key_len = build_hash_table_M2(c, c->sd, (int)L);
+	const sah_t *h = (strand == FORWARD) ? c->sa_hash[0] : c->sa_hash[1];
+	c->n_sms = 0;
+	sdp_match(c, q_bg, q_ed, q_str, t_str, t_len, key_len, h, t_st, is_forward != 0);
+	for (uint32_t i = 0; i < c->n_sms && (int)i < max_out; i++) { out[3 * i] = c->sms[i].t_pos; out[3 * i + 1] = c->sms[i].q_pos; out[3 * i + 2] = c->sms[i].len; }
+	int n = (int)c->n_sms;
+	c->n_sms = 0; c->n_hit = 0;
+	return n;
+}
+/* sdp_middle_M2 on one chain over a synthetic reference text (2-bit packed as the index holds it, followed by its 4 KiB of zeros:
+ * U3; one reference, seq_offset 0).  anchors: rows of 4 (index_in_read, ref_offset, mtch_len, pre); c_a: the chain's last anchor.
+ * -> the score; gap_nodes[k] = match nodes sdp_match produced in the k-th gap of the walk (from the last anchor backwards) */
+int ora_gap_stage(ora_ctx_t *c, const char *seq, uint32_t L, int strand, const uint8_t *refbin, uint64_t ref_bases,
+                  const int32_t *anchors, uint32_t n_anchors, int32_t c_a, uint32_t *gap_nodes, uint32_t *n_gaps)
+{
+	static ora_idx_t x; ora_refinfo_t r0; memset(&r0, 0, sizeof r0);
+	r0.seq_l = ref_bases; r0.seq_offset = 0;
+	x.refbin = (uint8_t *)refbin; x.n_refbin = (ref_bases + 3) / 4; x.ref = &r0; x.n_ref = 1;
+	const uint8_t *q_str = stage_read(c, seq, L, strand);
+	c->ref_bases = ref_bases;
+	c->n_anc = 0;
+	for (uint32_t i = 0; i < n_anchors; i++) {
+		anchor_t *a = push_anchor(c);
+		a->index_in_read = (uint32_t)anchors[4 * i]; a->ref_offset = (uint32_t)anchors[4 * i + 1]; a->a_m.mtch_len = (uint16_t)anchors[4 * i + 2]; a->pre = anchors[4 * i + 3];
+		a->ref_ID = 0; a->direction = (uint8_t)strand;
+	}
+	int key_len = build_hash_table_M2(c, c->sd, (int)L);
+	const sah_t *h = (strand == FORWARD) ? c->sa_hash[0] : c->sa_hash[1];
+	c->gap_nodes = gap_nodes; c->n_gap_nodes = 0;
+	int score = sdp_middle_M2(c, &x, c_a, q_str, h, key_len);
+	if (n_gaps) *n_gaps = c->n_gap_nodes;
+	c->gap_nodes = NULL; c->n_sms = 0; c->n_anc = 0; c->n_hit = 0;
+	return score;
 }
 
 /* sdp_right_M2, src/cly.c:2532-2677 */

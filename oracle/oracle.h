@@ -99,6 +99,11 @@ uint64_t ora_occ(const ora_idx_t *idx, uint64_t r, uint8_t *c);
 int32_t ora_lv_extd(const uint8_t *ref_padded, int32_t ref_length, const uint8_t *query_padded, int32_t query_length);
 /* a-11 on its own (tests/test_stage_combine_chain.py) */
 void ora_combine_stage(uint32_t *chains, uint32_t n, const int32_t *queries, uint32_t n_q, int32_t *out);
+/* a-12 on its own (tests/test_stage_sdp.py): sdp_match on one window, sdp_middle_M2 on one chain over a synthetic text (oracle/classify.c) */
+int ora_sdp_match_stage(ora_ctx_t *c, const char *seq, uint32_t len, int strand, uint32_t q_bg, uint32_t q_ed,
+                        const uint8_t *t_str, uint32_t t_len, uint32_t t_st, int is_forward, uint32_t *out, int max_out);
+int ora_gap_stage(ora_ctx_t *c, const char *seq, uint32_t len, int strand, const uint8_t *refbin, uint64_t ref_bases,
+                  const int32_t *anchors, uint32_t n_anchors, int32_t c_a, uint32_t *gap_nodes, uint32_t *n_gaps);
 #ifdef __cplusplus
 }
 #endif

@@ -297,3 +297,99 @@ extern "C" void emu_steps(void *p, uint32_t out[2]) { out[0] = ((EmuCtx *)p)->w.
 extern "C" void emu_counters(void *p, uint32_t out[4]) { memcpy(out, ((EmuCtx *)p)->cnt, 16); }
 // cly_r.anchor_v.n when classify_seq returned (printed by the DES writers)
 extern "C" uint32_t emu_n_anc(void *p) { return ((EmuCtx *)p)->w.n_anc; }
+
+// ---- stage a-12 form by form (tests/stage/dsb_stage_forms.h, tests/test_stage_sdp.py): sdp_match as wtab_build + sdp_match_t,
+// wtab_build_pk + sdp_match_t, sdp_match_inv, the dispatcher, sdp_match_lds; gap_lane; sdp_middle_M2.  The context is the one
+// classify_kernel_body sets up, on host memory; no index directory is involved.
+#include "../stage/dsb_stage_forms.h"
+struct StageHost {
+	alignas(16) uint32_t wtab[DSB_WTAB_SLOTS]; uint4 ring[DSB_RING]; uint32_t red[4], cnt[4]; DsbDevIndex sx; WCtx w; DsbRefInfo ri; DpBatch dpb;
+	std::vector<uint8_t> slice;
+};
+static StageHost *stage_host()
+{
+	static StageHost *h = nullptr;
+	if (!h) { h = new StageHost(); h->slice.assign(STAGE_SLICE, 0xCD); }
+	memset(&h->sx, 0, sizeof h->sx); memset(&h->w, 0, sizeof h->w); memset(h->cnt, 0, sizeof h->cnt);
+	h->ri.seq_l = ~0ULL; h->ri.seq_offset = 0; h->w.dpb = &h->dpb;
+	return h;
+}
+struct StageJob {
+	StageHost *h; int what, form; StageSdp *sc; StageChain *cc; const uint8_t *bin; const uint64_t *pk; const uint8_t *aux; DsbSms *nodes; uint4 *mirror; DsbGap *G; const int32_t *anchors;
+};
+static void stage_lane(void *p)
+{
+	StageJob *j = (StageJob *)p; StageHost *h = j->h;
+	stage_ctx(h->w, &h->sx, h->slice.data(), h->wtab, h->ring, h->red, h->cnt, &h->ri);
+	if (j->what == 0) stage_sdp(h->w, &h->sx, j->form, j->sc, j->bin, j->pk, j->aux, j->nodes, j->mirror);
+	else if (j->what == 1) stage_gap_lane(h->w, &h->sx, j->cc, j->bin, j->pk, j->aux, j->G);
+	else stage_middle(h->w, &h->sx, j->cc, j->bin, j->pk, j->aux, j->anchors);
+}
+static void stage_run(StageJob &j)
+{
+#if DSB_EMU_LANES == 64
+	dsb_emu_run(stage_lane, &j);
+#else
+	stage_lane(&j);
+#endif
+}
+static void stage_regions(StageJob &j, const void *cases, size_t case_bytes, size_t bin_bytes, size_t pk_words, size_t aux_bytes)
+{
+#if DSB_EMU_LANES == 64
+	StageHost *h = j.h;
+	dsb_emu_regions_clear();
+	dsb_emu_region(&j, sizeof j, "job"); dsb_emu_region(&h->slice, sizeof h->slice, "slice handle"); dsb_emu_region(h->wtab, sizeof h->wtab, "LDS window table"); dsb_emu_region(h->ring, sizeof h->ring, "LDS ring");
+	dsb_emu_region(h->red, sizeof h->red, "LDS red"); dsb_emu_region(h->cnt, sizeof h->cnt, "LDS counters"); dsb_emu_region(&h->sx, sizeof h->sx, "index descriptor");
+	dsb_emu_region(&h->w, sizeof h->w, "context"); dsb_emu_region(&h->ri, sizeof h->ri, "reference info"); dsb_emu_region(&h->dpb, sizeof h->dpb, "LDS DP batch");
+	dsb_emu_region(h->slice.data() + STAGE_OFF_SORTKEY, 16384, "sort keys"); dsb_emu_region(h->slice.data() + STAGE_OFF_SORTIDX, 4096, "sort indices");
+	dsb_emu_region(h->slice.data() + STAGE_OFF_ANC, 16384, "anchors"); dsb_emu_region(h->slice.data() + STAGE_OFF_ANC_TMP, 16384, "anchors (copy)");
+	dsb_emu_region(h->slice.data() + STAGE_OFF_WIN, 6656, "reference windows"); dsb_emu_region(h->slice.data() + STAGE_OFF_SMS, STAGE_CHAIN_SMS * 16, "match nodes");
+	dsb_emu_region(cases, case_bytes, "cases"); dsb_emu_region(j.bin, bin_bytes, "byte strands"); dsb_emu_region(j.pk, 8 * pk_words, "packed strands");
+	dsb_emu_region(j.aux, aux_bytes, j.what == 0 ? "window bytes" : "reference text");
+#else
+	(void)j; (void)cases; (void)case_bytes; (void)bin_bytes; (void)pk_words; (void)aux_bytes;
+#endif
+}
+extern "C" uint32_t emu_stage_sizes(uint32_t *out)
+{
+	out[0] = sizeof(StageSdp); out[1] = sizeof(StageChain); out[2] = sizeof(DsbGap); out[3] = DSB_WTAB_SLOTS; out[4] = DSB_WTAB_MAXQ; out[5] = DSB_INV_PAIRS; out[6] = DSB_INV_MINQ; out[7] = DSB_INV_MAXPOS;
+	out[8] = DSB_SDP_CAND; out[9] = DSB_SDP_KEEP; out[10] = DSB_GL_QW; out[11] = DSB_GL_NODES; out[12] = DSB_GL_MAXT; out[13] = DSB_INV_WORDS; out[14] = DSB_EMU_LANES; out[15] = STAGE_MAX_ANC;
+	return 16;
+}
+extern "C" int emu_stage_sdp(int form, StageSdp *cases, uint32_t n, const uint8_t *bin, size_t bin_bytes, const uint64_t *pk, size_t pk_words, const uint8_t *win, size_t win_bytes,
+                             DsbSms *nodes, size_t node_entries, uint4 *mirror)
+{
+	StageJob j; memset(&j, 0, sizeof j); j.h = stage_host(); j.what = 0; j.form = form; j.bin = bin; j.pk = pk; j.aux = win; j.nodes = nodes;
+	stage_regions(j, cases, (size_t)n * sizeof(StageSdp), bin_bytes, pk_words, win_bytes);
+#if DSB_EMU_LANES == 64
+	dsb_emu_region(nodes, node_entries * sizeof(DsbSms), "node lists"); dsb_emu_region(mirror, (size_t)n * 64 * sizeof(uint4), "node mirrors");
+#else
+	(void)node_entries;
+#endif
+	for (uint32_t k = 0; k < n; k++) { j.sc = cases + k; j.mirror = mirror + 64 * (size_t)k; stage_run(j); }
+	return 0;
+}
+extern "C" int emu_stage_gap_lane(StageChain *cases, uint32_t n, const uint8_t *bin, size_t bin_bytes, const uint64_t *pk, size_t pk_words, const uint8_t *ref, size_t ref_bytes, DsbGap *G, size_t n_gaps)
+{
+	StageJob j; memset(&j, 0, sizeof j); j.h = stage_host(); j.what = 1; j.bin = bin; j.pk = pk; j.aux = ref; j.G = G;
+	stage_regions(j, cases, (size_t)n * sizeof(StageChain), bin_bytes, pk_words, ref_bytes);
+#if DSB_EMU_LANES == 64
+	dsb_emu_region(G, n_gaps * sizeof(DsbGap), "gaps");
+#else
+	(void)n_gaps;
+#endif
+	for (uint32_t k = 0; k < n; k++) { j.cc = cases + k; stage_run(j); }
+	return 0;
+}
+extern "C" int emu_stage_middle(StageChain *cases, uint32_t n, const uint8_t *bin, size_t bin_bytes, const uint64_t *pk, size_t pk_words, const uint8_t *ref, size_t ref_bytes, const int32_t *anchors, size_t n_rows)
+{
+	StageJob j; memset(&j, 0, sizeof j); j.h = stage_host(); j.what = 2; j.bin = bin; j.pk = pk; j.aux = ref; j.anchors = anchors;
+	stage_regions(j, cases, (size_t)n * sizeof(StageChain), bin_bytes, pk_words, ref_bytes);
+#if DSB_EMU_LANES == 64
+	dsb_emu_region(anchors, n_rows * 16, "anchor rows");
+#else
+	(void)n_rows;
+#endif
+	for (uint32_t k = 0; k < n; k++) { j.cc = cases + k; stage_run(j); }
+	return 0;
+}
