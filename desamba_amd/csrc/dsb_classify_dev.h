@@ -1133,10 +1133,13 @@ DN uint32_t *stable_sort_keys(WCtxL &w, uint32_t n)
 
 // chain_insert_M3 (src/cly.c:238-323): stable sort by (ref_ID, direction, ref_offset), then sparse DP per group
 #define DSB_RANKSORT_MAX (DSB_WTAB_SLOTS / 4)            /* 8-byte keys in the window table's LDS, at most half of it */
+// (FORCE: the stage test of tests/stage takes one path whatever n is -- 1 rank with distinct keys, n <= 1024 and reference numbers
+// below 2^21; 2 rank with the tie rule, n <= DSB_WTAB_SLOTS / 2; 3 merge.  0, the product: the path follows from n and the anchors.)
+template <int FORCE = 0>
 DN void chain_sort_M3(WCtxL &w)
 {
 	DsbAnchor *A = w.anc, *T = w.anc_tmp; const int32_t n = w.n_anc; const int lane = DSB_LANE;
-	if (n <= DSB_RANKSORT_MAX && w.wtab) {
+	if (FORCE ? FORCE != 3 : (n <= DSB_RANKSORT_MAX && w.wtab)) {
 		// the usual size: keys in LDS (the window table is idle), every lane ranks its own anchors against all keys
 		// (stable: ties by index) and moves them straight to their sorted place; the two anchor arrays swap roles
 		lds_u64 *keys = (lds_u64 *)w.wtab;
@@ -1144,7 +1147,7 @@ DN void chain_sort_M3(WCtxL &w)
 		for (int32_t i = lane; i < n; i += DSB_WAVE) { keys[i] = ((uint64_t)A[i].ref_ID << 33) | ((uint64_t)A[i].direction << 32) | A[i].ref_offset; max_ref = MAXV(max_ref, A[i].ref_ID); }
 		max_ref = (uint32_t)grp_max_i((int)max_ref);
 		wave_sync();
-		if (max_ref < (1u << 21) && n <= 1024) {
+		if (FORCE ? FORCE == 1 : (max_ref < (1u << 21) && n <= 1024)) {
 			// reference numbers below 2^21 (any index but a collection of millions of sequences): the anchor's index fits under the key, the keys
 			// become distinct, and a rank is a count of smaller keys -- one compare per key instead of the three of "smaller, or equal and earlier"
 			for (int32_t i = lane; i < n; i += DSB_WAVE) { const uint64_t k = keys[i]; keys[i] = ((k >> 32) << 42) | ((k & 0xffffffffULL) << 10) | (uint64_t)(uint32_t)i; }
@@ -1192,7 +1195,7 @@ DN void chain_sort_M3(WCtxL &w)
 // ... and the DP.  The usual size (n <= DSB_CHAINDP_LDS anchors) runs on the whole wavefront from six 4-byte arrays
 // staged in the window table's LDS -- q, t, mtch_len | score << 16, key (ref_ID << 3 | direction << 2 | useless << 1 |
 // duplicate), then the DP's score and predecessor -- with the lanes over the predecessors of one anchor at a time
-// (chain_dp_M3_wave); larger sets take the serial form on lane 0 from global memory (chain_dp_M3<false>).
+// (chain_dp_M3_wave); without a window table the serial form on lane 0 runs from global memory (chain_dp_M3).
 #define DSB_CHAINDP_LDS (DSB_WTAB_SLOTS / 6)              /* 512 */
 // (P32: lds_w32 * for the arrays in LDS, uint32_t * for larger anchor sets whose arrays lie in the idle half of the
 // anchor arena -- global memory, same code, the loads of a chunk of predecessors are coalesced; C = array stride)
@@ -1324,15 +1327,14 @@ DN void chain_dp_M3_wave(WCtxL &w, P32 LQ, const uint32_t C)
 	if (n_grp > room) w.status |= DSB_ST_HIT_OVF;               // (a read whose chains do not fit is run again with a larger arena)
 	wave_sync();
 }
-template <bool LDSMODE>
+// the reference's own loop on lane 0, from global memory (no window table: chain_dp_M3_wave has no room for its arrays)
 DN void chain_dp_M3(WCtxL &w)
 {
 	DsbAnchor *A = w.anc; int32_t n = w.n_anc;
 	int *score_v = w.score_v;
-	lds_w32 *LQ = (lds_w32 *)w.wtab, *LT = LQ + DSB_CHAINDP_LDS, *LM = LQ + 2 * DSB_CHAINDP_LDS, *LS = LQ + 3 * DSB_CHAINDP_LDS, *LP = LQ + 4 * DSB_CHAINDP_LDS;
-#define AQ(i) (LDSMODE ? (uint32_t)LQ[i] : A[i].index_in_read)
-#define AT(i) (LDSMODE ? (uint32_t)LT[i] : A[i].ref_offset)
-#define AM(i) (LDSMODE ? (uint32_t)LM[i] : (uint32_t)A[i].mtch_len)
+#define AQ(i) (A[i].index_in_read)
+#define AT(i) (A[i].ref_offset)
+#define AM(i) ((uint32_t)A[i].mtch_len)
 	for (int32_t st = 0; st < n;) {
 		int32_t ed = st + 1;
 		uint32_t ref_ID = A[st].ref_ID, direction = A[st].direction;
@@ -1351,18 +1353,17 @@ DN void chain_dp_M3(WCtxL &w)
 				int indel = p_q - p_t - (max_q - max_t);
 				int ai = ABSV(indel);
 				if (ai > 200) continue;
-				int ns = (LDSMODE ? (int)LS[p] : score_v[p - st]) + ca_ml - (ai >> 4) - ((max_q - p_q) >> 8);
+				int ns = score_v[p - st] + ca_ml - (ai >> 4) - ((max_q - p_q) >> 8);
 				if (ns > ams) { ams = ns; best_pre = p; }
 			}
-			if (LDSMODE) { LP[ca] = (uint32_t)best_pre; LS[ca] = (uint32_t)ams; } else { A[ca].pre = best_pre; score_v[ca - st] = ams; }
+			A[ca].pre = best_pre; score_v[ca - st] = ams;
 			if (max_score < ams) { max_score = ams; max_anchor = ca; }
 		}
-#define APRE(i) (LDSMODE ? (int32_t)LP[i] : A[i].pre)
 		int sum_INDEL = 0, anchor_number = 1; int32_t pre = max_anchor;
 		int sum_score = (A[max_anchor].duplicate) ? 1 : A[max_anchor].score;
 		bool with_top = !A[max_anchor].useless;
-		for (; APRE(pre) != -1; anchor_number++) {
-			int32_t pre_ = APRE(pre);
+		for (; A[pre].pre != -1; anchor_number++) {
+			int32_t pre_ = A[pre].pre;
 			sum_INDEL += (AQ(pre) - AQ(pre_)) - (AT(pre) - AT(pre_));
 			with_top |= (!A[pre].useless);
 			sum_score += (A[pre].duplicate) ? 1 : A[pre].score;
@@ -1380,7 +1381,6 @@ DN void chain_dp_M3(WCtxL &w)
 #undef AQ
 #undef AT
 #undef AM
-#undef APRE
 }
 
 // comparators on chains
@@ -1504,7 +1504,7 @@ DN void resolve_tree(WCtxL &w)
 	}
 	DSB_SERIAL(w) {
 		if (w.n_anc < 50) for (uint32_t i = 0; i < w.n_anc; i++) chain_insert_M2(w, i);
-		else if (!wave_dp) chain_dp_M3<false>(w);
+		else if (!wave_dp) chain_dp_M3(w);
 	}
 	serial_end(w);
 	chain_top_select(w);
@@ -3388,7 +3388,17 @@ DN void get_score_M2(WCtxL &w, SDirL *sd, uint32_t l_read, DsbScHash *sc_hash)
 	}
 }
 
-// delete_small_score_rst (src/cly.c:2883-2993)
+// delete_small_score_rst (src/cly.c:2883-2993); the cut at its head (src/cly.c:2885-2892, lane 0) is a function of its own so that
+// tests/stage can call it
+DV void small_score_head_cut(WCtxL &w)
+{
+	if (w.n_hit > 200) {
+		uint32_t r = 200;
+		for (; r < w.n_hit && w.hit[r].sum_score > 50; r++);
+		w.n_hit = r;
+	}
+	w.n_hit = MINV(400u, w.n_hit);
+}
 template <bool MW>
 DN void delete_small_score_rst(WCtxL &w, SDirL *sd, uint32_t l_read)
 {
@@ -3397,12 +3407,7 @@ DN void delete_small_score_rst(WCtxL &w, SDirL *sd, uint32_t l_read)
 	for (int i = DSB_LANE; i < 256; i += DSB_WAVE) { w.sc[i].next = 0; w.sc[i].seed_ID = 0; }
 	wave_sync();
 	DSB_SERIAL(w) {
-		if (w.n_hit > 200) {
-			uint32_t r = 200;
-			for (; r < w.n_hit && w.hit[r].sum_score > 50; r++);
-			w.n_hit = r;
-		}
-		w.n_hit = MINV(400u, w.n_hit);
+		small_score_head_cut(w);
 		sc_hash_idx(w.sc, w.hit, w.n_hit);
 	}
 	serial_end(w);

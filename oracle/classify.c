@@ -739,6 +739,34 @@ static void resolve_tree(ora_ctx_t *cx)
 	cx->n_hit = rst_num;
 }
 
+/* stage access for tests/test_stage_chain.py (a-10).  anchors: rows of 8 u32 (index_in_read, ref_ID, ref_offset, mtch_len, score,
+ * direction, anchor_useless, duplicate), pre = -1 as map_seed leaves it.  m3 == 0: the loop of chain_insert_M2 over all anchors,
+ * else chain_insert_M3, whatever n is (resolve_tree takes M2 below 50 anchors).  order[i] = the input row that stands at place i
+ * afterwards, pre[i] = its chain_anchor_pre; raw: the chains as the insertion left them (n_raw of them, at most max_raw stored),
+ * fin: what the sort by chain_cmp_by_score and the cut leave.  Returns the number of chains left. */
+int ora_resolve_stage(ora_ctx_t *c, const uint32_t *anchors, uint32_t n, int m3, uint32_t *order, int32_t *pre,
+                      ora_chain_t *raw, uint32_t max_raw, uint32_t *n_raw, ora_chain_t *fin, uint32_t max_fin)
+{
+	c->n_anc = 0; c->n_hit = 0;
+	for (uint32_t i = 0; i < n; i++) {
+		const uint32_t *r = anchors + 8 * (size_t)i;
+		anchor_t *a = push_anchor(c);
+		a->index_in_read = r[0]; a->ref_ID = r[1]; a->ref_offset = r[2]; a->a_m.mtch_len = (uint16_t)r[3]; a->a_m.score = (int16_t)r[4];
+		a->direction = (uint8_t)r[5]; a->anchor_useless = (uint8_t)r[6]; a->duplicate = (uint8_t)r[7]; a->pre = -1; a->global_offset = i;
+	}
+	if (!m3) for (uint32_t i = 0; i < c->n_anc; i++) chain_insert_M2(c, i);
+	else chain_insert_M3(c);
+	for (uint32_t i = 0; i < n; i++) { order[i] = (uint32_t)c->anc[i].global_offset; pre[i] = c->anc[i].pre; }
+	*n_raw = c->n_hit;
+	memcpy(raw, c->hit, sizeof(chain_t) * MINV(c->n_hit, max_raw));
+	if (c->n_hit > 1) glibc_qsort(c, c->hit, c->n_hit, sizeof(chain_t), chain_cmp_by_score);
+	int rst_num = MINV(5, c->n_hit);
+	while (rst_num < c->n_hit && c->hit[rst_num].with_top_anchor == 1) rst_num++;
+	c->n_hit = rst_num;
+	memcpy(fin, c->hit, sizeof(chain_t) * MINV(c->n_hit, max_fin));
+	return (int)c->n_hit;
+}
+
 /* ---- a-11 sc_hash_idx / combine_chain, src/cly.c:1691-1710,1763-1808 ------------------- */
 static void sc_hash_idx(sch_t *sc, chain_t *hit, uint32_t n_hit)
 {
@@ -1203,19 +1231,9 @@ static int chain_cmp_by_MEM_score(const void *a_, const void *b_)
 	if (sa > sb) return -1;
 	return (a->sum_score % 2);
 }
-static void delete_small_score_rst(ora_ctx_t *cx, const ora_idx_t *x, sdir_t *sd, uint32_t l_read)
+/* ... its part behind get_score_M2 (src/cly.c:2921-2993) */
+static void small_score_tail(ora_ctx_t *cx, int min_length, int min_score, int min_score_LV3, uint32_t l_read)
 {
-	if (cx->n_hit == 0) return;
-	if (cx->n_hit > 200) {
-		uint32_t r = 200;
-		for (; r < cx->n_hit && cx->hit[r].sum_score > 50; r++);
-		cx->n_hit = r;
-	}
-	cx->n_hit = MINV(400, cx->n_hit);
-	uint32_t n_sc = 256 + (cx->n_hit << 1);
-	if (n_sc > cx->m_sc) { cx->m_sc = n_sc + 20; cx->sc_hash = realloc(cx->sc_hash, cx->m_sc * sizeof(sch_t)); }
-	sc_hash_idx(cx->sc_hash, cx->hit, cx->n_hit);
-	get_score_M2(cx, x, sd, l_read, cx->sc_hash);
 	chain_t *st_c = cx->hit, *ed_c = st_c + cx->n_hit, *c_c;
 	if (cx->n_hit > 1) glibc_qsort(cx, cx->hit, cx->n_hit, sizeof(chain_t), chain_cmp_by_pos);
 	for (c_c = st_c; c_c < ed_c - 1; c_c++) {
@@ -1247,12 +1265,28 @@ static void delete_small_score_rst(ora_ctx_t *cx, const ora_idx_t *x, sdir_t *sd
 	} else {
 		for (c_c = st_c; c_c < ed_c; c_c++) {
 			int s = c_c->sum_score + ((c_c->q_ed - c_c->q_st) >> 5);
-			if (s < (x->filter_min_score_LV3) && (c_c->q_ed - c_c->q_st < x->filter_min_length || s < x->filter_min_score)) c_c->sum_score = 0;
+			if (s < (min_score_LV3) && (c_c->q_ed - c_c->q_st < min_length || s < min_score)) c_c->sum_score = 0;
 		}
 	}
 	if (cx->n_hit > 1) glibc_qsort(cx, cx->hit, cx->n_hit, sizeof(chain_t), chain_cmp_by_MEM_score);
 	for (c_c = st_c; c_c < ed_c; c_c++) if (c_c->sum_score == 0) break;
 	cx->n_hit = c_c - st_c;
+}
+
+static void delete_small_score_rst(ora_ctx_t *cx, const ora_idx_t *x, sdir_t *sd, uint32_t l_read)
+{
+	if (cx->n_hit == 0) return;
+	if (cx->n_hit > 200) {
+		uint32_t r = 200;
+		for (; r < cx->n_hit && cx->hit[r].sum_score > 50; r++);
+		cx->n_hit = r;
+	}
+	cx->n_hit = MINV(400, cx->n_hit);
+	uint32_t n_sc = 256 + (cx->n_hit << 1);
+	if (n_sc > cx->m_sc) { cx->m_sc = n_sc + 20; cx->sc_hash = realloc(cx->sc_hash, cx->m_sc * sizeof(sch_t)); }
+	sc_hash_idx(cx->sc_hash, cx->hit, cx->n_hit);
+	get_score_M2(cx, x, sd, l_read, cx->sc_hash);
+	small_score_tail(cx, x->filter_min_length, x->filter_min_score, x->filter_min_score_LV3, l_read);
 }
 
 /* ---- a-14 detect_primary, src/cly.c:2995-3058 ------------------------------------------ */
@@ -1288,6 +1322,38 @@ static void detect_primary(chain_t *hit, uint32_t n_hit, uint32_t read_len)
 			if (n_primary_v > 750) n_primary_v = 750;
 		}
 	}
+}
+
+/* stage access for tests/test_stage_finish.py (a-13 without the extensions, a-14): n chains go through the cut at the head of
+ * delete_small_score_rst (src/cly.c:2885-2892), then -- get_score_M2 left out -- through its part behind get_score_M2 and through
+ * detect_primary.  tail: all n_cut chains of the array as the tail left them (n_tail of them stay), chains: the same after
+ * detect_primary.  Returns n_tail; *max_read_l is the running maximum, in and out. */
+int ora_finish_stage(ora_ctx_t *c, ora_chain_t *chains, uint32_t n, uint32_t read_len, int *max_read_l, int min_length, int min_score,
+                     int min_score_LV3, ora_chain_t *tail, uint32_t *n_cut)
+{
+	c->n_hit = 0;
+	for (uint32_t i = 0; i < n; i++) memcpy(push_hit(c), chains + i, sizeof(chain_t));
+	c->max_read_l = *max_read_l;
+	if (c->n_hit != 0) {
+		if (c->n_hit > 200) {
+			uint32_t r = 200;
+			for (; r < c->n_hit && c->hit[r].sum_score > 50; r++);
+			c->n_hit = r;
+		}
+		c->n_hit = MINV(400, c->n_hit);
+		*n_cut = c->n_hit;
+		small_score_tail(c, min_length, min_score, min_score_LV3, read_len);
+	} else *n_cut = 0;
+	memcpy(tail, c->hit, sizeof(chain_t) * *n_cut);
+	detect_primary(c->hit, c->n_hit, read_len);
+	memcpy(chains, c->hit, sizeof(chain_t) * *n_cut);
+	*max_read_l = c->max_read_l;
+	return (int)c->n_hit;
+}
+/* a-17 on its own: glibc's qsort of n chains with chain_cmp_by_score (0), chain_cmp_by_pos (1) or chain_cmp_by_MEM_score (2) */
+void ora_sort_stage(ora_ctx_t *c, ora_chain_t *chains, uint32_t n, int which)
+{
+	glibc_qsort(c, chains, n, sizeof(chain_t), which == 0 ? chain_cmp_by_score : which == 1 ? chain_cmp_by_pos : chain_cmp_by_MEM_score);
 }
 
 /* ---- classify_seq, src/cly.c:3064-3132 ------------------------------------------------- */

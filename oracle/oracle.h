@@ -104,6 +104,19 @@ int ora_sdp_match_stage(ora_ctx_t *c, const char *seq, uint32_t len, int strand,
                         const uint8_t *t_str, uint32_t t_len, uint32_t t_st, int is_forward, uint32_t *out, int max_out);
 int ora_gap_stage(ora_ctx_t *c, const char *seq, uint32_t len, int strand, const uint8_t *refbin, uint64_t ref_bases,
                   const int32_t *anchors, uint32_t n_anchors, int32_t c_a, uint32_t *gap_nodes, uint32_t *n_gaps);
+/* a chain as the stage entries below take and give it: the layout of chain_item as oracle/classify.c and the device code hold it */
+typedef struct {
+	uint32_t ref_ID; int32_t q_t_dis; uint32_t sum_score, anchor_number;
+	uint8_t direction, with_top_anchor, primary, pri_index;
+	uint32_t t_st, t_ed, q_st, q_ed, indel, chain_id; int32_t cur;
+} ora_chain_t;
+/* a-10 on its own (tests/test_stage_chain.py): chain_insert_M2 / chain_insert_M3 and the end of resolve_tree on a list of anchors */
+int ora_resolve_stage(ora_ctx_t *c, const uint32_t *anchors, uint32_t n, int m3, uint32_t *order, int32_t *pre,
+                      ora_chain_t *raw, uint32_t max_raw, uint32_t *n_raw, ora_chain_t *fin, uint32_t max_fin);
+/* a-13 without the extensions and a-14 (tests/test_stage_finish.py); a-17: glibc's qsort with one of the three chain comparators */
+int ora_finish_stage(ora_ctx_t *c, ora_chain_t *chains, uint32_t n, uint32_t read_len, int *max_read_l, int min_length, int min_score,
+                     int min_score_LV3, ora_chain_t *tail, uint32_t *n_cut);
+void ora_sort_stage(ora_ctx_t *c, ora_chain_t *chains, uint32_t n, int which);
 #ifdef __cplusplus
 }
 #endif

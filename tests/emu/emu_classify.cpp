@@ -393,3 +393,73 @@ extern "C" int emu_stage_middle(StageChain *cases, uint32_t n, const uint8_t *bi
 	for (uint32_t k = 0; k < n; k++) { j.cc = cases + k; stage_run(j); }
 	return 0;
 }
+
+// ---- the chain stages form by form (tests/stage/dsb_stage_forms.h, tests/test_stage_chain.py, tests/test_stage_finish.py): resolve_tree with the
+// sort, the DP and the selection forced; the cut and the tail of delete_small_score_rst, detect_primary; glibc_sort_chains
+struct Stage2Job { StageHost *h; uint8_t *slice; StageRes *rc; StageFin *fc; const uint32_t *rows; uint32_t *order; int32_t *pre; DsbChain *hits, *raw; };
+static void stage2_lane(void *p)
+{
+	Stage2Job *j = (Stage2Job *)p; StageHost *h = j->h;
+	stage_ctx(h->w, &h->sx, j->slice, h->wtab, h->ring, h->red, h->cnt, &h->ri);
+	if (j->rc) stage_resolve(h->w, j->rc, j->rows, j->order, j->pre, j->hits, j->raw, j->slice);
+	else stage_finish(h->w, &h->sx, j->fc, j->hits, j->raw, j->slice);
+}
+static std::vector<uint8_t> g_stage2_slice;      // (at file scope: a function's static would bring a guard variable and, in the 64-lane build, an atomic hook)
+static std::vector<uint8_t> &stage2_slice()
+{
+	if (g_stage2_slice.empty()) g_stage2_slice.assign(STAGE2_SLICE, 0xCD);
+	return g_stage2_slice;
+}
+static void stage2_run(Stage2Job &j)
+{
+#if DSB_EMU_LANES == 64
+	dsb_emu_run(stage2_lane, &j);
+#else
+	stage2_lane(&j);
+#endif
+}
+static void stage2_regions(Stage2Job &j, const void *cases, size_t case_bytes)
+{
+#if DSB_EMU_LANES == 64
+	StageHost *h = j.h; uint8_t *s = j.slice;
+	dsb_emu_regions_clear();
+	dsb_emu_region(&j, sizeof j, "job"); dsb_emu_region(h->wtab, sizeof h->wtab, "LDS window table"); dsb_emu_region(h->ring, sizeof h->ring, "LDS ring");
+	dsb_emu_region(h->red, sizeof h->red, "LDS red"); dsb_emu_region(h->cnt, sizeof h->cnt, "LDS counters"); dsb_emu_region(&h->sx, sizeof h->sx, "index descriptor");
+	dsb_emu_region(&h->w, sizeof h->w, "context"); dsb_emu_region(&h->ri, sizeof h->ri, "reference info"); dsb_emu_region(&h->dpb, sizeof h->dpb, "LDS DP batch");
+	dsb_emu_region(s + STAGE2_OFF_ANC, STAGE2_MAX_ANC * 40u, "anchors"); dsb_emu_region(s + STAGE2_OFF_ANC_TMP, STAGE2_MAX_ANC * 40u, "anchors (copy)");
+	dsb_emu_region(s + STAGE2_OFF_SORTKEY, 2u * STAGE2_MAX_ANC * 8u, "sort keys"); dsb_emu_region(s + STAGE2_OFF_SORTIDX, 2u * STAGE2_MAX_ANC * 4u, "sort indices");
+	dsb_emu_region(s + STAGE2_OFF_SCOREV, 4096, "score_v"); dsb_emu_region(s + STAGE2_OFF_WIN, 4096, "reference window"); dsb_emu_region(s + STAGE2_OFF_HIT_TMP, STAGE2_MAX_HIT * 48u, "chains (copy)");
+	dsb_emu_region(cases, case_bytes, "cases");
+#else
+	(void)j; (void)cases; (void)case_bytes;
+#endif
+}
+extern "C" uint32_t emu_stage_sizes2(uint32_t *out)
+{
+	out[0] = sizeof(StageRes); out[1] = sizeof(StageFin); out[2] = sizeof(DsbChain); out[3] = DSB_WTAB_SLOTS; out[4] = DSB_RANKSORT_MAX; out[5] = DSB_CHAINDP_LDS; out[6] = STAGE2_MAX_ANC; out[7] = STAGE2_MAX_HIT;
+	out[8] = STAGE2_GUARD; out[9] = DSB_EMU_LANES;
+	return 10;
+}
+extern "C" int emu_stage_resolve(StageRes *cases, uint32_t n, const uint32_t *rows, size_t n_rows, uint32_t *order, int32_t *pre, DsbChain *hits, size_t n_hits, DsbChain *raw, size_t n_raw)
+{
+	if (stage_resolve_check(cases, n, rows, n_rows, n_hits, n_raw)) return __LINE__;
+	Stage2Job j; memset(&j, 0, sizeof j); j.h = stage_host(); j.slice = stage2_slice().data(); j.rows = rows; j.order = order; j.pre = pre; j.hits = hits; j.raw = raw;
+	stage2_regions(j, cases, (size_t)n * sizeof(StageRes));
+#if DSB_EMU_LANES == 64
+	dsb_emu_region(rows, n_rows * 32, "anchor rows"); dsb_emu_region(order, n_rows * 4, "anchor order"); dsb_emu_region(pre, n_rows * 4, "anchor links");
+	dsb_emu_region(hits, n_hits * sizeof(DsbChain), "chains"); dsb_emu_region(raw, n_raw * sizeof(DsbChain), "chains before the selection");
+#endif
+	for (uint32_t k = 0; k < n; k++) { j.rc = cases + k; stage2_run(j); }
+	return 0;
+}
+extern "C" int emu_stage_finish(StageFin *cases, uint32_t n, DsbChain *chains, DsbChain *tail, size_t n_chains)
+{
+	if (stage_finish_check(cases, n, n_chains)) return __LINE__;
+	Stage2Job j; memset(&j, 0, sizeof j); j.h = stage_host(); j.slice = stage2_slice().data(); j.hits = chains; j.raw = tail;
+	stage2_regions(j, cases, (size_t)n * sizeof(StageFin));
+#if DSB_EMU_LANES == 64
+	dsb_emu_region(chains, n_chains * sizeof(DsbChain), "chains"); dsb_emu_region(tail, n_chains * sizeof(DsbChain), "chains behind the tail");
+#endif
+	for (uint32_t k = 0; k < n; k++) { j.fc = cases + k; stage2_run(j); }
+	return 0;
+}

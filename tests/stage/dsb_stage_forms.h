@@ -1,4 +1,5 @@
-// TEST INFRASTRUCTURE: stage a-12 (sdp_match in its five forms, gap_lane, sdp_middle_M2; dsb_classify_dev.h) called form by form
+// TEST INFRASTRUCTURE: stage a-12 (sdp_match in its five forms, gap_lane, sdp_middle_M2; dsb_classify_dev.h) and, further down, the
+// chain stages a-10, a-13, a-14 and a-17 (resolve_tree in every form, the tail of delete_small_score_rst, detect_primary, glibc_sort_chains) called form by form
 // on cases that a test lays out in flat arrays, so that a test knows which code produced a node list.  One text for the three
 // legs: tests/emu/emu_classify.cpp compiles it for the host (1 lane, or 64 lanes with the race detector), tests/stage/dsb_stage.hip
 // for gfx950 (one wavefront per case).  Included after dsb_classify_dev.h; nothing here is part of libdesamba_amd.so.
@@ -154,6 +155,207 @@ DN void stage_middle(WCtxL &w, DSB_LDS_AS DsbDevIndex *sx, StageChain *cs, const
 	wave_sync();
 	if (DSB_LANE == 0) { cs->score = score; cs->status = c.n_anc <= STAGE_MAX_ANC ? (uint32_t)w.status : 0xffffffffu; }
 	wave_sync();
+}
+
+// ---- stages a-10 (resolve_tree), a-13 behind get_score_M2, a-14 (detect_primary), a-17 (glibc_sort_chains): tests/test_stage_chain.py,
+// tests/test_stage_finish.py.  Inputs are arrays of anchors or chains; no read, no index.
+//   rows    anchors, 8 u32 each: index_in_read, ref_ID, ref_offset, mtch_len, score, direction, useless, duplicate (pre = -1)
+//   order   per anchor place: the input row that stands there afterwards;  pre: its predecessor link
+//   hits    one region of hit_cap + STAGE2_GUARD DsbChain per case, filled with a pattern by the test: w.hit itself
+//   raw     one region of hit_cap DsbChain per case: the chains as the DP left them, before chain_top_select
+enum { RES_SORT_DISTINCT = 1, RES_SORT_TIE = 2, RES_SORT_MERGE = 3 };
+enum { RES_DP_M2 = 1, RES_DP_LDS = 2, RES_DP_GLOBAL = 3, RES_DP_SERIAL = 4 };
+enum { RES_SEL_RANK = 1, RES_SEL_GLIBC = 2 };
+struct StageRes {                 // one resolve_tree; sort = dp = sel = 0: resolve_tree itself, else the forms named (sort: none for RES_DP_M2)
+	uint32_t a0, n_anc, hit_cap, sort, dp, sel, pad0, pad1;
+	uint64_t hit_off, raw_off;
+	// out: chains before the selection (0xffffffff: resolve_tree itself, unknown) and after it, w.status, whether the forms are defined for
+	// the case, and the forms resolve_tree's own tests lead to (nat_sort 0: no sort, fewer than 50 anchors; nat_sel 0: at most one chain)
+	uint32_t n_raw, n_hit, status, defined, nat_sort, nat_dp, nat_sel, pad2;
+};
+struct StageFin {                 // which 0: the cut at the head of delete_small_score_rst, its part behind get_score_M2, detect_primary; 1 .. 3: glibc_sort_chains<which - 1>
+	uint32_t c0, n, read_len, which; int32_t max_read_l, min_length, min_score, min_score_LV3;
+	uint32_t n_cut, n_hit, status; int32_t max_read_l_out;        // out
+};
+#define STAGE2_MAX_ANC 3072u
+#define STAGE2_MAX_HIT 3200u
+#define STAGE2_GUARD 2u            /* guard chains behind a case's region */
+// its own slice: both anchor arrays, both halves of the sort keys and indices, score_v, one reference window (detect_primary's bytes), hit_tmp
+#define STAGE2_OFF_ANC 0u
+#define STAGE2_OFF_ANC_TMP (STAGE2_OFF_ANC + STAGE2_MAX_ANC * 40u)
+#define STAGE2_OFF_SORTKEY (STAGE2_OFF_ANC_TMP + STAGE2_MAX_ANC * 40u)
+#define STAGE2_OFF_SORTIDX (STAGE2_OFF_SORTKEY + 2u * STAGE2_MAX_ANC * 8u)
+#define STAGE2_OFF_SCOREV (STAGE2_OFF_SORTIDX + 2u * STAGE2_MAX_ANC * 4u)
+#define STAGE2_OFF_WIN (STAGE2_OFF_SCOREV + 4096u)
+#define STAGE2_OFF_HIT_TMP (STAGE2_OFF_WIN + 4096u)
+#define STAGE2_SLICE (STAGE2_OFF_HIT_TMP + STAGE2_MAX_HIT * 48u)
+static_assert(sizeof(DsbAnchor) == 40 && sizeof(DsbChain) == 48 && DSB_REFWIN_FRONT + DSB_REFWIN <= 4096u, "slice of the chain stages");
+
+DV void stage2_ctx(WCtxL &w, uint8_t *slice)
+{
+	w.anc = (DsbAnchor *)(slice + STAGE2_OFF_ANC); w.anc_tmp = (DsbAnchor *)(slice + STAGE2_OFF_ANC_TMP);
+	w.sortkey = (uint64_t *)(slice + STAGE2_OFF_SORTKEY); w.sortidx = (uint32_t *)(slice + STAGE2_OFF_SORTIDX);
+	w.score_v = (int *)(slice + STAGE2_OFF_SCOREV); w.win_mid = slice + STAGE2_OFF_WIN + DSB_REFWIN_FRONT;
+	w.hit_tmp = (DsbChain *)(slice + STAGE2_OFF_HIT_TMP);
+	w.anc_cap = w.anc_cap_main = STAGE2_MAX_ANC; w.n_anc = 0; w.n_hit = 0; w.status = 0;
+}
+// a-10: the sort, the DP and the selection in the forms the case names, or resolve_tree as it is
+DN void stage_resolve(WCtxL &w, StageRes *cs, const uint32_t *rows, uint32_t *order, int32_t *pre, DsbChain *hits, DsbChain *raw, uint8_t *slice)
+{
+	const StageRes c = *cs;
+	const int lane = DSB_LANE; const uint32_t n = c.n_anc;
+	wave_sync();
+	stage2_ctx(w, slice);
+	w.hit = hits + c.hit_off; w.hit_cap = c.hit_cap;
+	wave_sync();
+	uint32_t *const wtab = w.wtab;
+	uint32_t defined = n <= STAGE2_MAX_ANC && c.hit_cap >= 1 && c.hit_cap <= STAGE2_MAX_HIT, n_raw = 0xffffffffu, nat_sort = 0, nat_dp = RES_DP_M2, nat_sel = 0;
+	if (defined) {
+		uint32_t max_ref = 0;
+		for (uint32_t i = (uint32_t)lane; i < n; i += DSB_WAVE) {
+			const uint32_t *r = rows + 8 * (size_t)(c.a0 + i);
+			DsbAnchor an; an.mtch_len = (uint16_t)r[3]; an.score = (int16_t)r[4]; an.left_len = an.left_ED = an.rigt_len = an.rigt_ED = 0; an.direction = (uint8_t)r[5];
+			an.useless = (uint8_t)r[6]; an.duplicate = (uint8_t)r[7]; an.pad0 = 0; an.seed_ID = an.chain_id = 0; an.ref_ID = r[1]; an.ref_offset = r[2]; an.index_in_read = r[0];
+			an.pre = -1; an.global_offset = i;
+			w.anc[i] = an; max_ref = MAXV(max_ref, r[1]);
+		}
+		max_ref = (uint32_t)grp_max_i((int)max_ref);
+		wave_sync();
+		w.n_anc = n;
+		wave_sync();
+		// resolve_tree's and chain_sort_M3's own tests, restated: what they lead to, not an observation of the path taken -- a change of the
+		// product's thresholds shows in the results of the natural run, not in these words.  (nat_sel follows from the chains the DP leaves, so
+		// only a forced run reports it; for resolve_tree itself the test takes it from the oracle's chain count.)
+		if (n >= 50) {
+			nat_sort = n <= DSB_RANKSORT_MAX ? (max_ref < (1u << 21) && n <= 1024 ? RES_SORT_DISTINCT : RES_SORT_TIE) : RES_SORT_MERGE;
+			nat_dp = n <= DSB_CHAINDP_LDS ? RES_DP_LDS : RES_DP_GLOBAL;
+		}
+		if (!c.sort && !c.dp && !c.sel) resolve_tree(w);
+		else {
+			if (c.dp != RES_DP_M2) {
+				if (c.sort == RES_SORT_DISTINCT) defined = n <= 1024 && max_ref < (1u << 21);
+				if (c.sort == RES_SORT_TIE) defined = n <= DSB_WTAB_SLOTS / 2;
+				if (c.dp == RES_DP_LDS) defined = defined && n <= DSB_CHAINDP_LDS;
+			}
+			if (defined) {
+				if (c.dp != RES_DP_M2) { if (c.sort == RES_SORT_DISTINCT) chain_sort_M3<1>(w); else if (c.sort == RES_SORT_TIE) chain_sort_M3<2>(w); else chain_sort_M3<3>(w); }
+				if (c.dp == RES_DP_LDS) { lds_w32 *L = (lds_w32 *)w.wtab; chain_stage_M3(w, L, DSB_CHAINDP_LDS); chain_dp_M3_wave(w, L, DSB_CHAINDP_LDS); chain_unstage_M3(w, L, DSB_CHAINDP_LDS); }
+				else if (c.dp == RES_DP_GLOBAL) { uint32_t *L = reinterpret_cast<uint32_t *>(w.anc_tmp); chain_stage_M3(w, L, n); chain_dp_M3_wave(w, L, n); chain_unstage_M3(w, L, n); }
+				else {
+					DSB_SERIAL(w) {
+						if (c.dp == RES_DP_M2) for (uint32_t i = 0; i < w.n_anc; i++) chain_insert_M2(w, i);
+						else chain_dp_M3(w);
+					}
+					serial_end(w);
+				}
+				n_raw = w.n_hit;
+				for (uint32_t i = (uint32_t)lane; i < n_raw; i += DSB_WAVE) raw[c.raw_off + i] = w.hit[i];
+				wave_sync();
+				nat_sel = n_raw <= 1 ? 0 : n_raw > DSB_WTAB_SLOTS / 2 ? RES_SEL_GLIBC : RES_SEL_RANK;
+				if (c.sel == RES_SEL_GLIBC) { w.wtab = nullptr; wave_sync(); chain_top_select(w); w.wtab = wtab; wave_sync(); }
+				else if (n_raw <= DSB_WTAB_SLOTS / 2) chain_top_select(w);
+				else defined = 0;
+			}
+		}
+		wave_sync();
+		if (defined) for (uint32_t i = (uint32_t)lane; i < n; i += DSB_WAVE) { order[c.a0 + i] = (uint32_t)w.anc[i].global_offset; pre[c.a0 + i] = w.anc[i].pre; }
+	}
+	wave_sync();
+	if (lane == 0) { cs->n_raw = n_raw; cs->n_hit = w.n_hit; cs->status = (uint32_t)w.status; cs->defined = defined; cs->nat_sort = nat_sort; cs->nat_dp = nat_dp; cs->nat_sel = nat_sel; }
+	wave_sync();
+}
+// The part of delete_small_score_rst behind get_score_M2 (dsb_classify_dev.h, src/cly.c:2921-2993) is not callable on its own: the same
+// statements in the same order, replayed here -- glibc_sort_chains<1>, absorb and merge, the three filters, glibc_sort_chains<2>, the cut.
+// (Moving them into a function of the product changed the compiler's resource report of the k_classify kernels, see DESIGN.md.)
+DV void stage_small_score_tail(WCtxL &w, uint32_t l_read)
+{
+	DsbXP x = w.x;
+	DsbChain *st_c = w.hit, *ed_c = st_c + w.n_hit, *c_c;
+	if (w.n_hit > 1) glibc_sort_chains<1>(w, w.n_hit);
+	for (c_c = st_c; c_c < ed_c - 1; c_c++) {
+		if (c_c->sum_score == 0) continue;
+		DsbChain *nx = c_c + 1;
+		for (; nx < ed_c; nx++) {
+			if (c_c->ref_ID == nx->ref_ID) {
+				if (c_c->direction != nx->direction) continue;
+				if (nx->sum_score == 0) continue;
+				if (nx->t_st < c_c->t_st + 5 && nx->q_st < c_c->q_st + 5 && nx->sum_score < c_c->sum_score + 5) {
+					nx->sum_score = 0; nx->q_ed = nx->q_st; nx->t_ed = nx->t_st;
+					continue;
+				}
+				int dis_t = nx->t_st - c_c->t_ed, dis_q = nx->q_st - c_c->q_ed;
+				int dis_t_q = ABSV(dis_t - dis_q);
+				if ((dis_t > -20 && dis_t < 1000 && dis_q > -20 && dis_q < 1000) && dis_t_q < 200) {
+					c_c->t_ed = MAXV(c_c->t_ed, nx->t_ed); c_c->q_ed = MAXV(c_c->q_ed, nx->q_ed);
+					c_c->sum_score += nx->sum_score;
+					nx->sum_score = 0; nx->q_ed = nx->q_st; nx->t_ed = nx->t_st;
+				}
+			} else break;
+		}
+	}
+	w.max_read_l = MAXV((uint32_t)w.max_read_l, l_read);
+	if (w.max_read_l < 510) {
+		for (c_c = st_c; c_c < ed_c; c_c++) { int s = c_c->sum_score + ((c_c->q_ed - c_c->q_st) >> 5); if (s < 26) c_c->sum_score = 0; }
+	} else if (l_read < 310) {
+		for (c_c = st_c; c_c < ed_c; c_c++) { int s = c_c->sum_score + ((c_c->q_ed - c_c->q_st) >> 5); if (s < 30) c_c->sum_score = 0; }
+	} else {
+		for (c_c = st_c; c_c < ed_c; c_c++) {
+			int s = c_c->sum_score + ((c_c->q_ed - c_c->q_st) >> 5);
+			if (s < (x->filter_min_score_LV3) && (c_c->q_ed - c_c->q_st < (uint32_t)x->filter_min_length || s < x->filter_min_score)) c_c->sum_score = 0;
+		}
+	}
+	if (w.n_hit > 1) glibc_sort_chains<2>(w, w.n_hit);
+	for (c_c = st_c; c_c < ed_c; c_c++) if (c_c->sum_score == 0) break;
+	w.n_hit = c_c - st_c;
+}
+// a-13 / a-14 / a-17 on the chains [c0, c0 + n) of `chains` (in place); tail: the same places, the chains as the tail of delete_small_score_rst left them
+DN void stage_finish(WCtxL &w, DSB_LDS_AS DsbDevIndex *sx, StageFin *cs, DsbChain *chains, DsbChain *tail, uint8_t *slice)
+{
+	const StageFin c = *cs;
+	const int lane = DSB_LANE;
+	wave_sync();
+	stage2_ctx(w, slice);
+	w.hit = chains + c.c0; w.hit_cap = c.n; w.n_hit = c.n; w.max_read_l = c.max_read_l;
+	sx->filter_min_length = c.min_length; sx->filter_min_score = c.min_score; sx->filter_min_score_LV3 = c.min_score_LV3;
+	wave_sync();
+	uint32_t n_cut = c.n;
+	if (c.n > STAGE2_MAX_HIT) n_cut = 0;
+	else if (c.which) {
+		DSB_SERIAL(w) { if (c.which == 1) glibc_sort_chains<0>(w, c.n); else if (c.which == 2) glibc_sort_chains<1>(w, c.n); else glibc_sort_chains<2>(w, c.n); }
+		serial_end(w);
+	} else {
+		if (w.n_hit != 0) {
+			// delete_small_score_rst without its extensions: the product's own cut at its head, then its part behind get_score_M2 replayed (stage_small_score_tail)
+			DSB_SERIAL(w) small_score_head_cut(w);
+			serial_end(w);
+			n_cut = w.n_hit;
+			DSB_SERIAL(w) stage_small_score_tail(w, c.read_len);
+			serial_end(w);
+		}
+		for (uint32_t i = (uint32_t)lane; i < n_cut; i += DSB_WAVE) tail[c.c0 + i] = w.hit[i];
+		wave_sync();
+		DSB_SERIAL(w) detect_primary(w, c.read_len);
+		serial_end(w);
+	}
+	wave_sync();
+	if (lane == 0) { cs->n_cut = n_cut; cs->n_hit = w.n_hit; cs->status = c.n > STAGE2_MAX_HIT ? 0xffffffffu : (uint32_t)w.status; cs->max_read_l_out = w.max_read_l; }
+	wave_sync();
+}
+// what the host entries refuse before a case reaches the device code: regions outside the arrays, scores outside the domain (a group
+// without a positive score has no best anchor, in the reference as here)
+static inline int stage_resolve_check(const StageRes *cs, uint32_t n, const uint32_t *rows, size_t n_rows, size_t n_hits, size_t n_raw)
+{
+	for (uint32_t k = 0; k < n; k++) {
+		const StageRes &c = cs[k];
+		if ((size_t)c.a0 + c.n_anc > n_rows || c.hit_off + c.hit_cap + STAGE2_GUARD > n_hits || c.raw_off + c.hit_cap > n_raw) return 1;
+		for (uint32_t i = 0; i < c.n_anc; i++) { const uint32_t *r = rows + 8 * (size_t)(c.a0 + i); if (r[4] < 1 || r[4] > 32767 || r[3] > 65535 || r[5] > 1) return 1; }
+	}
+	return 0;
+}
+static inline int stage_finish_check(const StageFin *cs, uint32_t n, size_t n_chains)
+{
+	for (uint32_t k = 0; k < n; k++) if ((size_t)cs[k].c0 + cs[k].n > n_chains || cs[k].which > 3) return 1;
+	return 0;
 }
 
 }  // namespace
