@@ -88,6 +88,14 @@ class DsbAbundanceSummary(C.Structure):
 ABUNDANCE_DTYPE = [("numreads", "<u8"), ("uniqreads", "<u8"), ("est_reads", "<f8"), ("read_share", "<f8"), ("copy_share", "<f8")]
 
 
+class DsbReadAssign(C.Structure):
+    _fields_ = [("ref_ID", C.c_uint32), ("n_cand", C.c_uint32), ("posterior", C.c_double)]
+
+
+DSB_ASSIGN_NONE = 0xffffffff
+ASSIGN_DTYPE = [("ref_ID", "<u4"), ("n_cand", "<u4"), ("posterior", "<f8")]
+
+
 class DsbReadLca(C.Structure):
     _fields_ = [("taxid", C.c_uint32), ("score", C.c_uint32), ("n_pass", C.c_uint32), ("depth", C.c_uint16), ("flags", C.c_uint8), ("pad", C.c_uint8)]
 
@@ -121,6 +129,7 @@ EXPORTS = ["dsb_index_open", "dsb_index_close", "dsb_index_n_ref", "dsb_index_re
            "dsb_ctx_enable_coverage", "dsb_ctx_reset_coverage", "dsb_ctx_coverage", "dsb_multi_enable_coverage", "dsb_multi_coverage",
            "dsb_coverage_format", "dsb_ctx_enable_abundance", "dsb_ctx_reset_abundance", "dsb_ctx_abundance", "dsb_multi_enable_abundance",
            "dsb_multi_abundance", "dsb_abundance_format",
+           "dsb_ctx_set_batch_ordinal", "dsb_ctx_abundance_assign", "dsb_multi_abundance_assign", "dsb_format_assign",
            "dsb_ctx_enable_lca", "dsb_ctx_reset_lca", "dsb_batch_lca", "dsb_ctx_lca_counts", "dsb_multi_enable_lca", "dsb_multi_lca",
            "dsb_multi_lca_counts", "dsb_taxnames_load", "dsb_taxnames_close", "dsb_format_kraken", "dsb_lca_report_format"]
 
@@ -203,6 +212,10 @@ def lib():
     L.dsb_multi_enable_abundance.argtypes = [C.c_void_p, C.c_int, C.c_uint32]
     L.dsb_multi_abundance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.dsb_abundance_format.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]; L.dsb_abundance_format.restype = C.c_long
+    L.dsb_ctx_set_batch_ordinal.argtypes = [C.c_void_p, C.c_uint64]
+    L.dsb_ctx_abundance_assign.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.dsb_multi_abundance_assign.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.dsb_format_assign.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]; L.dsb_format_assign.restype = C.c_long
     L.dsb_ctx_enable_lca.argtypes = [C.c_void_p, C.c_int, C.c_uint32]
     L.dsb_ctx_reset_lca.argtypes = [C.c_void_p]
     L.dsb_batch_lca.argtypes = [C.c_void_p, C.POINTER(C.POINTER(DsbReadLca))]
@@ -440,6 +453,18 @@ class Ctx:
         """EM over everything since enable / reset: (numpy structured array of n_ref rows, ABUNDANCE_DTYPE; summary dict)"""
         return _abundance(lib().dsb_ctx_abundance, self.h, self.index.n_ref, max_iter, tol, "dsb_ctx_abundance")
 
+    def set_batch_ordinal(self, first):
+        """read i of the batch staged in the selected slot is read first + i of the input (abundance_assign's order); holds for that
+        slot's next run() / classify() alone.  Not set: the reads this context has collected since enable / reset."""
+        rc = lib().dsb_ctx_set_batch_ordinal(self.h, int(first))
+        if rc != 0:
+            raise DsbError(rc, "dsb_ctx_set_batch_ordinal")
+
+    def abundance_assign(self, max_iter=10000, tol=0.01):
+        """abundance(), and each read assigned to one reference by its EM posterior: (ab, summary, records) -- records in input
+        order (ASSIGN_DTYPE: ref_ID, DSB_ASSIGN_NONE for an unclassified read; n_cand; posterior)"""
+        return _abundance_assign(lib().dsb_ctx_abundance_assign, self.h, self.index.n_ref, max_iter, tol, "dsb_ctx_abundance_assign")
+
     def enable_lca(self, on=True, min_frac=0.95):
         """per-read classification by the LCA of the near-best hits from now on (needs a Taxonomy attached), or off (freed).  min_frac: a
         hit takes part when its AS is at least min_frac x the read's best AS (0 < min_frac <= 1, in steps of 0.001)"""
@@ -552,6 +577,10 @@ class Multi:
         """Ctx.abundance over the contexts' reads together"""
         return _abundance(lib().dsb_multi_abundance, self.h, self.index.n_ref, max_iter, tol, "dsb_multi_abundance")
 
+    def abundance_assign(self, max_iter=10000, tol=0.01):
+        """Ctx.abundance_assign over the contexts' reads together, in the input order of the classify() calls"""
+        return _abundance_assign(lib().dsb_multi_abundance_assign, self.h, self.index.n_ref, max_iter, tol, "dsb_multi_abundance_assign")
+
     def enable_lca(self, on=True, min_frac=0.95):
         rc = lib().dsb_multi_enable_lca(self.h, 1 if on else 0, _permille(min_frac) if on else 0)
         if rc != 0:
@@ -625,6 +654,42 @@ def _abundance(fn, h, n_ref, max_iter, tol, what):
     if rc != 0:
         raise DsbError(rc, what)
     return out, {f: getattr(s, f) for f in SUMMARY_FIELDS}
+
+
+def _abundance_assign(fn, h, n_ref, max_iter, tol, what):
+    import numpy as np
+    out = np.zeros(n_ref, dtype=ABUNDANCE_DTYPE)
+    s = DsbAbundanceSummary()
+    o = DsbEmOpts(int(max_iter), 0, float(tol))
+    n = C.c_size_t(0)
+    rc = fn(h, C.byref(o), None, None, None, 0, C.byref(n))        # (count)
+    if rc != 0:
+        raise DsbError(rc, what)
+    recs = np.zeros(n.value, dtype=ASSIGN_DTYPE)
+    rc = fn(h, C.byref(o), out.ctypes.data_as(C.c_void_p), C.byref(s), recs.ctypes.data_as(C.c_void_p), max(n.value, 1), C.byref(n))
+    if rc != 0:
+        raise DsbError(rc, what)
+    return out, {f: getattr(s, f) for f in SUMMARY_FIELDS}, recs
+
+
+def format_assign(index, reads, records):
+    """dsb_format_assign over the reads of a run: one line (bytes) per read of make_reads()'s array and abundance_assign()'s records"""
+    import numpy as np
+    records = np.ascontiguousarray(records, dtype=ASSIGN_DTYPE)
+    if len(records) != len(reads):
+        raise ValueError("format_assign: %d records for %d reads" % (len(records), len(reads)))
+    out = []
+    for i in range(len(reads)):
+        cap = 512
+        while True:
+            buf = C.create_string_buffer(cap)
+            n = lib().dsb_format_assign(index.h, C.byref(reads[i]), records[i:i + 1].ctypes.data_as(C.c_void_p), buf, cap)
+            if n >= 0:
+                out.append(buf.raw[:n]); break
+            if records[i]["ref_ID"] != DSB_ASSIGN_NONE and records[i]["ref_ID"] >= index.n_ref:
+                raise ValueError("format_assign: record %d names reference %d of %d" % (i, records[i]["ref_ID"], index.n_ref))
+            cap *= 4
+    return b"".join(out)
 
 
 def format_abundance(index, ab, summary):

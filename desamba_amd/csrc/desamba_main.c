@@ -57,6 +57,7 @@ typedef struct {
 	size_t bytes;                                     /* text the batch was parsed from */
 	uint32_t hist_before;                             /* longest read of the run before this batch */
 	long seqno; double t_parsed;
+	uint64_t first;                                   /* reads of the run before this batch, over all input files (--abundance-reads: the batch's ordinal) */
 	void **own; int n_own, cap_own;                   /* malloc'd blocks the reads point into: names, records joined across blocks */
 	gzbuf_t **gzb; int n_gzb, cap_gzb;                /* inflated blocks the reads point into */
 	dsb_read_result *rr; dsb_hit *hits; size_t cap_rr, cap_hits, n_hits;
@@ -135,6 +136,9 @@ typedef struct {
 	dsb_taxonomy *tx; dsb_report *rep; FILE *rep_out[2];
 	/* --kraken-out / --kraken-report: LCA classification on; the per-read lines are written by the writer in input order */
 	int lca_on; FILE *kr_out;
+	/* --abundance-reads: each batch runs under the input index of its first read, and the writer keeps every read's
+	 * QNAME, NUL-terminated, in input order, for the lines written when the run ends */
+	int keep_names; char *qnames; size_t qnames_len, qnames_cap;
 } app_t;
 
 /* ================================================================ gzip input: inflate ahead of the parser ==========
@@ -502,7 +506,7 @@ static size_t parse_wave(app_t *a, batch_t *b, char *t, size_t pos, size_t soft_
 static int is_gzip(int fd);
 static void batch_release(app_t *a, batch_t *b);
 /* ---------------------------------------------------------------- the reader */
-typedef struct { app_t *a; long seqno; uint32_t hist; batch_t *b; int ramp; } rd_t;   /* ramp: the current batch closes at 1 / 2^ramp of the thresholds */
+typedef struct { app_t *a; long seqno; uint32_t hist; batch_t *b; int ramp; uint64_t n_reads; } rd_t;   /* ramp: the current batch closes at 1 / 2^ramp of the thresholds */
 static int batch_full(const rd_t *r)
 {
 	const app_t *a = r->a; const batch_t *b = r->b;
@@ -523,6 +527,7 @@ static void rd_close_batch(rd_t *r)
 {
 	if (!r->b) return;
 	r->b->t_parsed = now();
+	r->b->first = r->n_reads; r->n_reads += r->b->n;           /* (batches close in the order of their sequence numbers) */
 	q_push(&r->a->parsed_q, r->b);                         /* empty batches keep the sequence numbers dense */
 	r->b = NULL;
 }
@@ -680,7 +685,7 @@ static void *reader_main(void *arg)
 	app_t *a = arg;
 	/* max_read_l (src/cly.c:2958) lives in the per-thread buffers that classify_main allocates once, before the loop
 	 * over the input files (src/cly_mt.c:538-556), and is never reset: the prefix maximum runs over ALL files */
-	rd_t r = { a, 0, 0, NULL, 0 };
+	rd_t r = { a, 0, 0, NULL, 0, 0 };
 	const int nf = a->argc - a->first_file;
 	inflater_t *inf = calloc((size_t)(nf > 0 ? nf : 1), sizeof *inf);
 	int *fds = xmalloc((size_t)(nf > 0 ? nf : 1) * sizeof *fds); size_t *sizes = xmalloc((size_t)(nf > 0 ? nf : 1) * sizeof *sizes);
@@ -740,6 +745,7 @@ static void *gpu_main(void *arg)
 			dsb_ctx_set_history(ctx, b->hist_before);
 			rc = dsb_batch_upload(ctx, b->reads, b->n);
 			t1 = now();
+			if (!rc && a->keep_names) rc = dsb_ctx_set_batch_ordinal(ctx, b->first);
 			if (!rc) rc = dsb_batch_run(ctx);
 			t2 = now();
 			if (!rc || rc == DSB_ECAP) rc = dsb_batch_fetch(ctx, &res);
@@ -840,6 +846,12 @@ static void *writer_main(void *arg)
 				if (fwrite(kb, 1, (size_t)w, a->kr_out) != (size_t)w) die("[classify] cannot write the per-read classifications");
 			}
 		}
+		if (a->keep_names)
+			for (size_t i = 0; i < b->n; i++) {
+				const size_t l = strlen(b->reads[i].name) + 1;
+				if (a->qnames_len + l > a->qnames_cap) { a->qnames_cap = (a->qnames_len + l) * 2 + 4096; a->qnames = xrealloc(a->qnames, a->qnames_cap); }
+				memcpy(a->qnames + a->qnames_len, b->reads[i].name, l); a->qnames_len += l;
+			}
 		if (a->trace) fprintf(stderr, "[writer] batch %ld written at %.3f s\n", b->seqno, now() - a->t0);
 		a->total += b->n;
 		next++;
@@ -870,6 +882,9 @@ static void usage(void)
 	fprintf(stderr, "    --coverage FILE  write the coverage of every reference the run touched into FILE (columns of `samtools coverage`)\n");
 	fprintf(stderr, "    --abundance FILE  write the reads and shares per reference, estimated by EM over each read's near-best references, into FILE\n");
 	fprintf(stderr, "    --abundance-min-frac F  a read's candidates: references whose AS is at least F x its best AS, 0 < F <= 1 [0.95]\n");
+	fprintf(stderr, "    --abundance-reads FILE  assign each read to the candidate reference with the largest EM posterior and write, when the run ends, one\n");
+	fprintf(stderr, "                     line per read in input order into FILE: read name, reference, taxid, number of candidates, posterior.  Turns the\n");
+	fprintf(stderr, "                     estimate on (with or without --abundance) and keeps every read's name in memory until the run ends\n");
 	fprintf(stderr, "    --kraken-out FILE  classify each read by the lowest common ancestor of its near-best hits (needs --taxonomy) and write Kraken's\n");
 	fprintf(stderr, "                     per-read lines into FILE: C|U, read name, taxid, read length, then <best AS>:<near-best hits> (Kraken\n");
 	fprintf(stderr, "                     puts its k-mer string in that fifth column; the first four are Kraken's)\n");
@@ -945,8 +960,9 @@ static int classify_main(int argc, char **argv)
 	                                              {"coverage", required_argument, NULL, 4}, {"abundance", required_argument, NULL, 5},
 	                                              {"abundance-min-frac", required_argument, NULL, 6}, {"kraken-out", required_argument, NULL, 7},
 	                                              {"kraken-report", required_argument, NULL, 8}, {"names", required_argument, NULL, 9},
-	                                              {"lca-min-frac", required_argument, NULL, 10}, {NULL, 0, NULL, 0}};
-	const char *tax_path = NULL, *rep_path[2] = {NULL, NULL}, *cov_path = NULL, *ab_path = NULL, *kr_path = NULL, *krep_path = NULL, *names_path = NULL;
+	                                              {"lca-min-frac", required_argument, NULL, 10}, {"abundance-reads", required_argument, NULL, 11},
+	                                              {NULL, 0, NULL, 0}};
+	const char *tax_path = NULL, *rep_path[2] = {NULL, NULL}, *cov_path = NULL, *ab_path = NULL, *kr_path = NULL, *krep_path = NULL, *names_path = NULL, *abr_path = NULL;
 	uint32_t ab_permille = 950, lca_permille = 950; int lca_frac_set = 0;
 	while ((c = getopt_long(argc, argv, "ht:l:r:f:o:s:g:", long_opts, NULL)) >= 0) {
 		if (c == 'h') { usage(); return 0; }
@@ -967,6 +983,8 @@ static int classify_main(int argc, char **argv)
 			if (e == optarg || *e || !(f > 0 && f <= 1) || f * 1000 + 0.5 < 1) die("[classify] --lca-min-frac takes a number F with 0 < F <= 1 (steps of 0.001)");
 			lca_permille = (uint32_t)(f * 1000 + 0.5); lca_frac_set = 1;
 		}
+		else if (c == 11) abr_path = optarg;
+		else if (c == '?' && optopt == 11) die("[classify] --abundance-reads takes a file name");   /* (last on the line: getopt_long found no argument) */
 		else if (c == 't') { /* thread count: accepted for compatibility, unused */ }
 		else if (c == 'l') a.o.L_min_matching = atoi(optarg);
 		else if (c == 'r') a.o.max_sec_N = atoi(optarg);
@@ -1019,6 +1037,9 @@ static int classify_main(int argc, char **argv)
 	if (cov_path && !(cov_out = fopen(cov_path, "w"))) { fprintf(stderr, "[xopen] fail to open file '%s'\n", cov_path); exit(1); }
 	FILE *ab_out = NULL;
 	if (ab_path && !(ab_out = fopen(ab_path, "w"))) { fprintf(stderr, "[xopen] fail to open file '%s'\n", ab_path); exit(1); }
+	FILE *abr_out = NULL;
+	if (abr_path && !(abr_out = fopen(abr_path, "w"))) { fprintf(stderr, "[xopen] fail to open file '%s'\n", abr_path); exit(1); }
+	a.keep_names = abr_out != NULL;
 	app_defaults(&a);
 	setvbuf(a.out, NULL, _IOFBF, 8 << 20);
 
@@ -1035,7 +1056,7 @@ static int classify_main(int argc, char **argv)
 	for (int k = 0; k < a.n_ctx; k++) a.ctx[k] = dsb_multi_ctx(a.multi, k);
 	if ((a.rep || a.lca_on) && (rc = dsb_multi_set_taxonomy(a.multi, a.tx))) { fprintf(stderr, "\n[dsb_ctx_set_taxonomy] %s\n", dsb_strerror(rc)); exit(1); }
 	if (cov_out && (rc = dsb_multi_enable_coverage(a.multi, 1))) { fprintf(stderr, "\n[dsb_ctx_enable_coverage] %s\n", dsb_strerror(rc)); exit(1); }
-	if (ab_out && (rc = dsb_multi_enable_abundance(a.multi, 1, ab_permille))) { fprintf(stderr, "\n[dsb_ctx_enable_abundance] %s\n", dsb_strerror(rc)); exit(1); }
+	if ((ab_out || abr_out) && (rc = dsb_multi_enable_abundance(a.multi, 1, ab_permille))) { fprintf(stderr, "\n[dsb_ctx_enable_abundance] %s\n", dsb_strerror(rc)); exit(1); }
 	if (a.lca_on && (rc = dsb_multi_enable_lca(a.multi, 1, lca_permille))) { fprintf(stderr, "\n[dsb_ctx_enable_lca] %s\n", dsb_strerror(rc)); exit(1); }
 	double t0 = now(), cpu0 = cputime(); a.t0 = t0;
 	a.thr0 = a.trace ? throttled_usec() : -1;
@@ -1074,19 +1095,51 @@ static int classify_main(int argc, char **argv)
 		if (fwrite(buf, 1, (size_t)w, cov_out) != (size_t)w || fclose(cov_out)) die("[classify] cannot write the coverage table");
 		free(buf); free(cov);
 	}
-	if (ab_out) {
-		/* --abundance: the EM estimate over the whole run's candidate sets, the contexts' sets together */
+	if (ab_out || abr_out) {
+		/* --abundance / --abundance-reads: the EM estimate over the whole run's candidate sets, the contexts' sets together; one solve
+		 * serves both files */
 		const size_t n_ref = (size_t)dsb_index_n_ref(a.idx);
 		dsb_ref_abundance *ab = xrealloc(NULL, (n_ref ? n_ref : 1) * sizeof *ab);
 		dsb_abundance_summary sum;
+		dsb_read_assign *recs = NULL; size_t n_recs = 0; unsigned long n_low = 0;
 		const double ta = now();
-		if ((rc = dsb_multi_abundance(a.multi, NULL, ab, &sum))) { fprintf(stderr, "[dsb_multi_abundance] %s\n", dsb_strerror(rc)); exit(1); }
-		fprintf(stderr, "[classify] abundance: %llu classified reads, %llu classes, %u EM iterations (%s), %.1f ms\n", (unsigned long long)sum.classified,
+		if (abr_out) {
+			if ((rc = dsb_multi_abundance_assign(a.multi, NULL, NULL, NULL, NULL, 0, &n_recs))) { fprintf(stderr, "[dsb_multi_abundance_assign] %s\n", dsb_strerror(rc)); exit(1); }
+			if (n_recs > a.total) die("[classify] --abundance-reads: more per-read records than reads");
+			recs = xrealloc(NULL, (n_recs ? n_recs : 1) * sizeof *recs);
+			if ((rc = dsb_multi_abundance_assign(a.multi, NULL, ab, &sum, recs, n_recs ? n_recs : 1, &n_recs))) { fprintf(stderr, "[dsb_multi_abundance_assign] %s\n", dsb_strerror(rc)); exit(1); }
+			for (size_t i = 0; i < n_recs; i++) n_low += recs[i].ref_ID != DSB_ASSIGN_NONE && recs[i].posterior < 0.5;
+		}
+		else if ((rc = dsb_multi_abundance(a.multi, NULL, ab, &sum))) { fprintf(stderr, "[dsb_multi_abundance] %s\n", dsb_strerror(rc)); exit(1); }
+		fprintf(stderr, "[classify] abundance: %llu classified reads, %llu classes, %u EM iterations (%s), %.1f ms", (unsigned long long)sum.classified,
 		        (unsigned long long)sum.classes, sum.iterations, sum.converged ? "converged" : "max_iter reached", 1e3 * (now() - ta));
-		size_t cap = 1 << 16; char *buf = NULL; long w;
-		do { cap *= 4; buf = xrealloc(buf, cap); w = dsb_abundance_format(a.idx, ab, &sum, buf, cap); } while (w < 0);
-		if (fwrite(buf, 1, (size_t)w, ab_out) != (size_t)w || fclose(ab_out)) die("[classify] cannot write the abundance table");
-		free(buf); free(ab);
+		if (abr_out) fprintf(stderr, "; %lu reads assigned with posterior < 0.5", n_low);
+		fprintf(stderr, "\n");
+		if (ab_out) {
+			size_t cap = 1 << 16; char *buf = NULL; long w;
+			do { cap *= 4; buf = xrealloc(buf, cap); w = dsb_abundance_format(a.idx, ab, &sum, buf, cap); } while (w < 0);
+			if (fwrite(buf, 1, (size_t)w, ab_out) != (size_t)w || fclose(ab_out)) die("[classify] cannot write the abundance table");
+			free(buf);
+		}
+		if (abr_out) {
+			/* one line per input read, in input order: the names the writer kept, the records by ordinal (reads behind the last batch
+			 * that held any -- none: every batch with reads is logged -- would be unclassified) */
+			const dsb_read_assign none = {DSB_ASSIGN_NONE, 0, 0.0};
+			size_t cap = 4096, off = 0; char *buf = xmalloc(cap);
+			setvbuf(abr_out, NULL, _IOFBF, 1 << 20);
+			for (size_t i = 0; i < (size_t)a.total; i++) {
+				dsb_read rd; memset(&rd, 0, sizeof rd); rd.name = a.qnames + off;
+				const size_t l = strlen(rd.name);
+				if (l + 4096 > cap) { cap = (l + 4096) * 2; buf = xrealloc(buf, cap); }       /* (reference names are far below 4 KB) */
+				long w;
+				while ((w = dsb_format_assign(a.idx, &rd, i < n_recs ? &recs[i] : &none, buf, cap)) < 0) { if (cap > ((size_t)1 << 30)) die("[dsb_format_assign] cannot format a record"); cap *= 4; buf = xrealloc(buf, cap); }
+				if (fwrite(buf, 1, (size_t)w, abr_out) != (size_t)w) die("[classify] cannot write the per-read assignments");
+				off += l + 1;
+			}
+			if (fclose(abr_out)) die("[classify] cannot write the per-read assignments");
+			free(buf); free(recs); free(a.qnames);
+		}
+		free(ab);
 	}
 	if (a.kr_out && fclose(a.kr_out)) die("[classify] cannot write the per-read classifications");
 	if (krep_out) {

@@ -22,6 +22,7 @@ struct InSlot {
 	bool ragged = false;
 	uint64_t upload_bytes = 0;     // what the sequences of this batch took over PCIe
 	bool packed = false;           // d_ascii holds 2-bit packed sequences (dsb_batch_upload's gather), not text
+	bool ord_set = false; uint64_t ord_first = 0;   // dsb_ctx_set_batch_ordinal: read i of the staged batch has ordinal ord_first + i (taken by the slot's next run)
 };
 
 // pinned staging of dsb_batch_upload: one per gather thread, two chunks each (one is filled while the other is on its way)

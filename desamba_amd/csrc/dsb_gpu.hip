@@ -1518,6 +1518,7 @@ static int batch_run_locked(dsb_ctx *c, std::unique_lock<std::mutex> *turn)
 	HIPCHK(hipSetDevice(c->device));
 	InSlot &s = c->in[c->cur];
 	size_t n = s.n_reads;
+	const bool ord_set = s.ord_set; s.ord_set = false;         // (dsb_ctx_set_batch_ordinal holds for this run alone)
 	memset(&c->timing, 0, sizeof c->timing);
 	c->timing.upload_bytes = s.upload_bytes;
 	c->taxa.run = c->taxa.tx != nullptr && n == 0; c->taxa.done = false;
@@ -1693,7 +1694,7 @@ static int batch_run_locked(dsb_ctx *c, std::unique_lock<std::mutex> *turn)
 		}
 	}
 	// the run reductions (dsb_reductions.hip), after every classify launch of the batch
-	const DsbBatchView hits = {c->stream, c->d_rout, c->d_hout, c->d_counters, c->cap_hout, s.d_rd, (uint32_t)n};
+	const DsbBatchView hits = {c->stream, c->d_rout, c->d_hout, c->d_counters, c->cap_hout, s.d_rd, (uint32_t)n, ord_set, s.ord_first};
 	if (int rc = reductions_run(c, hits)) return rc;
 	if (dbg) {
 		static const char *nm[10] = {"seed_vector", "fast_classify", "resolve_tree", "slow+resolve", "hash_build", "sdp_middle", "sdp_right", "sdp_left", "sort/filter", "primary"};
@@ -1950,6 +1951,9 @@ extern "C" int dsb_multi_classify_batch(dsb_multi *m, const dsb_read *reads, siz
 	std::vector<std::vector<dsb_hit>> chunk_hits(nc);
 	std::vector<int> rcs(W, DSB_OK);
 	const uint32_t hist0 = m->hist;
+	// abundance on: each piece's reads are logged under their input index, counted over all calls since enable / reset
+	uint64_t ord0 = 0;
+	for (const dsb_ctx *c : m->ctx) ord0 += c->em.reads;
 	std::atomic<size_t> next_chunk(0);
 	m->last_calls.assign((size_t)W, 0);
 	auto worker = [&](int w) {
@@ -1959,6 +1963,7 @@ extern "C" int dsb_multi_classify_batch(dsb_multi *m, const dsb_read *reads, siz
 			if (k >= nc) break;
 			const dsb_chunk &ch = plan[k];
 			dsb_ctx_set_history(c, ch.hist_max_before > hist0 ? ch.hist_max_before : hist0);
+			if (c->em.d_cnt) dsb_ctx_set_batch_ordinal(c, ord0 + ch.start);
 			dsb_result r;
 			int rc = dsb_classify_batch(c, reads + ch.start, (size_t)(ch.end - ch.start), &r);
 			m->last_calls[(size_t)w]++;

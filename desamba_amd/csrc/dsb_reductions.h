@@ -26,10 +26,13 @@ struct DsbCover {
 };
 
 // abundance: the run's candidate sets (DsbEmSet + their elements, grown geometrically between batches), the store's counters,
-// and the reads the batches held; one k_em_collect launch per batch
+// and the reads the batches held; one k_em_collect launch per batch.  log: one entry per k_em_collect launch -- the
+// batch's n records start at store position base, and record i is the read of ordinal first + i (dsb_ctx_set_batch_ordinal)
+struct DsbEmLog { uint64_t base, first, n; };
 struct DsbEmStore {
 	DsbEmSet *d_sets = nullptr; uint32_t *d_elems = nullptr; unsigned long long *d_cnt = nullptr;
 	size_t cap_sets = 0, cap_elems = 0, used_sets = 0, used_elems = 0; uint64_t reads = 0; uint32_t permille = 0;
+	std::vector<DsbEmLog> log;
 };
 
 // LCA classification: a depth table beside DsbTaxa's parent table (u16, DSB_DEPTH_UNROOTED for an unrooted taxid), the
@@ -48,6 +51,7 @@ struct DsbBatchView {
 	hipStream_t st;
 	const DsbReadOut *rout; const DsbHitOut *hout; const unsigned int *counters; size_t cap_hout;
 	const DsbReadDesc *rd; uint32_t n;
+	bool ord_set; uint64_t ord_first;             // dsb_ctx_set_batch_ordinal was called for this batch / with this ordinal
 };
 
 struct dsb_ctx;

@@ -1,5 +1,5 @@
 // The run reductions of classify (dsb_reductions.h): per-read taxa, per-reference coverage and per-reference
-// abundance by EM, per-read LCA classification -- their kernels, the launches after a batch's last classify launch (reductions_run), the
+// abundance by EM with each read's assignment by its posterior, per-read LCA classification -- their kernels, the launches after a batch's last classify launch (reductions_run), the
 // host side of each, and their merges over the contexts of a dsb_multi.
 #include <algorithm>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -341,6 +341,41 @@ __global__ void __launch_bounds__(256) k_em_rebase(DsbEmSet *sets, uint32_t n, u
 	if (i < n) sets[i].off += base;
 }
 
+// ---- per-read assignment by the EM posterior (dsb_*_abundance_assign) ----
+// After the solve, one thread per class k (k_em_class's launch shape, and its walk: the class's references in ascending ref_ID):
+// w_s = a_s / L_s from the final shares, d = their sum in that order (k_em_class's d_k), the reference with the largest w -- the
+// strict comparison leaves equal weights to the smallest ref_ID -- and posterior = w_ref / d (d == 0, every share underflowed: the
+// first reference and 0).  Every read of the class gets this record.
+__global__ void __launch_bounds__(256) k_em_assign_class(const uint32_t *__restrict__ cref, const uint32_t *__restrict__ coff, uint32_t K,
+                                                         const double *__restrict__ a, const double *__restrict__ L, dsb_read_assign *__restrict__ crec)
+{
+	const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+	if (k >= K) return;
+	const uint32_t q0 = coff[k], q1 = coff[k + 1];
+	double d = 0.0, best = -1.0; uint32_t ref = DSB_ASSIGN_NONE;
+	for (uint32_t q = q0; q < q1; q++) {
+		const uint32_t s = cref[q];
+		const double w = a[s] / L[s];
+		d += w;
+		if (w > best) { best = w; ref = s; }
+	}
+	dsb_read_assign o; o.ref_ID = ref; o.n_cand = q1 - q0; o.posterior = d > 0.0 ? best / d : 0.0;
+	crec[k] = o;
+}
+
+// One lane per store record: sorted position p holds record order[p], of class cls[p] - 1; the empty records (unclassified reads)
+// are sorted in front of every class, cls 0 (p < start[0]), and get the "none" record.  order is a permutation: plain stores.
+__global__ void __launch_bounds__(256) k_em_assign_read(const uint32_t *__restrict__ order, const uint32_t *__restrict__ cls, uint32_t n,
+                                                        const dsb_read_assign *__restrict__ crec, dsb_read_assign *__restrict__ out)
+{
+	const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+	if (p >= n) return;
+	const uint32_t k = cls[p];
+	dsb_read_assign o; o.ref_ID = DSB_ASSIGN_NONE; o.n_cand = 0; o.posterior = 0.0;
+	if (k) o = crec[k - 1];
+	out[order[p]] = o;
+}
+
 // ---- per-read LCA classification (dsb_ctx_enable_lca) ----
 // The lowest common ancestor of two rooted taxids, 0 standing for "nothing yet" (the neutral value: taxid 0 is never rooted).  The
 // deeper node is lifted to the other's depth, then both are lifted until they meet -- at taxid 1 at the latest, since both chains
@@ -633,7 +668,7 @@ extern "C" int dsb_ctx_reset_abundance(dsb_ctx *c)
 	HIPCHK(hipSetDevice(c->device));
 	HIPCHK(hipMemsetAsync(c->em.d_cnt, 0, DSB_EM_CNT * sizeof(unsigned long long), c->stream));
 	HIPCHK(hipStreamSynchronize(c->stream));
-	c->em.reads = 0;
+	c->em.reads = 0; c->em.log.clear();
 	return DSB_OK;
 }
 
@@ -669,9 +704,13 @@ static int em_opts(const dsb_em_opts *o, dsb_em_opts *v)
 //            reference's classes stay in class order; the row offsets by binary search.
 //   EM:      k_em_class + k_em_ref per iteration, EM_ITER_BLOCK iterations per host round trip; the device's done word makes the
 //            result the state after the first iteration that met tol, whatever the block.
+//   assign:  with d_assign (n records, in store order) the two kernels of DESIGN 2.10.1 behind the last iteration, *assigned = they ran
+//            (they do not when no read is classified: every record is then "none", which the caller writes itself)
 static int em_solve(hipStream_t st, const dsb_index *idx, const DsbEmSet *sets, const uint32_t *elems, uint32_t n, uint32_t n_elems, uint64_t reads,
-                    uint32_t permille, const dsb_em_opts &o, dsb_ref_abundance *out, dsb_abundance_summary *sum)
+                    uint32_t permille, const dsb_em_opts &o, dsb_ref_abundance *out, dsb_abundance_summary *sum, dsb_read_assign *d_assign = nullptr,
+                    bool *assigned = nullptr)
 {
+	if (assigned) *assigned = false;
 	const uint32_t n_ref = (uint32_t)dsb_index_n_ref(idx);
 	memset(out, 0, (size_t)n_ref * sizeof *out); memset(sum, 0, sizeof *sum);
 	sum->reads = reads; sum->min_permille = permille; sum->converged = 1;
@@ -770,6 +809,15 @@ static int em_solve(hipStream_t st, const dsb_index *idx, const DsbEmSet *sets, 
 		if (hs.done) break;
 	}
 	const uint32_t iters = hs.done ? hs.iters : o.max_iter;
+	if (d_assign) {
+		// the per-read records, from the shares the table below is made of (a[iters & 1]); done by the wait that follows
+		dsb_read_assign *crec = T.get<dsb_read_assign>(K);
+		if (!crec) return DSB_ENOMEM;
+		hipLaunchKernelGGL(k_em_assign_class, gk, b256, 0, st, (const uint32_t *)cref, (const uint32_t *)coff, K, (const double *)a[iters & 1], (const double *)L, crec);
+		hipLaunchKernelGGL(k_em_assign_read, gn, b256, 0, st, (const uint32_t *)order, (const uint32_t *)cls, n, (const dsb_read_assign *)crec, d_assign);
+		EMCK(hipGetLastError());
+		if (assigned) *assigned = true;
+	}
 	double chg = 0.0;
 	memcpy(&chg, &hs.chg[(iters - 1) & 1], 8);
 	std::vector<double> ha(n_ref); std::vector<unsigned long long> hnr(n_ref), hur(n_ref);
@@ -807,6 +855,66 @@ extern "C" int dsb_ctx_abundance(dsb_ctx *c, const dsb_em_opts *opts, dsb_ref_ab
 	int rc = em_counts(c, cnt);
 	if (rc) return rc;
 	return em_solve(c->stream, c->idx, c->em.d_sets, c->em.d_elems, (uint32_t)cnt[0], (uint32_t)cnt[1], c->em.reads, c->em.permille, o, out, summary);
+}
+
+// ---- per-read assignment: the ordinal log and the delivery in input order ----
+extern "C" int dsb_ctx_set_batch_ordinal(dsb_ctx *c, uint64_t first)
+{
+	if (!c) return DSB_EINVAL;
+	InSlot &s = c->in[c->cur];
+	s.ord_set = true; s.ord_first = first;
+	return DSB_OK;
+}
+
+// a context's log and where its records start in the store that was solved (dsb_multi: the contexts' stores one after the other)
+struct EmPiece { const std::vector<DsbEmLog> *log; uint64_t off; };
+
+// 1 + the largest ordinal logged, or 0
+static uint64_t assign_count(const std::vector<EmPiece> &pc)
+{
+	uint64_t n = 0;
+	for (const EmPiece &p : pc) for (const DsbEmLog &e : *p.log) if (e.n) n = std::max(n, e.first + e.n);
+	return n;
+}
+
+// reads[0 .. n_out) = "none", then each logged batch's records, a contiguous run of the store (d_assign, n_store records; nullptr:
+// no read was classified), to reads[first ..): one copy per batch, 16 bytes per read
+static int assign_deliver(hipStream_t st, const dsb_read_assign *d_assign, uint64_t n_store, const std::vector<EmPiece> &pc, dsb_read_assign *reads, uint64_t n_out)
+{
+	dsb_read_assign none; none.ref_ID = DSB_ASSIGN_NONE; none.n_cand = 0; none.posterior = 0.0;
+	std::fill(reads, reads + n_out, none);
+	if (!d_assign) return DSB_OK;
+	for (const EmPiece &p : pc)
+		for (const DsbEmLog &e : *p.log) {
+			if (!e.n) continue;
+			if (p.off + e.base + e.n > n_store || e.first + e.n > n_out) return DSB_ENODEV;     // (cannot happen: the log follows k_em_collect)
+			EMCK(hipMemcpyAsync(reads + e.first, d_assign + p.off + e.base, e.n * sizeof(dsb_read_assign), hipMemcpyDeviceToHost, st));
+		}
+	EMCK(hipStreamSynchronize(st));
+	return DSB_OK;
+}
+
+extern "C" int dsb_ctx_abundance_assign(dsb_ctx *c, const dsb_em_opts *opts, dsb_ref_abundance *out, dsb_abundance_summary *summary, dsb_read_assign *reads,
+                                        size_t cap, size_t *n)
+{
+	dsb_em_opts o;
+	if (!c || !n || !c->em.d_cnt || em_opts(opts, &o)) return DSB_EINVAL;
+	const std::vector<EmPiece> pc = {{&c->em.log, 0}};
+	*n = (size_t)assign_count(pc);
+	if (!reads) return DSB_OK;                                 // (count only)
+	if (!out || !summary) return DSB_EINVAL;
+	if (cap < *n) return DSB_ECAP;
+	HIPCHK(hipSetDevice(c->device));
+	unsigned long long cnt[DSB_EM_CNT];
+	int rc = em_counts(c, cnt);
+	if (rc) return rc;
+	DevScratch T;
+	dsb_read_assign *d_assign = T.get<dsb_read_assign>((size_t)cnt[0]);
+	if (!d_assign) return DSB_ENOMEM;
+	bool ran = false;
+	rc = em_solve(c->stream, c->idx, c->em.d_sets, c->em.d_elems, (uint32_t)cnt[0], (uint32_t)cnt[1], c->em.reads, c->em.permille, o, out, summary, d_assign, &ran);
+	if (rc) return rc;
+	return assign_deliver(c->stream, ran ? d_assign : nullptr, cnt[0], pc, reads, *n);
 }
 
 // ---- per-read LCA classification ----
@@ -943,6 +1051,8 @@ int reductions_run(dsb_ctx *c, const DsbBatchView &b)
 		// hold (a read's set lies in the room of its hits) is made first: the store's counters are read here, where the stream
 		// has already run everything before this batch's second run (ev[3]) and nothing of this batch touched them.
 		if (int rc = em_reserve(c, b.n, b.cap_hout)) return rc;
+		// the ordinal log of DESIGN 2.10.1: where the batch's records lie in the store and which reads of the input they are
+		c->em.log.push_back({(uint64_t)c->em.used_sets, b.ord_set ? b.ord_first : c->em.reads, (uint64_t)b.n});
 		c->em.reads += b.n;
 		hipLaunchKernelGGL(k_em_collect, dim3((b.n + 3) / 4), dim3(256), 0, b.st, DSB_BATCH_HITS(b), b.n, n_ref, c->em.permille,
 		                   c->em.d_sets, c->em.d_elems, c->em.d_cnt, (uint64_t)c->em.used_sets, (uint64_t)c->em.used_elems, (uint64_t)c->em.cap_sets,
@@ -1081,22 +1191,19 @@ extern "C" int dsb_multi_enable_abundance(dsb_multi *m, int on, uint32_t min_per
 // The contexts' stores one after the other on the first context's device (copy_to), each context's element offsets moved
 // behind the elements before it, then the solve of one context.  The classes, their order and every sum depend only on the
 // multiset of sets, so the result is bitwise that of one context.
-extern "C" int dsb_multi_abundance(dsb_multi *m, const dsb_em_opts *opts, dsb_ref_abundance *out, dsb_abundance_summary *summary)
+// reads: nullptr (dsb_multi_abundance), or the n_out per-read records of dsb_multi_abundance_assign
+static int multi_solve(dsb_multi *m, const dsb_em_opts &o, dsb_ref_abundance *out, dsb_abundance_summary *summary, dsb_read_assign *reads, uint64_t n_out)
 {
-	dsb_em_opts o;
-	if (!m || !out || !summary || m->ctx.empty() || em_opts(opts, &o)) return DSB_EINVAL;
 	dsb_ctx *c0 = m->ctx[0];
-	for (dsb_ctx *c : m->ctx) if (!c->em.d_cnt || c->em.permille != c0->em.permille) return DSB_EINVAL;
-	if (m->ctx.size() == 1) return dsb_ctx_abundance(c0, opts, out, summary);
 	std::vector<unsigned long long> ns(m->ctx.size()), ne(m->ctx.size());
-	uint64_t S = 0, E = 0, reads = 0;
+	uint64_t S = 0, E = 0, n_reads = 0;
 	for (size_t i = 0; i < m->ctx.size(); i++) {
 		dsb_ctx *c = m->ctx[i];
 		HIPCHK(hipSetDevice(c->device));
 		unsigned long long cnt[DSB_EM_CNT];
 		int rc = em_counts(c, cnt);
 		if (rc) return rc;
-		ns[i] = cnt[0]; ne[i] = cnt[1]; S += cnt[0]; E += cnt[1]; reads += c->em.reads;
+		ns[i] = cnt[0]; ne[i] = cnt[1]; S += cnt[0]; E += cnt[1]; n_reads += c->em.reads;
 	}
 	if (S > 0xffffffffu || E > 0xffffffffu) return DSB_ENOMEM;
 	HIPCHK(hipSetDevice(c0->device));
@@ -1115,7 +1222,43 @@ extern "C" int dsb_multi_abundance(dsb_multi *m, const dsb_em_opts *opts, dsb_re
 		s0 += ns[i]; e0 += ne[i];
 	}
 	EMCK(hipGetLastError());
-	return em_solve(st, m->idx, sets, elems, (uint32_t)S, (uint32_t)E, reads, c0->em.permille, o, out, summary);
+	if (!reads) return em_solve(st, m->idx, sets, elems, (uint32_t)S, (uint32_t)E, n_reads, c0->em.permille, o, out, summary);
+	dsb_read_assign *d_assign = T.get<dsb_read_assign>(S);
+	if (!d_assign) return DSB_ENOMEM;
+	bool ran = false;
+	int rc = em_solve(st, m->idx, sets, elems, (uint32_t)S, (uint32_t)E, n_reads, c0->em.permille, o, out, summary, d_assign, &ran);
+	if (rc) return rc;
+	std::vector<EmPiece> pc;
+	s0 = 0;
+	for (size_t i = 0; i < m->ctx.size(); i++) { pc.push_back({&m->ctx[i]->em.log, s0}); s0 += ns[i]; }
+	return assign_deliver(st, ran ? d_assign : nullptr, S, pc, reads, n_out);
+}
+
+extern "C" int dsb_multi_abundance(dsb_multi *m, const dsb_em_opts *opts, dsb_ref_abundance *out, dsb_abundance_summary *summary)
+{
+	dsb_em_opts o;
+	if (!m || !out || !summary || m->ctx.empty() || em_opts(opts, &o)) return DSB_EINVAL;
+	dsb_ctx *c0 = m->ctx[0];
+	for (dsb_ctx *c : m->ctx) if (!c->em.d_cnt || c->em.permille != c0->em.permille) return DSB_EINVAL;
+	if (m->ctx.size() == 1) return dsb_ctx_abundance(c0, opts, out, summary);
+	return multi_solve(m, o, out, summary, nullptr, 0);
+}
+
+extern "C" int dsb_multi_abundance_assign(dsb_multi *m, const dsb_em_opts *opts, dsb_ref_abundance *out, dsb_abundance_summary *summary, dsb_read_assign *reads,
+                                          size_t cap, size_t *n)
+{
+	dsb_em_opts o;
+	if (!m || !n || m->ctx.empty() || em_opts(opts, &o)) return DSB_EINVAL;
+	dsb_ctx *c0 = m->ctx[0];
+	for (dsb_ctx *c : m->ctx) if (!c->em.d_cnt || c->em.permille != c0->em.permille) return DSB_EINVAL;
+	if (m->ctx.size() == 1) return dsb_ctx_abundance_assign(c0, opts, out, summary, reads, cap, n);
+	std::vector<EmPiece> pc;
+	for (dsb_ctx *c : m->ctx) pc.push_back({&c->em.log, 0});
+	*n = (size_t)assign_count(pc);
+	if (!reads) return DSB_OK;                                 // (count only)
+	if (!out || !summary) return DSB_EINVAL;
+	if (cap < *n) return DSB_ECAP;
+	return multi_solve(m, o, out, summary, reads, *n);
 }
 
 extern "C" int dsb_multi_enable_lca(dsb_multi *m, int on, uint32_t min_permille)

@@ -408,6 +408,21 @@ extern "C" long dsb_abundance_format(const dsb_index *x, const dsb_ref_abundance
 	return (long)o;
 }
 
+// one read's line of the per-read assignment
+extern "C" long dsb_format_assign(const dsb_index *x, const dsb_read *rd, const dsb_read_assign *a, char *buf, size_t cap)
+{
+	if (!x || !rd || !rd->name || !a || !buf) return -1;
+	int w;
+	if (a->ref_ID == DSB_ASSIGN_NONE) w = snprintf(buf, cap, "%s\t*\t0\t0\t0.000000\n", rd->name);
+	else {
+		if (a->ref_ID >= dsb_index_n_ref(x)) return -1;
+		const char *name = dsb_index_ref_name(x, a->ref_ID);
+		const uint32_t tid = dsb_ref_taxid(name);
+		w = snprintf(buf, cap, "%s\t%s\t%u\t%u\t%.6f\n", rd->name, name, tid == DSB_TID_NONE ? 0u : tid, a->n_cand, a->posterior);
+	}
+	return (w < 0 || (size_t)w >= cap) ? -1 : (long)w;
+}
+
 // ---- names.dmp, Kraken's per-read line and Kraken's report for the LCA classification ----
 extern "C" int dsb_taxnames_load(const char *path, dsb_taxnames **out)
 {

@@ -345,6 +345,32 @@ int  dsb_multi_abundance(dsb_multi *m, const dsb_em_opts *opts, dsb_ref_abundanc
  * formats).  Same return convention as dsb_format_sam. */
 long dsb_abundance_format(const dsb_index *idx, const dsb_ref_abundance *ab, const dsb_abundance_summary *summary, char *buf, size_t cap);
 
+/* ---- each read assigned to one reference by its EM posterior.  With a_r the read_share of the solve, L_r the
+ * reference lengths as doubles (1 for an empty reference) and C a read's candidate set in ascending ref_ID: w_s = a_s / L_s,
+ * d = the sum of w_s over C in that order from 0.0, ref_ID = the s of C with the largest w_s (equal weights: the smallest ref_ID),
+ * posterior = w_ref / d (d == 0, every share underflowed: the smallest ref_ID of C and 0), n_cand = |C|.  A read without a
+ * candidate set: ref_ID DSB_ASSIGN_NONE, n_cand 0, posterior 0.  The record is a function of the read's class alone: reads of one
+ * class get bitwise-equal records, whatever the batch split, input slot, context or run. */
+typedef struct { uint32_t ref_ID;   /* DSB_ASSIGN_NONE: unclassified */
+                 uint32_t n_cand; double posterior; } dsb_read_assign;
+#define DSB_ASSIGN_NONE 0xffffffffu
+/* read i of the batch staged in the selected input slot has ordinal first + i in the records below.  Taken by that slot's next
+ * dsb_batch_run / dsb_classify_batch and forgotten after it.  Not set: the reads this context has collected since
+ * dsb_ctx_enable_abundance / dsb_ctx_reset_abundance, so that a context driven plainly numbers its reads in run order.
+ * dsb_multi_classify_batch numbers each piece by its input index, counted over all calls since enable / reset. */
+int  dsb_ctx_set_batch_ordinal(dsb_ctx *ctx, uint64_t first);
+/* dsb_ctx_abundance, and reads[ordinal] = the record of every read since enable / reset.  *n = 1 + the largest ordinal a batch
+ * covered (0: none); an ordinal below *n that no batch covered gets the "none" record.  reads NULL: *n is set and nothing else is
+ * done (out and summary may be NULL); cap < *n: DSB_ECAP.  out and summary are what dsb_ctx_abundance gives for the same state. */
+int  dsb_ctx_abundance_assign(dsb_ctx *ctx, const dsb_em_opts *opts, dsb_ref_abundance *out, dsb_abundance_summary *summary,
+                              dsb_read_assign *reads, size_t cap, size_t *n);
+int  dsb_multi_abundance_assign(dsb_multi *m, const dsb_em_opts *opts, dsb_ref_abundance *out, dsb_abundance_summary *summary,
+                                dsb_read_assign *reads, size_t cap, size_t *n);
+/* one line per read: QNAME \t rname \t taxid \t n_cand \t posterior (%.6f) \n -- QNAME as dsb_format_sam prints it, taxid the second
+ * '|' field of the reference name (0: none); an unclassified read: QNAME \t * \t 0 \t 0 \t 0.000000.  Return as dsb_format_sam
+ * (-1 also for a ref_ID that is neither DSB_ASSIGN_NONE nor a reference of the index). */
+long dsb_format_assign(const dsb_index *idx, const dsb_read *read, const dsb_read_assign *a, char *buf, size_t cap);
+
 /* ---- per-read classification by the lowest common ancestor (LCA) of the near-best hits, on the GPU.
  * Per read (reads are not joined by name): its hits are those dsb_batch_fetch hands out, whatever max_sec_N is; hits with
  * ref_ID >= n_ref are skipped, and a read with no hit left is unclassified (record all zero).  S_max is the largest AS; a hit
