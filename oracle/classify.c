@@ -46,6 +46,10 @@ typedef struct { int match_len; uint64_t sp, sa_sp; int sa_sp_l; int kmer_index;
 typedef struct { uint64_t *set; int l, m; } spset_t;
 typedef struct { ora_seed_t *seed_v; uint32_t l_seed_v; uint8_t *bin_read; uint64_t *kmer; uint32_t direction, total_score; } sdir_t;
 
+/* what ora_ext_stage records of one sdp_right_M2 / sdp_left_M2: why the loop ended (1 reference end, 2 last_search, 3 empty window, 4 the
+ * window's first node more than 1000 beyond the best, 5 a scored node more than 1000 beyond the best), merges, the list length behind every
+ * sdp_match, and the node list with its scores whenever it is given up (a merge) or the loop ends: seg = pairs (nodes, nodes scored) */
+struct ext_trace { int reason, merges; uint32_t n_win, max_win, *win_n; uint32_t n_seg, max_seg, *seg; uint32_t n_nodes, max_nodes, *nodes; };
 struct ora_ctx {
 	uint8_t *bin_base; uint32_t m_bin; uint8_t *bin_read;
 	uint64_t *kmer_buff; uint32_t m_kmer;
@@ -61,6 +65,7 @@ struct ora_ctx {
 	sdir_t sd[2]; uint32_t read_len;
 	uint64_t cnt[8];      /* P0,P1,OCC,SA,RW,MEMS */
 	uint64_t ref_bases;   /* bases of the 2-bit reference text (U6) */
+	struct ext_trace *xt;  /* ora_ext_stage: how an extension ran (null: not recorded) */
 	uint32_t *gap_nodes; uint32_t n_gap_nodes;   /* ora_gap_stage: match nodes sdp_match produced per gap of sdp_middle_M2 (null: not recorded) */
 	void *sort_tmp; size_t m_sort_tmp;
 };
@@ -924,6 +929,86 @@ static void sdp_match(ora_ctx_t *cx, uint32_t q_bg, uint32_t q_ed, const uint8_t
 	}
 }
 
+/* The predecessor loops of the sparse DP (src/cly.c:2495-2517, 2612-2638, 2759-2783): the score of node ci of the list S from the
+ * nodes in front of it, newest first.  sdp_middle_M2 / sdp_right_M2 / sdp_left_M2 and ora_sdp_dp_stage all call these. */
+static int dp_pred_middle(const sms_t *S, uint32_t ci)
+{
+	const sms_t *c_spd = S + ci;
+	int max_score = c_spd->len;
+	uint32_t max_q = c_spd->q_pos + 6, max_t = c_spd->t_pos + 6;
+	for (int32_t pi = (int32_t)ci - 1; pi >= 0; pi--) {
+		const sms_t *ps = S + pi;
+		int pre_q_ed = ps->q_pos + ps->len + 9 - 1, pre_t_ed = ps->t_pos + ps->len + 9 - 1;
+		if (pre_q_ed > max_q) continue;
+		if (pre_t_ed > max_t) continue;
+		int indel = ps->q_pos - ps->t_pos - (max_q - max_t);
+		int ai = ABSV(indel);
+		if (ai > 200) continue;
+		int ns = ps->score + c_spd->len - (ai >> 3);
+		if (pre_q_ed > c_spd->q_pos || pre_t_ed > c_spd->t_pos) {
+			int oq = pre_q_ed - c_spd->q_pos, ot = pre_t_ed - c_spd->t_pos;
+			ns -= MAXV(oq, ot);
+		}
+		max_score = MAXV(max_score, ns);
+	}
+	return max_score;
+}
+static int dp_pred_right(const sms_t *S, uint32_t ci)
+{
+	const sms_t *c_sms = S + ci;
+	int max_score = c_sms->len;
+	uint32_t max_pre_q = c_sms->q_pos + 6, max_pre_t = c_sms->t_pos + 6;
+	for (int32_t pi = (int32_t)ci - 1; pi >= 0; pi--) {
+		const sms_t *ps = S + pi;
+		int pre_q_ed = ps->q_pos + ps->len + 9 - 1, pre_t_ed = ps->t_pos + ps->len + 9 - 1;
+		if (pre_q_ed > max_pre_q) continue;
+		if (pre_t_ed > max_pre_t) continue;
+		if (ps->t_pos + 600 < max_pre_t) break;
+		int indel = ps->q_pos - ps->t_pos - (max_pre_q - max_pre_t);
+		int ai = ABSV(indel);
+		if (ai > 200) continue;
+		int ns = ps->score + c_sms->len - (ai >> 3);
+		if (pre_q_ed > c_sms->q_pos || pre_t_ed > c_sms->t_pos) {
+			int oq = pre_q_ed - c_sms->q_pos, ot = pre_t_ed - c_sms->t_pos;
+			ns -= MAXV(oq, ot);
+		}
+		max_score = MAXV(max_score, ns);
+	}
+	return max_score;
+}
+static int dp_pred_left(const sms_t *S, uint32_t ci)
+{
+	const sms_t *c_sms = S + ci;
+	int max_score = c_sms->len;
+	uint32_t min_pre_q = c_sms->q_pos + c_sms->len - 6 + 9 - 1, min_pre_t = c_sms->t_pos + c_sms->len - 6 + 9 - 1;
+	for (int32_t pi = (int32_t)ci - 1; pi >= 0; pi--) {
+		const sms_t *ps = S + pi;
+		if (ps->q_pos < min_pre_q) continue;
+		if (ps->t_pos < min_pre_t) continue;
+		if (min_pre_t + 600 < ps->t_pos) break;
+		int indel = ps->q_pos - ps->t_pos - (min_pre_q - min_pre_t);
+		int ai = ABSV(indel);
+		if (ai > 200) continue;
+		int ns = ps->score + c_sms->len - (ai >> 3);
+		if (min_pre_q + 6 > ps->q_pos || min_pre_t + 6 > ps->t_pos) {
+			int oq = min_pre_q + 6 - ps->q_pos, ot = min_pre_t + 6 - ps->t_pos;
+			ns -= MAXV(oq, ot);
+		}
+		max_score = MAXV(max_score, ns);
+	}
+	return max_score;
+}
+/* the sparse DP on a bare node list (tests/test_stage_dp.py): nodes = rows of 4 (t_pos, q_pos, len, score), node 0 carries its score;
+ * mode 0 middle, 1 right, 2 left -> scores[i] of every node */
+void ora_sdp_dp_stage(int mode, const uint32_t *nodes, uint32_t n, int32_t *scores)
+{
+	sms_t *S = (sms_t *)malloc((n ? n : 1) * sizeof *S);
+	for (uint32_t i = 0; i < n; i++) { S[i].t_pos = nodes[4 * i]; S[i].q_pos = nodes[4 * i + 1]; S[i].len = nodes[4 * i + 2]; S[i].score = i ? 0 : nodes[3]; }
+	for (uint32_t ci = 1; ci < n; ci++) S[ci].score = mode == 0 ? dp_pred_middle(S, ci) : mode == 1 ? dp_pred_right(S, ci) : dp_pred_left(S, ci);
+	for (uint32_t i = 0; i < n; i++) scores[i] = (int32_t)S[i].score;
+	free(S);
+}
+
 /* sdp_middle_M2, src/cly.c:2444-2530 */
 static int sdp_middle_M2(ora_ctx_t *cx, const ora_idx_t *x, int32_t c_a, const uint8_t *q_str, const sah_t *sa_hash, int key_len)
 {
@@ -955,23 +1040,7 @@ static int sdp_middle_M2(ora_ctx_t *cx, const ora_idx_t *x, int32_t c_a, const u
 				sms_t *S = cx->sms;
 				for (uint32_t ci = 1; ci < cx->n_sms; ci++) {
 					sms_t *c_spd = S + ci;
-					int max_score = c_spd->len;
-					uint32_t max_q = c_spd->q_pos + 6, max_t = c_spd->t_pos + 6;
-					for (int32_t pi = (int32_t)ci - 1; pi >= 0; pi--) {
-						sms_t *ps = S + pi;
-						int pre_q_ed = ps->q_pos + ps->len + 9 - 1, pre_t_ed = ps->t_pos + ps->len + 9 - 1;
-						if (pre_q_ed > max_q) continue;
-						if (pre_t_ed > max_t) continue;
-						int indel = ps->q_pos - ps->t_pos - (max_q - max_t);
-						int ai = ABSV(indel);
-						if (ai > 200) continue;
-						int ns = ps->score + c_spd->len - (ai >> 3);
-						if (pre_q_ed > c_spd->q_pos || pre_t_ed > c_spd->t_pos) {
-							int oq = pre_q_ed - c_spd->q_pos, ot = pre_t_ed - c_spd->t_pos;
-							ns -= MAXV(oq, ot);
-						}
-						max_score = MAXV(max_score, ns);
-					}
+					int max_score = dp_pred_middle(S, ci);
 					score = MAXV(max_score, score);
 					c_spd->score = max_score;
 				}
@@ -1043,6 +1112,24 @@ int ora_gap_stage(ora_ctx_t *c, const char *seq, uint32_t L, int strand, const u
 	return score;
 }
 
+#define XT_REASON(cx, r) do { if ((cx)->xt) (cx)->xt->reason = (r); } while (0)
+static void xt_window(ora_ctx_t *cx)
+{
+	struct ext_trace *x = cx->xt;
+	if (x) { if (x->n_win < x->max_win) x->win_n[x->n_win] = cx->n_sms; x->n_win++; }
+}
+static void xt_segment(ora_ctx_t *cx, uint32_t scored)
+{
+	struct ext_trace *x = cx->xt;
+	if (!x) return;
+	if (x->n_seg < x->max_seg && x->n_nodes + cx->n_sms <= x->max_nodes) {
+		x->seg[2 * x->n_seg] = cx->n_sms; x->seg[2 * x->n_seg + 1] = scored;
+		memcpy(x->nodes + 4 * (size_t)x->n_nodes, cx->sms, sizeof(sms_t) * cx->n_sms);
+		x->n_nodes += cx->n_sms;
+	}
+	x->n_seg++;
+}
+
 /* sdp_right_M2, src/cly.c:2532-2677 */
 static int sdp_right_M2(ora_ctx_t *cx, const ora_idx_t *x, const uint8_t *q_str, const sah_t *sa_hash, int key_len,
                         chain_t *c_st, int chain_ID, uint32_t l_read, sch_t *sc_hash, int score_ori)
@@ -1062,10 +1149,10 @@ static int sdp_right_M2(ora_ctx_t *cx, const ora_idx_t *x, const uint8_t *q_str,
 	while (1) {
 		if (cx->n_sms == current_sms) {
 			uint32_t next_step = t_length - c_t_offset;
-			if (next_step < 12) break;
+			if (next_step < 12) { XT_REASON(cx, 1); break; }
 			uint32_t max_search_ref;
 			if (l_read - c_h->q_ed < 600) {
-				if (last_search == true) break;
+				if (last_search == true) { XT_REASON(cx, 2); break; }
 				last_search = true;
 				max_search_ref = l_read - c_h->q_ed + 60;
 			} else max_search_ref = t_length - c_t_offset;
@@ -1076,31 +1163,16 @@ static int sdp_right_M2(ora_ctx_t *cx, const ora_idx_t *x, const uint8_t *q_str,
 			int search_q_st = MAXV(search_q_ed - 2000, c_h->q_st - 8);
 			sdp_match(cx, search_q_st, search_q_ed, q_str, ref, max_search_ref, key_len, sa_hash, c_t_offset, true);
 			c_t_offset += max_search_ref - 9 - 3;
-			if (cx->n_sms == current_sms) break;
-			if (cx->sms[current_sms].t_pos > cx->sms[max_sms_id].t_pos + 1000) break;
+			xt_window(cx);
+			if (cx->n_sms == current_sms) { XT_REASON(cx, 3); break; }
+			if (cx->sms[current_sms].t_pos > cx->sms[max_sms_id].t_pos + 1000) { XT_REASON(cx, 4); break; }
 		}
 		sms_t *c_sms = cx->sms + current_sms++;
-		int max_score = c_sms->len;
-		uint32_t max_pre_q = c_sms->q_pos + 6, max_pre_t = c_sms->t_pos + 6;
-		for (int32_t pi = (int32_t)current_sms - 2; pi >= 0; pi--) {
-			sms_t *ps = cx->sms + pi;
-			int pre_q_ed = ps->q_pos + ps->len + 9 - 1, pre_t_ed = ps->t_pos + ps->len + 9 - 1;
-			if (pre_q_ed > max_pre_q) continue;
-			if (pre_t_ed > max_pre_t) continue;
-			if (ps->t_pos + 600 < max_pre_t) break;
-			int indel = ps->q_pos - ps->t_pos - (max_pre_q - max_pre_t);
-			int ai = ABSV(indel);
-			if (ai > 200) continue;
-			int ns = ps->score + c_sms->len - (ai >> 3);
-			if (pre_q_ed > c_sms->q_pos || pre_t_ed > c_sms->t_pos) {
-				int oq = pre_q_ed - c_sms->q_pos, ot = pre_t_ed - c_sms->t_pos;
-				ns -= MAXV(oq, ot);
-			}
-			max_score = MAXV(max_score, ns);
-		}
+		int max_score = dp_pred_right(cx->sms, current_sms - 1);
 		c_sms->score = max_score;
 		if (c_sms->len >= 8 && combine_chain(c_st, chain_ID, sc_hash, c_sms->t_pos - c_sms->q_pos, false, c_sms->q_pos, &combined) == true) {
 			int c_len = c_sms->len;
+			xt_segment(cx, current_sms); if (cx->xt) cx->xt->merges++;
 			total_max_score = MAXV(score_ori, max_score) - c_len + sdp_middle_M2(cx, x, combined->cur, q_str, sa_hash, key_len);
 			score_ori = total_max_score; max_sms_id = 0;
 			cx->n_sms = 0;
@@ -1111,8 +1183,9 @@ static int sdp_right_M2(ora_ctx_t *cx, const ora_idx_t *x, const uint8_t *q_str,
 			continue;
 		}
 		if (total_max_score < max_score) { total_max_score = max_score; max_sms_id = current_sms - 1; }
-		if (c_sms->t_pos > cx->sms[max_sms_id].t_pos + 1000) break;
+		if (c_sms->t_pos > cx->sms[max_sms_id].t_pos + 1000) { XT_REASON(cx, 5); break; }
 	}
+	xt_segment(cx, current_sms);
 	c_h->q_ed = cx->sms[max_sms_id].q_pos + cx->sms[max_sms_id].len + 9;
 	c_h->t_ed = cx->sms[max_sms_id].t_pos + cx->sms[max_sms_id].len + 9;
 	return total_max_score - 10000;
@@ -1137,10 +1210,10 @@ static int sdp_left_M2(ora_ctx_t *cx, const ora_idx_t *x, const uint8_t *q_str, 
 	while (1) {
 		if (cx->n_sms == current_sms) {
 			uint32_t next_step = c_t_offset;
-			if (next_step < 12) break;
+			if (next_step < 12) { XT_REASON(cx, 1); break; }
 			uint32_t max_search_ref;
 			if (c_h->q_st < 600) {
-				if (last_search == true) break;
+				if (last_search == true) { XT_REASON(cx, 2); break; }
 				last_search = true;
 				max_search_ref = c_h->q_st + 60;
 			} else max_search_ref = c_t_offset;
@@ -1154,30 +1227,16 @@ static int sdp_left_M2(ora_ctx_t *cx, const ora_idx_t *x, const uint8_t *q_str, 
 			int search_q_ed = MINV(search_q_st + 2000, c_h->q_st - 1);
 			sdp_match(cx, search_q_st, search_q_ed, q_str, ref + 50, max_search_ref, key_len, sa_hash, c_t_offset - max_search_ref, false);
 			c_t_offset = c_t_offset - max_search_ref + 9 + 3;
-			if (cx->n_sms == current_sms) break;
-			if (cx->sms[current_sms].t_pos + 1000 < cx->sms[max_sms_id].t_pos) break;
+			xt_window(cx);
+			if (cx->n_sms == current_sms) { XT_REASON(cx, 3); break; }
+			if (cx->sms[current_sms].t_pos + 1000 < cx->sms[max_sms_id].t_pos) { XT_REASON(cx, 4); break; }
 		}
 		sms_t *c_sms = cx->sms + current_sms++;
-		int max_score = c_sms->len;
-		uint32_t min_pre_q = c_sms->q_pos + c_sms->len - 6 + 9 - 1, min_pre_t = c_sms->t_pos + c_sms->len - 6 + 9 - 1;
-		for (int32_t pi = (int32_t)current_sms - 2; pi >= 0; pi--) {
-			sms_t *ps = cx->sms + pi;
-			if (ps->q_pos < min_pre_q) continue;
-			if (ps->t_pos < min_pre_t) continue;
-			if (min_pre_t + 600 < ps->t_pos) break;
-			int indel = ps->q_pos - ps->t_pos - (min_pre_q - min_pre_t);
-			int ai = ABSV(indel);
-			if (ai > 200) continue;
-			int ns = ps->score + c_sms->len - (ai >> 3);
-			if (min_pre_q + 6 > ps->q_pos || min_pre_t + 6 > ps->t_pos) {
-				int oq = min_pre_q + 6 - ps->q_pos, ot = min_pre_t + 6 - ps->t_pos;
-				ns -= MAXV(oq, ot);
-			}
-			max_score = MAXV(max_score, ns);
-		}
+		int max_score = dp_pred_left(cx->sms, current_sms - 1);
 		c_sms->score = max_score;
 		if (c_sms->len >= 8 && combine_chain(c_st, chain_ID, sc_hash, c_sms->t_pos - c_sms->q_pos, true, c_sms->q_pos + c_sms->len, &combined) == true) {
 			int c_len = c_sms->len;
+			xt_segment(cx, current_sms); if (cx->xt) cx->xt->merges++;
 			total_max_score = MAXV(score_ori, max_score) - c_len + sdp_middle_M2(cx, x, combined->cur, q_str, sa_hash, key_len);
 			score_ori = total_max_score; max_sms_id = 0;
 			cx->n_sms = 0;
@@ -1188,11 +1247,51 @@ static int sdp_left_M2(ora_ctx_t *cx, const ora_idx_t *x, const uint8_t *q_str, 
 			continue;
 		}
 		if (total_max_score < max_score) { total_max_score = max_score; max_sms_id = current_sms - 1; }
-		if (c_sms->t_pos + 1000 < cx->sms[max_sms_id].t_pos) break;
+		if (c_sms->t_pos + 1000 < cx->sms[max_sms_id].t_pos) { XT_REASON(cx, 5); break; }
 	}
+	xt_segment(cx, current_sms);
 	c_h->q_st = cx->sms[max_sms_id].q_pos;
 	c_h->t_st = cx->sms[max_sms_id].t_pos;
 	return total_max_score - 10000;
+}
+
+/* One sdp_right_M2 (left == 0) or sdp_left_M2 on its own (tests/test_stage_ext.py).  refbin: a synthetic 2-bit text of n_ref references
+ * (refinfo: rows of seq_l, seq_offset) with its 4 KiB of zeros behind; chains: the chain list, changed in place (cur: index of the chain's
+ * last anchor); anchors: rows of 5 (index_in_read, ref_offset, mtch_len, pre, ref_ID).  The chain hash is sc_hash_idx over the list.
+ * -> the score; info = reason, merges, windows, segments; win_n, seg, nodes: see struct ext_trace */
+int ora_ext_stage(ora_ctx_t *c, const char *seq, uint32_t L, int strand, int left, const uint8_t *refbin, uint64_t ref_bases,
+                  const uint64_t *refinfo, uint32_t n_ref, ora_chain_t *chains, uint32_t n_chains, const int32_t *anchors, uint32_t n_anchors,
+                  int chain_ID, int score_ori, uint32_t *info, uint32_t *win_n, uint32_t max_win, uint32_t *seg, uint32_t max_seg,
+                  uint32_t *nodes, uint32_t max_nodes)
+{
+	ora_idx_t x; memset(&x, 0, sizeof x);
+	ora_refinfo_t *R = calloc(n_ref ? n_ref : 1, sizeof *R);
+	for (uint32_t i = 0; i < n_ref; i++) { R[i].seq_l = refinfo[2 * i]; R[i].seq_offset = refinfo[2 * i + 1]; }
+	x.refbin = (uint8_t *)refbin; x.n_refbin = (ref_bases + 3) / 4; x.ref = R; x.n_ref = n_ref;
+	const uint8_t *q_str = stage_read(c, seq, L, strand);
+	c->ref_bases = ref_bases;
+	c->n_anc = 0;
+	for (uint32_t i = 0; i < n_anchors; i++) {
+		anchor_t *a = push_anchor(c);
+		a->index_in_read = (uint32_t)anchors[5 * i]; a->ref_offset = (uint32_t)anchors[5 * i + 1]; a->a_m.mtch_len = (uint16_t)anchors[5 * i + 2]; a->pre = anchors[5 * i + 3];
+		a->ref_ID = (uint32_t)anchors[5 * i + 4]; a->direction = (uint8_t)strand;
+	}
+	c->n_hit = 0;
+	for (uint32_t i = 0; i < n_chains; i++) memcpy(push_hit(c), chains + i, sizeof(chain_t));
+	int key_len = build_hash_table_M2(c, c->sd, (int)L);
+	const sah_t *h = (strand == FORWARD) ? c->sa_hash[0] : c->sa_hash[1];
+	sch_t *sc = calloc(256 + 2 * (size_t)n_chains + 8, sizeof(sch_t));
+	sc_hash_idx(sc, c->hit, n_chains);
+	struct ext_trace t; memset(&t, 0, sizeof t);
+	t.win_n = win_n; t.max_win = max_win; t.seg = seg; t.max_seg = max_seg; t.nodes = nodes; t.max_nodes = max_nodes;
+	c->xt = &t;
+	int score = left ? sdp_left_M2(c, &x, q_str, h, key_len, c->hit, chain_ID, L, sc, score_ori) : sdp_right_M2(c, &x, q_str, h, key_len, c->hit, chain_ID, L, sc, score_ori);
+	c->xt = NULL;
+	memcpy(chains, c->hit, sizeof(chain_t) * n_chains);
+	info[0] = (uint32_t)t.reason; info[1] = (uint32_t)t.merges; info[2] = t.n_win; info[3] = t.n_seg;
+	free(sc); free(R);
+	c->n_sms = 0; c->n_anc = 0; c->n_hit = 0;
+	return score;
 }
 
 /* get_score_M2, src/cly.c:2821-2849 */

@@ -104,12 +104,20 @@ int ora_sdp_match_stage(ora_ctx_t *c, const char *seq, uint32_t len, int strand,
                         const uint8_t *t_str, uint32_t t_len, uint32_t t_st, int is_forward, uint32_t *out, int max_out);
 int ora_gap_stage(ora_ctx_t *c, const char *seq, uint32_t len, int strand, const uint8_t *refbin, uint64_t ref_bases,
                   const int32_t *anchors, uint32_t n_anchors, int32_t c_a, uint32_t *gap_nodes, uint32_t *n_gaps);
+/* the sparse DP of a-12 on a bare node list (tests/test_stage_dp.py): rows of 4 (t_pos, q_pos, len, score), node 0 carries its score;
+ * mode 0 middle, 1 right, 2 left -> the score of every node */
+void ora_sdp_dp_stage(int mode, const uint32_t *nodes, uint32_t n, int32_t *scores);
 /* a chain as the stage entries below take and give it: the layout of chain_item as oracle/classify.c and the device code hold it */
 typedef struct {
 	uint32_t ref_ID; int32_t q_t_dis; uint32_t sum_score, anchor_number;
 	uint8_t direction, with_top_anchor, primary, pri_index;
 	uint32_t t_st, t_ed, q_st, q_ed, indel, chain_id; int32_t cur;
 } ora_chain_t;
+/* one sdp_right_M2 (left == 0) or sdp_left_M2 on its own (tests/test_stage_ext.py): see oracle/classify.c */
+int ora_ext_stage(ora_ctx_t *c, const char *seq, uint32_t L, int strand, int left, const uint8_t *refbin, uint64_t ref_bases,
+                  const uint64_t *refinfo, uint32_t n_ref, ora_chain_t *chains, uint32_t n_chains, const int32_t *anchors, uint32_t n_anchors,
+                  int chain_ID, int score_ori, uint32_t *info, uint32_t *win_n, uint32_t max_win, uint32_t *seg, uint32_t max_seg,
+                  uint32_t *nodes, uint32_t max_nodes);
 /* a-10 on its own (tests/test_stage_chain.py): chain_insert_M2 / chain_insert_M3 and the end of resolve_tree on a list of anchors */
 int ora_resolve_stage(ora_ctx_t *c, const uint32_t *anchors, uint32_t n, int m3, uint32_t *order, int32_t *pre,
                       ora_chain_t *raw, uint32_t max_raw, uint32_t *n_raw, ora_chain_t *fin, uint32_t max_fin);

@@ -315,7 +315,7 @@ static StageHost *stage_host()
 	return h;
 }
 struct StageJob {
-	StageHost *h; int what, form; StageSdp *sc; StageChain *cc; const uint8_t *bin; const uint64_t *pk; const uint8_t *aux; DsbSms *nodes; uint4 *mirror; DsbGap *G; const int32_t *anchors;
+	StageHost *h; int what, form; StageSdp *sc; StageChain *cc; StageDp *dc; const uint32_t *sizes; StageExt *ec; DsbChain *chains; const int32_t *rows5; DsbScHash *scs; const DsbRefInfo *ris; const uint8_t *bin; const uint64_t *pk; const uint8_t *aux; DsbSms *nodes; uint4 *mirror; DsbGap *G; const int32_t *anchors;
 };
 static void stage_lane(void *p)
 {
@@ -323,7 +323,9 @@ static void stage_lane(void *p)
 	stage_ctx(h->w, &h->sx, h->slice.data(), h->wtab, h->ring, h->red, h->cnt, &h->ri);
 	if (j->what == 0) stage_sdp(h->w, &h->sx, j->form, j->sc, j->bin, j->pk, j->aux, j->nodes, j->mirror);
 	else if (j->what == 1) stage_gap_lane(h->w, &h->sx, j->cc, j->bin, j->pk, j->aux, j->G);
-	else stage_middle(h->w, &h->sx, j->cc, j->bin, j->pk, j->aux, j->anchors);
+	else if (j->what == 2) stage_middle(h->w, &h->sx, j->cc, j->bin, j->pk, j->aux, j->anchors);
+	else if (j->what == 3) stage_dp(h->w, &h->sx, j->dc, j->nodes, j->sizes);
+	else stage_ext(h->w, &h->sx, j->ec, j->bin, j->pk, j->aux, j->chains, j->rows5, j->nodes, j->scs, j->ris);
 }
 static void stage_run(StageJob &j)
 {
@@ -393,6 +395,42 @@ extern "C" int emu_stage_middle(StageChain *cases, uint32_t n, const uint8_t *bi
 	for (uint32_t k = 0; k < n; k++) { j.cc = cases + k; stage_run(j); }
 	return 0;
 }
+
+// the sparse DP on bare node lists (tests/test_stage_dp.py): forms (a) .. (c); form (d), sdp_batch_old_mw on several wavefronts, runs on the device only
+extern "C" int emu_stage_dp(StageDp *cases, uint32_t n, DsbSms *nodes, size_t node_entries, const uint32_t *sizes, size_t n_sizes)
+{
+	if (stage_dp_check(cases, n, node_entries, n_sizes)) return __LINE__;
+	for (uint32_t k = 0; k < n; k++) if (cases[k].form == DP_MW) return __LINE__;
+	StageJob j; memset(&j, 0, sizeof j); j.h = stage_host(); j.what = 3; j.nodes = nodes; j.sizes = sizes;
+	stage_regions(j, cases, (size_t)n * sizeof(StageDp), 0, 0, 0);
+#if DSB_EMU_LANES == 64
+	dsb_emu_region(nodes, node_entries * sizeof(DsbSms), "node lists"); dsb_emu_region(sizes, n_sizes * 4, "block sizes");
+#endif
+	for (uint32_t k = 0; k < n; k++) { j.dc = cases + k; stage_run(j); }
+	return 0;
+}
+extern "C" uint32_t emu_stage_sizes_dp(uint32_t *out)
+{
+	out[0] = sizeof(StageDp); out[1] = STAGE_DP_GUARD; out[2] = DSB_RING; out[3] = DSB_DPB; out[4] = DSB_DP_UNROLL; out[5] = DSB_EMU_LANES; out[6] = DSB_MW_MAXW; out[7] = DSB_ST_HEAVY;
+	return 8;
+}
+
+// one sdp_right_M2 / sdp_left_M2 per case, block-wise or node by node (tests/test_stage_ext.py)
+extern "C" int emu_stage_ext(StageExt *cases, uint32_t n, const uint8_t *bin, size_t bin_bytes, const uint64_t *pk, size_t pk_words, const uint8_t *ref, size_t ref_bytes,
+                             DsbChain *chains, size_t n_chains, const int32_t *anchors, size_t n_rows, DsbSms *nodes, size_t node_entries, DsbScHash *scs, size_t n_sc,
+                             const DsbRefInfo *ris, size_t n_ri)
+{
+	if (stage_ext_check(cases, n, n_chains, n_rows, anchors, chains, node_entries, n_sc, n_ri)) return __LINE__;
+	StageJob j; memset(&j, 0, sizeof j); j.h = stage_host(); j.what = 4; j.bin = bin; j.pk = pk; j.aux = ref; j.chains = chains; j.rows5 = anchors; j.nodes = nodes; j.scs = scs; j.ris = ris;
+	stage_regions(j, cases, (size_t)n * sizeof(StageExt), bin_bytes, pk_words, ref_bytes);
+#if DSB_EMU_LANES == 64
+	dsb_emu_region(chains, n_chains * sizeof(DsbChain), "chains"); dsb_emu_region(anchors, n_rows * 20, "anchor rows"); dsb_emu_region(nodes, node_entries * sizeof(DsbSms), "node lists");
+	dsb_emu_region(scs, n_sc * sizeof(DsbScHash), "chain hash"); dsb_emu_region(ris, n_ri * sizeof(DsbRefInfo), "reference info");
+#endif
+	for (uint32_t k = 0; k < n; k++) { j.ec = cases + k; stage_run(j); }
+	return 0;
+}
+extern "C" uint32_t emu_stage_sizes_ext(uint32_t *out) { out[0] = sizeof(StageExt); out[1] = sizeof(DsbChain); out[2] = sizeof(DsbScHash); out[3] = sizeof(DsbRefInfo); return 4; }
 
 // ---- the chain stages form by form (tests/stage/dsb_stage_forms.h, tests/test_stage_chain.py, tests/test_stage_finish.py): resolve_tree with the
 // sort, the DP and the selection forced; the cut and the tail of delete_small_score_rst, detect_primary; glibc_sort_chains

@@ -1,7 +1,7 @@
 // TEST INFRASTRUCTURE: stage a-12 of the device code (dsb_classify_dev.h: sdp_match in its five forms, gap_lane, sdp_middle_M2) and the
 // chain stages a-10, a-13, a-14 and a-17 (resolve_tree in every form, the tail of delete_small_score_rst, detect_primary, glibc_sort_chains) on
 // the GPU, form by form, with the real wavefront primitives of dsb_wave.h (tests/stage/dsb_stage_forms.h holds the forms; the
-// host emulation runs the same text).  One wavefront per workgroup, one workgroup per case; the context is set up as
+// host emulation runs the same text).  One wavefront per workgroup (k_stage_dp_mw: 2, 4 or 8), one workgroup per case; the context is set up as
 // classify_kernel_body (dsb_gpu.hip) sets it up.  Built into tests/stage/libdsbstage.so; nothing of it is in libdesamba_amd.so.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -118,6 +118,140 @@ extern "C" int stage_dev_middle(StageChain *cases, uint32_t n, const uint8_t *bi
 	CK(hipGetLastError() != hipSuccess);
 	CK(hipDeviceSynchronize() != hipSuccess);
 	if (n) CK(dc.down(cases));
+	return 0;
+}
+
+// ---- the sparse DP on bare node lists (tests/test_stage_dp.py): forms (a) .. (c) on one wavefront per case ...
+__global__ void __launch_bounds__(64) k_stage_dp(StageDp *cases, uint32_t base, uint32_t n, DsbSms *nodes, const uint32_t *sizes, uint8_t *slices, const DsbRefInfo *refinfo)
+{
+	const uint32_t k = base + blockIdx.x;
+	if (k >= n) return;
+	STAGE_KERNEL_CTX
+	stage_dp(w, (DSB_LDS_AS DsbDevIndex *)&sx, cases + k, nodes, sizes);
+}
+// ... and form (d): the pass over the old predecessors of a batch on W wavefronts (sdp_batch_old_mw), called directly whatever DSB_MW_MIN_PREDS
+// says.  Wave 0 posts a batch of K nodes (K from the case's sizes, 1 .. DSB_DPB) as sdp_best_pred_b posts it, every wave runs the pass with its
+// own wave number, wave 0 combines the waves' maxima as sdp_best_pred_b does and scores the batch's nodes through sdp_best_pred_b itself (its
+// own old pass is skipped: the batch bounds and old_best are in place), keeping the ring.  Every wave reaches every barrier: the batch
+// bounds come from the case, and the exits of sdp_batch_old_mw's round loop depend on n0, W and the cut flags all waves read from LDS.
+template <int W>
+__global__ void __launch_bounds__(64 * W) k_stage_dp_mw(StageDp *cases, uint32_t base, uint32_t n, DsbSms *nodes, const uint32_t *sizes)
+{
+	const uint32_t k = base + blockIdx.x;
+	if (k >= n) return;
+	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+	__shared__ DsbDevIndex sx;
+	__shared__ uint4 lds_ring[DSB_RING];
+	__shared__ uint32_t lds_red[W + 1];
+	__shared__ uint32_t lds_cnt[4];
+	__shared__ DpBatch lds_dpb;
+	__shared__ DsbMw mw;
+	__shared__ WCtx s_w;
+	WCtxL &w = *(WCtxL *)&s_w;
+	const StageDp c = cases[k];
+	DsbSms *const sms = nodes + c.node_off;
+	const uint32_t *const sz = sizes + c.s0;
+	if (threadIdx.x < 4) lds_cnt[threadIdx.x] = 0;
+	__syncthreads();
+	if (wv == 0) {
+		w.dpb = (DpBatchL *)&lds_dpb;
+		w.x = (DsbXP)&sx; w.dbg = nullptr; w.ring = lds_ring; w.red = lds_red; w.k.c = (lds_u32 *)lds_cnt; w.k.uni = 1; w.step_limit = DSB_STEP_LIMIT; w.stage = 0;
+		stage_dp_begin(w, (DSB_LDS_AS DsbDevIndex *)&sx, c, sms);
+		if (c.n) { const DsbSms s0 = sms[0]; ring_put(w, 0, s0.t_pos, s0.q_pos, s0.len, s0.score); }
+	}
+	__syncthreads();
+	NodeBlock nb; nb.base = 0; nb.valid = 0;
+	uint32_t steps = 0, bi = 0;
+	for (uint32_t n0 = 1; n0 < c.n; bi++) {
+		uint32_t K = c.n_sizes ? sz[bi % c.n_sizes] : (uint32_t)DSB_DPB;
+		K = K < 1u ? 1u : K > (uint32_t)DSB_DPB ? (uint32_t)DSB_DPB : K;
+		if (K > c.n - n0) K = c.n - n0;
+		if (wv == 0) {
+			if (lane < DSB_DPB) { const DsbSms g = sms[n0 + ((uint32_t)lane < K ? lane : 0)]; mw.nd_t[lane] = g.t_pos; mw.nd_q[lane] = g.q_pos; mw.nd_l[lane] = g.len; }
+			if (lane == 0) { mw.cmd = c.mode; mw.n0 = n0; mw.K = K; mw.sms = sms; }
+		}
+		__syncthreads();
+		uint32_t preds = 0;
+		if (c.mode == 1) sdp_batch_old_mw<1>(&mw, lds_ring, lds_red, lane, wv, W, &preds);
+		else sdp_batch_old_mw<2>(&mw, lds_ring, lds_red, lane, wv, W, &preds);
+		if (wv == 0) {
+			DpBatchL &b = *w.dpb;
+			if (lane == 0) {
+				b.n0 = n0; b.K = K;
+				for (uint32_t j = 0; j < DSB_DPB; j++) { int m = -2147483647 - 1; for (int u = 0; u < W; u++) m = MAXV(m, mw.best[u][j]); b.old_best[j] = j < K ? m : 0; }
+			}
+			w.dp_preds += preds;
+			wave_sync();
+			uint32_t bn0 = n0, bK = K;
+			for (uint32_t cur = n0; cur < n0 + K; cur++) {
+				DsbSms nd = sms[cur]; nd.score = 0;
+				const int sc = c.mode == 1 ? sdp_best_pred_b<1>(w, b, nd, (int32_t)cur, nb, c.n, lds_ring, steps, bn0, bK) : sdp_best_pred_b<2>(w, b, nd, (int32_t)cur, nb, c.n, lds_ring, steps, bn0, bK);
+				sms[cur].score = (uint32_t)sc;
+				{ uint4 r_; r_.x = nd.t_pos; r_.y = nd.q_pos; r_.z = nd.len; r_.w = (uint32_t)sc; ring_st(lds_ring, cur & (DSB_RING - 1), r_); }
+			}
+			if (b.n0 != n0 || b.K != K || bn0 != n0 || bK != K) w.status |= DSB_ST_TIMEOUT;      // sdp_best_pred_b filled the batch anew: its own old pass ran, not the one under test (the test wants status 0)
+		}
+		__threadfence_block();
+		__syncthreads();                                                // the scores and the ring: the next batch's old predecessors
+		n0 += K;
+	}
+	if (threadIdx.x == 0) { cases[k].status = (uint32_t)w.status; cases[k].dp_preds = w.dp_preds; cases[k].scored = c.n; cases[k].defined = 1; }
+}
+extern "C" uint32_t stage_dev_sizes_dp(uint32_t *out)
+{
+	out[0] = sizeof(StageDp); out[1] = STAGE_DP_GUARD; out[2] = DSB_RING; out[3] = DSB_DPB; out[4] = DSB_DP_UNROLL; out[5] = 64; out[6] = DSB_MW_MAXW; out[7] = DSB_ST_HEAVY;
+	return 8;
+}
+// all cases of one call take the same form, and for form (d) the same number of wavefronts (2, 4 or 8)
+extern "C" int stage_dev_dp(StageDp *cases, uint32_t n, DsbSms *nodes, size_t node_entries, const uint32_t *sizes, size_t n_sizes)
+{
+	DevBuf dc, dn, dz, ds, dr;
+	CK(stage_dp_check(cases, n, node_entries, n_sizes));
+	if (!n) return 0;
+	const uint32_t form = cases[0].form, W = cases[0].waves;
+	for (uint32_t k = 0; k < n; k++) CK(cases[k].form != form || (form == DP_MW && (cases[k].waves != W || cases[k].mode == 0)));
+	CK(form == DP_MW && W != 2 && W != 4 && W != 8);
+	CK(stage_common(ds, dr));
+	CK(dc.up(cases, (size_t)n * sizeof(StageDp))); CK(dn.up(nodes, node_entries * sizeof(DsbSms))); CK(dz.up(sizes, n_sizes * 4));
+	for (uint32_t base = 0; base < n; base += STAGE_GRID) {
+		const dim3 grid(n - base < STAGE_GRID ? n - base : STAGE_GRID);
+		if (form != DP_MW) hipLaunchKernelGGL(k_stage_dp, grid, dim3(64), 0, 0, (StageDp *)dc.p, base, n, (DsbSms *)dn.p, (const uint32_t *)dz.p, (uint8_t *)ds.p, (const DsbRefInfo *)dr.p);
+		else if (W == 2) hipLaunchKernelGGL(k_stage_dp_mw<2>, grid, dim3(128), 0, 0, (StageDp *)dc.p, base, n, (DsbSms *)dn.p, (const uint32_t *)dz.p);
+		else if (W == 4) hipLaunchKernelGGL(k_stage_dp_mw<4>, grid, dim3(256), 0, 0, (StageDp *)dc.p, base, n, (DsbSms *)dn.p, (const uint32_t *)dz.p);
+		else hipLaunchKernelGGL(k_stage_dp_mw<8>, grid, dim3(512), 0, 0, (StageDp *)dc.p, base, n, (DsbSms *)dn.p, (const uint32_t *)dz.p);
+	}
+	CK(hipGetLastError() != hipSuccess);
+	CK(hipDeviceSynchronize() != hipSuccess);
+	CK(dc.down(cases)); CK(dn.down(nodes));
+	return 0;
+}
+
+// ---- one sdp_right_M2 / sdp_left_M2 per case (tests/test_stage_ext.py)
+__global__ void __launch_bounds__(64) k_stage_ext(StageExt *cases, uint32_t base, uint32_t n, const uint8_t *bin, const uint64_t *pk, const uint8_t *ref, DsbChain *chains, const int32_t *anchors,
+                                                  DsbSms *nodes, DsbScHash *scs, const DsbRefInfo *ris, uint8_t *slices, const DsbRefInfo *refinfo)
+{
+	const uint32_t k = base + blockIdx.x;
+	if (k >= n) return;
+	STAGE_KERNEL_CTX
+	stage_ext(w, (DSB_LDS_AS DsbDevIndex *)&sx, cases + k, bin, pk, ref, chains, anchors, nodes, scs, ris);
+}
+extern "C" uint32_t stage_dev_sizes_ext(uint32_t *out) { out[0] = sizeof(StageExt); out[1] = sizeof(DsbChain); out[2] = sizeof(DsbScHash); out[3] = sizeof(DsbRefInfo); return 4; }
+extern "C" int stage_dev_ext(StageExt *cases, uint32_t n, const uint8_t *bin, size_t bin_bytes, const uint64_t *pk, size_t pk_words, const uint8_t *ref, size_t ref_bytes,
+                             DsbChain *chains, size_t n_chains, const int32_t *anchors, size_t n_rows, DsbSms *nodes, size_t node_entries, DsbScHash *scs, size_t n_sc,
+                             const DsbRefInfo *ris, size_t n_ri)
+{
+	DevBuf dc, db, dp, dt, dh, da, dn, dz, di, ds, dr;
+	CK(stage_ext_check(cases, n, n_chains, n_rows, anchors, chains, node_entries, n_sc, n_ri));
+	if (!n) return 0;
+	CK(stage_common(ds, dr));
+	CK(dc.up(cases, (size_t)n * sizeof(StageExt))); CK(db.up(bin, bin_bytes)); CK(dp.up(pk, 8 * pk_words)); CK(dt.up(ref, ref_bytes)); CK(dh.up(chains, n_chains * sizeof(DsbChain)));
+	CK(da.up(anchors, n_rows * 20)); CK(dn.up(nodes, node_entries * sizeof(DsbSms))); CK(dz.up(scs, n_sc * sizeof(DsbScHash))); CK(di.up(ris, n_ri * sizeof(DsbRefInfo)));
+	for (uint32_t base = 0; base < n; base += STAGE_GRID)
+		hipLaunchKernelGGL(k_stage_ext, dim3(n - base < STAGE_GRID ? n - base : STAGE_GRID), dim3(64), 0, 0, (StageExt *)dc.p, base, n, (const uint8_t *)db.p, (const uint64_t *)dp.p, (const uint8_t *)dt.p,
+		                   (DsbChain *)dh.p, (const int32_t *)da.p, (DsbSms *)dn.p, (DsbScHash *)dz.p, (const DsbRefInfo *)di.p, (uint8_t *)ds.p, (const DsbRefInfo *)dr.p);
+	CK(hipGetLastError() != hipSuccess);
+	CK(hipDeviceSynchronize() != hipSuccess);
+	CK(dc.down(cases)); CK(dh.down(chains)); CK(dn.down(nodes));
 	return 0;
 }
 

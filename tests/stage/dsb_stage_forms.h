@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE: stage a-12 (sdp_match in its five forms, gap_lane, sdp_middle_M2; dsb_classify_dev.h) and, further down, the
+// TEST INFRASTRUCTURE: stage a-12 (sdp_match in its five forms, gap_lane, sdp_middle_M2, the sparse DP's predecessor scan; dsb_classify_dev.h) and, further down, the
 // chain stages a-10, a-13, a-14 and a-17 (resolve_tree in every form, the tail of delete_small_score_rst, detect_primary, glibc_sort_chains) called form by form
 // on cases that a test lays out in flat arrays, so that a test knows which code produced a node list.  One text for the three
 // legs: tests/emu/emu_classify.cpp compiles it for the host (1 lane, or 64 lanes with the race detector), tests/stage/dsb_stage.hip
@@ -155,6 +155,155 @@ DN void stage_middle(WCtxL &w, DSB_LDS_AS DsbDevIndex *sx, StageChain *cs, const
 	wave_sync();
 	if (DSB_LANE == 0) { cs->score = score; cs->status = c.n_anc <= STAGE_MAX_ANC ? (uint32_t)w.status : 0xffffffffu; }
 	wave_sync();
+}
+
+// ---- the sparse DP of stage a-12 on a bare node list (tests/test_stage_dp.py): the predecessor scan in each of its restatements.  A case is a
+// list of nodes (t_pos, q_pos, len) whose node 0 carries its score; a form scores every other node in place.
+//   nodes   one region of n + STAGE_DP_GUARD DsbSms per case; the test fills the scores of nodes 1 .. and the guards with a pattern
+//   sizes   block sizes of form (c) / batch sizes of form (d), taken in turn and cyclically ([s0, s0 + n_sizes); none: the callers' own)
+enum { DP_PRED = 0, DP_BATCH = 1, DP_BLOCK = 2, DP_MW = 3 };
+#define STAGE_DP_GUARD 4u
+struct StageDp {
+	uint32_t n, mode, form, waves;                    // mode 0 middle (form DP_PRED only), 1 right, 2 left; waves: wavefronts of form DP_MW
+	uint32_t s0, n_sizes, heavy_limit, pad0;
+	uint64_t node_off;
+	uint32_t status, dp_preds, scored, defined;       // out: w.status, w.dp_preds, nodes scored before the form returned, whether the form is defined for the case
+};
+DV void stage_dp_begin(WCtxL &w, DSB_LDS_AS DsbDevIndex *sx, const StageDp &c, DsbSms *sms)
+{
+	wave_sync();
+	w.sms = sms; w.n_sms = c.n; sx->sms_cap = c.n; w.status = 0; w.dp_preds = 0; w.steps = 0; w.heavy_limit = c.heavy_limit; w.boosted = 0; w.mw = nullptr; w.n_waves = 1;
+	wave_sync();
+}
+// (a) sdp_best_pred node by node: modes 1 and 2 keep the ring as the node-by-node extensions do, mode 0 runs without it (sdp_middle_M2)
+template <int MODE>
+DV uint32_t stage_dp_pred(WCtxL &w, DsbSms *sms, const uint32_t n)
+{
+	if (MODE != 0 && n) { const DsbSms s0 = sms[0]; ring_put(w, 0, s0.t_pos, s0.q_pos, s0.len, s0.score); wave_sync(); }
+	uint32_t cur = 1;
+	for (; cur < n; cur++) {
+		const DsbSms nd = sms[cur];
+		const int sc = sdp_best_pred<MODE>(w, nd, (int32_t)cur);
+		sms[cur].score = (uint32_t)sc;
+		if (MODE != 0) { ring_put(w, cur, nd.t_pos, nd.q_pos, nd.len, (uint32_t)sc); wave_sync(); }
+	}
+	return n ? cur : 0;
+}
+// (b) sdp_best_pred_b on one wavefront, through node_get / NodeBlock and the ring, as sdp_right_M2_mw / sdp_left_M2_mw run it
+template <int MODE>
+DV uint32_t stage_dp_batch(WCtxL &w, DsbSms *sms, const uint32_t n)
+{
+	if (!n) return 0;
+	{ const DsbSms s0 = sms[0]; ring_put(w, 0, s0.t_pos, s0.q_pos, s0.len, s0.score); }
+	NodeBlock nb; nb.base = 0; nb.valid = 0;
+	DpBatchL &db = *w.dpb; db.n0 = 0; db.K = 0;
+	uint32_t bn0 = 0, bK = 0, cur = 1, steps = w.steps; const uint32_t step_limit = w.step_limit; uint4 *const ring = w.ring;
+	wave_sync();
+	while (cur < n) {
+		if (++steps > step_limit) { w.status |= DSB_ST_TIMEOUT; break; }
+		DsbSms *c_sms = sms + cur;
+		const DsbSms nd = node_get(w, nb, cur); cur++;
+		const int sc = sdp_best_pred_b<MODE>(w, db, nd, (int32_t)cur - 1, nb, n, ring, steps, bn0, bK);
+		c_sms->score = (uint32_t)sc;
+		{ uint4 r_; r_.x = nd.t_pos; r_.y = nd.q_pos; r_.z = nd.len; r_.w = (uint32_t)sc; ring_st(ring, (cur - 1) & (DSB_RING - 1), r_); }
+	}
+	w.steps = steps;
+	return cur;
+}
+// (c) sdp_block_scores block by block, the scores written back between the blocks as ext_block does
+template <int MODE>
+DV uint32_t stage_dp_block(WCtxL &w, DsbSms *sms, const uint32_t n, const uint32_t *sizes, const uint32_t n_sizes)
+{
+	const int lane = DSB_LANE;
+	uint32_t cur = 1, k = 0;
+	while (cur < n) {
+		uint32_t m = MINV((uint32_t)DSB_WAVE, n - cur);
+		if (n_sizes) { m = MINV(m, MAXV(1u, sizes[k % n_sizes])); k++; }
+		const bool mine = (uint32_t)lane < m;
+		DsbSms nd; nd.t_pos = nd.q_pos = nd.len = nd.score = 0;
+		if (mine) nd = sms[cur + lane];
+		const int sc = sdp_block_scores<MODE>(w, cur, m, nd);
+		if (mine) sms[cur + lane].score = (uint32_t)sc;
+		wave_sync();                                                // (the scores: the next block's old predecessors)
+		cur += m;
+		if (w.status & DSB_ST_HEAVY) break;                         // ext_block spends the loop budget here: the extension stops at its next test
+	}
+	return n ? cur : 0;
+}
+DN void stage_dp(WCtxL &w, DSB_LDS_AS DsbDevIndex *sx, StageDp *cs, DsbSms *nodes, const uint32_t *sizes)
+{
+	const StageDp c = *cs;
+	DsbSms *const sms = nodes + c.node_off;
+	stage_dp_begin(w, sx, c, sms);
+	uint32_t scored = 0, defined = 1;
+	if (c.form == DP_PRED) scored = c.mode == 0 ? stage_dp_pred<0>(w, sms, c.n) : c.mode == 1 ? stage_dp_pred<1>(w, sms, c.n) : stage_dp_pred<2>(w, sms, c.n);
+	else if (c.mode == 0) defined = 0;
+	else if (c.form == DP_BATCH) scored = c.mode == 1 ? stage_dp_batch<1>(w, sms, c.n) : stage_dp_batch<2>(w, sms, c.n);
+	else if (c.form == DP_BLOCK) scored = c.mode == 1 ? stage_dp_block<1>(w, sms, c.n, sizes + c.s0, c.n_sizes) : stage_dp_block<2>(w, sms, c.n, sizes + c.s0, c.n_sizes);
+	else defined = 0;
+	wave_sync();
+	if (DSB_LANE == 0) { cs->status = (uint32_t)w.status; cs->dp_preds = w.dp_preds; cs->scored = scored; cs->defined = defined; }
+	wave_sync();
+}
+static inline int stage_dp_check(const StageDp *cs, uint32_t n, size_t n_nodes, size_t n_sizes)
+{
+	for (uint32_t k = 0; k < n; k++) {
+		const StageDp &c = cs[k];
+		if (c.node_off + c.n + STAGE_DP_GUARD > n_nodes || (size_t)c.s0 + c.n_sizes > n_sizes || c.mode > 2 || c.form > DP_MW || c.n > 0x7fffff00u) return 1;
+		if (c.form == DP_MW && (c.waves < 2 || c.waves > DSB_MW_MAXW)) return 1;
+	}
+	return 0;
+}
+
+// ---- the right / left extensions of stage a-12 on their own (tests/test_stage_ext.py): one sdp_right_M2 / sdp_left_M2, block-wise (through
+// ext_block) or node by node (the _mw forms with w.mw == nullptr), on a read, a 2-bit text of two references, a chain list with its anchors.
+//   chains  the chain list of a case, changed in place;  anchors: rows of 5 (index_in_read, ref_offset, mtch_len, pre, ref_ID)
+//   nodes   one region of sms_cap + STAGE_DP_GUARD DsbSms per case, filled with a pattern;  sc: 256 + 2 n_chains + 8 DsbScHash per case
+//   ris     DsbRefInfo of the case's references (ri_off: in entries)
+struct StageExt {
+	uint32_t L, strand, left, mw, c0, n_chains, chain_ID, a0, n_anc, sms_cap, heavy_limit, n_ref; int32_t score_ori; uint32_t pad0;
+	uint64_t bin_off, pk_off, ref_off, ref_bases, node_off, sc_off, ri_off;
+	int32_t score; uint32_t status, n_sms, defined;                     // out
+};
+DN void stage_ext(WCtxL &w, DSB_LDS_AS DsbDevIndex *sx, StageExt *cs, const uint8_t *bin, const uint64_t *pk, const uint8_t *ref, DsbChain *chains, const int32_t *anchors,
+                  DsbSms *nodes, DsbScHash *scs, const DsbRefInfo *ris)
+{
+	const StageExt c = *cs;
+	wave_sync();
+	stage_read(w, bin, c.bin_off, pk, c.pk_off, c.L, true);
+	sx->refbin = ref + c.ref_off; sx->ref_bases = c.ref_bases; sx->sms_cap = c.sms_cap; sx->refinfo = ris + c.ri_off;
+	w.sms = nodes + c.node_off; w.hit = chains + c.c0; w.n_hit = c.n_chains; w.sc = scs + c.sc_off; w.heavy_limit = c.heavy_limit; w.boosted = 0; w.mw = nullptr; w.n_waves = 1;
+	for (uint32_t i = (uint32_t)DSB_LANE; i < c.n_anc; i += DSB_WAVE) {
+		const int32_t *r = anchors + 5 * (size_t)(c.a0 + i);
+		DsbAnchor an; an.mtch_len = (uint16_t)r[2]; an.score = 0; an.left_len = an.left_ED = an.rigt_len = an.rigt_ED = 0; an.direction = (uint8_t)c.strand; an.useless = an.duplicate = an.pad0 = 0;
+		an.seed_ID = an.chain_id = 0; an.ref_ID = (uint32_t)r[4]; an.ref_offset = (uint32_t)r[1]; an.index_in_read = (uint32_t)r[0]; an.pre = r[3]; an.global_offset = 0;
+		w.anc[i] = an;
+	}
+	for (uint32_t k = (uint32_t)DSB_LANE; k < 256u; k += DSB_WAVE) { DsbScHash z; z.next = 0; z.seed_ID = 0; w.sc[k] = z; }
+	wave_sync();
+	w.n_anc = c.n_anc;
+	wave_sync();
+	DSB_SERIAL(w) sc_hash_idx(w.sc, w.hit, w.n_hit);
+	serial_end(w);
+	wave_sync();
+	const uint8_t *q_str = w.bin + (c.strand == D_FORWARD ? 0u : c.L); const int tbl = c.strand == D_FORWARD ? 0 : 1;
+	int score;
+	if (!c.left) score = c.mw ? sdp_right_M2_mw(w, q_str, tbl, 0, w.hit, (int)c.chain_ID, c.L, w.sc, c.score_ori) : sdp_right_M2(w, q_str, tbl, 0, w.hit, (int)c.chain_ID, c.L, w.sc, c.score_ori);
+	else score = c.mw ? sdp_left_M2_mw(w, q_str, tbl, 0, w.hit, (int)c.chain_ID, c.L, w.sc, c.score_ori) : sdp_left_M2(w, q_str, tbl, 0, w.hit, (int)c.chain_ID, c.L, w.sc, c.score_ori);
+	wave_sync();
+	if (DSB_LANE == 0) { cs->score = score; cs->status = (uint32_t)w.status; cs->n_sms = w.n_sms; cs->defined = 1; }
+	wave_sync();
+}
+static inline int stage_ext_check(const StageExt *cs, uint32_t n, size_t n_chains, size_t n_rows, const int32_t *anchors, const DsbChain *chains, size_t n_nodes, size_t n_sc, size_t n_ri)
+{
+	for (uint32_t k = 0; k < n; k++) {
+		const StageExt &c = cs[k];
+		if ((size_t)c.c0 + c.n_chains > n_chains || c.chain_ID >= c.n_chains || c.n_chains > 16000 || (size_t)c.a0 + c.n_anc > n_rows || c.n_anc > STAGE_MAX_ANC) return 1;
+		if (c.node_off + c.sms_cap + STAGE_DP_GUARD > n_nodes || c.sms_cap < 2 || c.sc_off + 256 + 2 * (size_t)c.n_chains + 8 > n_sc || c.ri_off + c.n_ref > n_ri || c.L < 9) return 1;
+		for (uint32_t i = 0; i < c.n_anc; i++) { const int32_t *r = anchors + 5 * (size_t)(c.a0 + i); if (r[3] < -1 || r[3] >= (int32_t)i || (uint32_t)r[4] >= c.n_ref) return 1; }
+		for (uint32_t i = 0; i < c.n_chains; i++) { const DsbChain &h = chains[c.c0 + i]; if (h.ref_ID >= c.n_ref || h.cur < -1 || (h.cur >= 0 && (uint32_t)h.cur >= c.n_anc)) return 1; }      // (cur: the last anchor of a chain that can be merged in, or -1)
+	}
+	return 0;
 }
 
 // ---- stages a-10 (resolve_tree), a-13 behind get_score_M2, a-14 (detect_primary), a-17 (glibc_sort_chains): tests/test_stage_chain.py,
