@@ -74,6 +74,7 @@ class DsbRefCoverage(C.Structure):
 
 
 COVERAGE_FIELDS = ("numreads", "covbases", "aligned_bases", "mapq_sum")
+WINDOW_FIELDS = ("starts", "aligned_bases", "covbases")
 
 
 class DsbEmOpts(C.Structure):
@@ -127,7 +128,8 @@ EXPORTS = ["dsb_index_open", "dsb_index_close", "dsb_index_n_ref", "dsb_index_re
            "dsb_ctx_set_taxonomy", "dsb_multi_set_taxonomy", "dsb_batch_taxa", "dsb_multi_taxa",
            "dsb_report_create", "dsb_report_add", "dsb_report_add_sam", "dsb_report_format", "dsb_report_destroy",
            "dsb_ctx_enable_coverage", "dsb_ctx_reset_coverage", "dsb_ctx_coverage", "dsb_multi_enable_coverage", "dsb_multi_coverage",
-           "dsb_coverage_format", "dsb_ctx_enable_abundance", "dsb_ctx_reset_abundance", "dsb_ctx_abundance", "dsb_multi_enable_abundance",
+           "dsb_coverage_format", "dsb_coverage_n_windows", "dsb_ctx_enable_coverage_windows", "dsb_ctx_coverage_windows",
+           "dsb_multi_enable_coverage_windows", "dsb_multi_coverage_windows", "dsb_coverage_windows_format", "dsb_ctx_enable_abundance", "dsb_ctx_reset_abundance", "dsb_ctx_abundance", "dsb_multi_enable_abundance",
            "dsb_multi_abundance", "dsb_abundance_format",
            "dsb_ctx_set_batch_ordinal", "dsb_ctx_abundance_assign", "dsb_multi_abundance_assign", "dsb_format_assign",
            "dsb_ctx_enable_lca", "dsb_ctx_reset_lca", "dsb_batch_lca", "dsb_ctx_lca_counts", "dsb_multi_enable_lca", "dsb_multi_lca",
@@ -206,6 +208,12 @@ def lib():
     L.dsb_multi_enable_coverage.argtypes = [C.c_void_p, C.c_int]
     L.dsb_multi_coverage.argtypes = [C.c_void_p, C.c_void_p]
     L.dsb_coverage_format.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]; L.dsb_coverage_format.restype = C.c_long
+    L.dsb_coverage_n_windows.argtypes = [C.c_void_p, C.c_uint32]; L.dsb_coverage_n_windows.restype = C.c_uint64
+    L.dsb_ctx_enable_coverage_windows.argtypes = [C.c_void_p, C.c_uint32]
+    L.dsb_ctx_coverage_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.dsb_multi_enable_coverage_windows.argtypes = [C.c_void_p, C.c_uint32]
+    L.dsb_multi_coverage_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.dsb_coverage_windows_format.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t]; L.dsb_coverage_windows_format.restype = C.c_long
     L.dsb_ctx_enable_abundance.argtypes = [C.c_void_p, C.c_int, C.c_uint32]
     L.dsb_ctx_reset_abundance.argtypes = [C.c_void_p]
     L.dsb_ctx_abundance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -437,6 +445,16 @@ class Ctx:
         """everything since enable / reset: numpy structured array of n_ref rows (COVERAGE_FIELDS, u64)"""
         return _coverage(lib().dsb_ctx_coverage, self.h, self.index.n_ref, "dsb_ctx_coverage")
 
+    def enable_coverage_windows(self, window=1000):
+        """per-window coverage from now on (coverage must be on; the whole coverage state is zeroed), or off for window 0"""
+        rc = lib().dsb_ctx_enable_coverage_windows(self.h, int(window))
+        if rc != 0:
+            raise DsbError(rc, "dsb_ctx_enable_coverage_windows")
+
+    def coverage_windows(self):
+        """everything since enable / reset: numpy structured array of n_coverage_windows rows (WINDOW_FIELDS, u64)"""
+        return _coverage_windows(lib().dsb_ctx_coverage_windows, self.h, "dsb_ctx_coverage_windows")
+
     def enable_abundance(self, on=True, min_frac=0.95):
         """per-reference abundance by EM from now on (each read's candidate set kept in HBM), or off (freed).  min_frac: a read's
         candidates are the references whose best AS is at least min_frac x its best AS (0 < min_frac <= 1, in steps of 0.001)"""
@@ -562,6 +580,15 @@ class Multi:
         """Ctx.coverage merged over the contexts"""
         return _coverage(lib().dsb_multi_coverage, self.h, self.index.n_ref, "dsb_multi_coverage")
 
+    def enable_coverage_windows(self, window=1000):
+        rc = lib().dsb_multi_enable_coverage_windows(self.h, int(window))
+        if rc != 0:
+            raise DsbError(rc, "dsb_multi_enable_coverage_windows")
+
+    def coverage_windows(self):
+        """Ctx.coverage_windows merged over the contexts"""
+        return _coverage_windows(lib().dsb_multi_coverage_windows, self.h, "dsb_multi_coverage_windows")
+
     def enable_abundance(self, on=True, min_frac=0.95):
         rc = lib().dsb_multi_enable_abundance(self.h, 1 if on else 0, _permille(min_frac) if on else 0)
         if rc != 0:
@@ -635,6 +662,27 @@ def _coverage(fn, h, n_ref, what):
     return out
 
 
+WINDOW_DTYPE = [(f, "<u8") for f in WINDOW_FIELDS]
+
+
+def _coverage_windows(fn, h, what):
+    import numpy as np
+    n = C.c_size_t(0)
+    rc = fn(h, None, 0, C.byref(n))
+    if rc != 0:
+        raise DsbError(rc, what)
+    out = np.zeros(n.value, dtype=WINDOW_DTYPE)
+    rc = fn(h, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n))
+    if rc != 0:
+        raise DsbError(rc, what)
+    return out
+
+
+def n_coverage_windows(index, window):
+    """dsb_coverage_n_windows: the number of windows of `window` bases over all references (0 for window 0)"""
+    return int(lib().dsb_coverage_n_windows(index.h, int(window)))
+
+
 def _permille(min_frac):
     f = float(min_frac)
     if not (0.0 < f <= 1.0) or int(f * 1000 + 0.5) < 1:
@@ -703,6 +751,22 @@ def format_abundance(index, ab, summary):
     while True:
         buf = C.create_string_buffer(cap)
         n = lib().dsb_abundance_format(index.h, ab.ctypes.data_as(C.c_void_p), C.byref(s), buf, cap)
+        if n >= 0:
+            return buf.raw[:n]
+        cap *= 4
+
+
+def format_coverage_windows(index, cov, win, window):
+    """dsb_coverage_windows_format: the per-window table (bytes) of a coverage array and a window array of size `window`"""
+    import numpy as np
+    cov = np.ascontiguousarray(cov, dtype=COVERAGE_DTYPE)
+    win = np.ascontiguousarray(win, dtype=WINDOW_DTYPE)
+    if len(cov) != index.n_ref or int(window) < 1 or len(win) != n_coverage_windows(index, window):
+        raise ValueError("format_coverage_windows: %d rows, %d windows of %d bases for %d references" % (len(cov), len(win), int(window), index.n_ref))
+    cap = 1 << 16
+    while True:
+        buf = C.create_string_buffer(cap)
+        n = lib().dsb_coverage_windows_format(index.h, cov.ctypes.data_as(C.c_void_p), win.ctypes.data_as(C.c_void_p), int(window), buf, cap)
         if n >= 0:
             return buf.raw[:n]
         cap *= 4

@@ -880,6 +880,9 @@ static void usage(void)
 	fprintf(stderr, "    --report FILE    write the read counts per taxon of the run into FILE, as `analysis ana_meta` prints them for its SAM\n");
 	fprintf(stderr, "    --report-base FILE  the same for `analysis ana_meta_base` (bases weighted by MAPQ)\n");
 	fprintf(stderr, "    --coverage FILE  write the coverage of every reference the run touched into FILE (columns of `samtools coverage`)\n");
+	fprintf(stderr, "    --coverage-windows FILE  write the reads, covered bases, breadth and mean depth of every fixed-size window of every reference the\n");
+	fprintf(stderr, "                     run touched into FILE (windows without reads included): where on a reference the reads lie\n");
+	fprintf(stderr, "    --coverage-window-size W  bases per window of --coverage-windows, 1 <= W < 2^31 [1000]\n");
 	fprintf(stderr, "    --abundance FILE  write the reads and shares per reference, estimated by EM over each read's near-best references, into FILE\n");
 	fprintf(stderr, "    --abundance-min-frac F  a read's candidates: references whose AS is at least F x its best AS, 0 < F <= 1 [0.95]\n");
 	fprintf(stderr, "    --abundance-reads FILE  assign each read to the candidate reference with the largest EM posterior and write, when the run ends, one\n");
@@ -961,9 +964,10 @@ static int classify_main(int argc, char **argv)
 	                                              {"abundance-min-frac", required_argument, NULL, 6}, {"kraken-out", required_argument, NULL, 7},
 	                                              {"kraken-report", required_argument, NULL, 8}, {"names", required_argument, NULL, 9},
 	                                              {"lca-min-frac", required_argument, NULL, 10}, {"abundance-reads", required_argument, NULL, 11},
+	                                              {"coverage-windows", required_argument, NULL, 12}, {"coverage-window-size", required_argument, NULL, 13},
 	                                              {NULL, 0, NULL, 0}};
-	const char *tax_path = NULL, *rep_path[2] = {NULL, NULL}, *cov_path = NULL, *ab_path = NULL, *kr_path = NULL, *krep_path = NULL, *names_path = NULL, *abr_path = NULL;
-	uint32_t ab_permille = 950, lca_permille = 950; int lca_frac_set = 0;
+	const char *tax_path = NULL, *rep_path[2] = {NULL, NULL}, *cov_path = NULL, *ab_path = NULL, *kr_path = NULL, *krep_path = NULL, *names_path = NULL, *abr_path = NULL, *covw_path = NULL;
+	uint32_t ab_permille = 950, lca_permille = 950, cov_window = 1000; int lca_frac_set = 0, cov_window_set = 0;
 	while ((c = getopt_long(argc, argv, "ht:l:r:f:o:s:g:", long_opts, NULL)) >= 0) {
 		if (c == 'h') { usage(); return 0; }
 		else if (c == 1) tax_path = optarg;
@@ -984,6 +988,12 @@ static int classify_main(int argc, char **argv)
 			lca_permille = (uint32_t)(f * 1000 + 0.5); lca_frac_set = 1;
 		}
 		else if (c == 11) abr_path = optarg;
+		else if (c == 12) covw_path = optarg;
+		else if (c == 13) {
+			char *e; const long long v = strtoll(optarg, &e, 10);
+			if (e == optarg || *e || v < 1 || v >= (1ll << 31)) die("[classify] --coverage-window-size takes a number of bases W with 1 <= W < 2^31");
+			cov_window = (uint32_t)v; cov_window_set = 1;
+		}
 		else if (c == '?' && optopt == 11) die("[classify] --abundance-reads takes a file name");   /* (last on the line: getopt_long found no argument) */
 		else if (c == 't') { /* thread count: accepted for compatibility, unused */ }
 		else if (c == 'l') a.o.L_min_matching = atoi(optarg);
@@ -1019,6 +1029,7 @@ static int classify_main(int argc, char **argv)
 	}
 	if ((rep_path[0] || rep_path[1]) && !tax_path) die("[classify] --report and --report-base need --taxonomy nodes.dmp");
 	if ((kr_path || krep_path || names_path || lca_frac_set) && !tax_path) die("[classify] --kraken-out, --kraken-report, --names and --lca-min-frac need --taxonomy nodes.dmp");
+	if (cov_window_set && !covw_path) die("[classify] --coverage-window-size needs --coverage-windows FILE");
 	a.lca_on = kr_path || krep_path;
 	dsb_taxnames *names = NULL;
 	if (tax_path) {
@@ -1035,6 +1046,8 @@ static int classify_main(int argc, char **argv)
 	if (krep_path && !(krep_out = fopen(krep_path, "w"))) { fprintf(stderr, "[xopen] fail to open file '%s'\n", krep_path); exit(1); }
 	FILE *cov_out = NULL;
 	if (cov_path && !(cov_out = fopen(cov_path, "w"))) { fprintf(stderr, "[xopen] fail to open file '%s'\n", cov_path); exit(1); }
+	FILE *covw_out = NULL;
+	if (covw_path && !(covw_out = fopen(covw_path, "w"))) { fprintf(stderr, "[xopen] fail to open file '%s'\n", covw_path); exit(1); }
 	FILE *ab_out = NULL;
 	if (ab_path && !(ab_out = fopen(ab_path, "w"))) { fprintf(stderr, "[xopen] fail to open file '%s'\n", ab_path); exit(1); }
 	FILE *abr_out = NULL;
@@ -1055,7 +1068,8 @@ static int classify_main(int argc, char **argv)
 	if (rc) { fprintf(stderr, "\n[dsb_ctx_create] %s\n", dsb_strerror(rc)); exit(1); }
 	for (int k = 0; k < a.n_ctx; k++) a.ctx[k] = dsb_multi_ctx(a.multi, k);
 	if ((a.rep || a.lca_on) && (rc = dsb_multi_set_taxonomy(a.multi, a.tx))) { fprintf(stderr, "\n[dsb_ctx_set_taxonomy] %s\n", dsb_strerror(rc)); exit(1); }
-	if (cov_out && (rc = dsb_multi_enable_coverage(a.multi, 1))) { fprintf(stderr, "\n[dsb_ctx_enable_coverage] %s\n", dsb_strerror(rc)); exit(1); }
+	if ((cov_out || covw_out) && (rc = dsb_multi_enable_coverage(a.multi, 1))) { fprintf(stderr, "\n[dsb_ctx_enable_coverage] %s\n", dsb_strerror(rc)); exit(1); }
+	if (covw_out && (rc = dsb_multi_enable_coverage_windows(a.multi, cov_window))) { fprintf(stderr, "\n[dsb_ctx_enable_coverage_windows] %s\n", dsb_strerror(rc)); exit(1); }
 	if ((ab_out || abr_out) && (rc = dsb_multi_enable_abundance(a.multi, 1, ab_permille))) { fprintf(stderr, "\n[dsb_ctx_enable_abundance] %s\n", dsb_strerror(rc)); exit(1); }
 	if (a.lca_on && (rc = dsb_multi_enable_lca(a.multi, 1, lca_permille))) { fprintf(stderr, "\n[dsb_ctx_enable_lca] %s\n", dsb_strerror(rc)); exit(1); }
 	double t0 = now(), cpu0 = cputime(); a.t0 = t0;
@@ -1085,14 +1099,26 @@ static int classify_main(int argc, char **argv)
 		if (fwrite(buf, 1, (size_t)w, a.rep_out[k]) != (size_t)w || fclose(a.rep_out[k])) die("[classify] cannot write the report");
 		free(buf);
 	}
-	if (cov_out) {
+	if (cov_out || covw_out) {
 		/* --coverage: the per-reference coverage of the whole run, merged over the contexts */
 		const size_t n_ref = (size_t)dsb_index_n_ref(a.idx);
 		dsb_ref_coverage *cov = xrealloc(NULL, (n_ref ? n_ref : 1) * sizeof *cov);
 		if ((rc = dsb_multi_coverage(a.multi, cov))) { fprintf(stderr, "[dsb_multi_coverage] %s\n", dsb_strerror(rc)); exit(1); }
 		size_t cap = 1 << 16; char *buf = NULL; long w;
-		do { cap *= 4; buf = xrealloc(buf, cap); w = dsb_coverage_format(a.idx, cov, buf, cap); } while (w < 0);
-		if (fwrite(buf, 1, (size_t)w, cov_out) != (size_t)w || fclose(cov_out)) die("[classify] cannot write the coverage table");
+		if (cov_out) {
+			do { cap *= 4; buf = xrealloc(buf, cap); w = dsb_coverage_format(a.idx, cov, buf, cap); } while (w < 0);
+			if (fwrite(buf, 1, (size_t)w, cov_out) != (size_t)w || fclose(cov_out)) die("[classify] cannot write the coverage table");
+		}
+		if (covw_out) {
+			/* --coverage-windows: the same run per window of cov_window bases (the rows of the references the table above lists) */
+			size_t n_win = 0;
+			if ((rc = dsb_multi_coverage_windows(a.multi, NULL, 0, &n_win))) { fprintf(stderr, "[dsb_multi_coverage_windows] %s\n", dsb_strerror(rc)); exit(1); }
+			dsb_cov_window *win = xrealloc(NULL, (n_win ? n_win : 1) * sizeof *win);
+			if ((rc = dsb_multi_coverage_windows(a.multi, win, n_win, &n_win))) { fprintf(stderr, "[dsb_multi_coverage_windows] %s\n", dsb_strerror(rc)); exit(1); }
+			do { cap *= 4; buf = xrealloc(buf, cap); w = dsb_coverage_windows_format(a.idx, cov, win, cov_window, buf, cap); } while (w < 0);
+			if (fwrite(buf, 1, (size_t)w, covw_out) != (size_t)w || fclose(covw_out)) die("[classify] cannot write the coverage windows table");
+			free(win);
+		}
 		free(buf); free(cov);
 	}
 	if (ab_out || abr_out) {

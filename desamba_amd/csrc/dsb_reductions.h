@@ -1,5 +1,5 @@
-// The run reductions of classify: per-read taxa (dsb_ctx_set_taxonomy), per-reference coverage (dsb_ctx_enable_coverage,
-// DESIGN 2.9), per-reference abundance by EM (dsb_ctx_enable_abundance) and per-read LCA classification
+// The run reductions of classify: per-read taxa (dsb_ctx_set_taxonomy), per-reference and per-window coverage (dsb_ctx_enable_coverage,
+// dsb_ctx_enable_coverage_windows), per-reference abundance by EM (dsb_ctx_enable_abundance) and per-read LCA classification
 // (dsb_ctx_enable_lca).  Each reads a batch's hit buffer
 // after its last classify launch, keeps state for the whole run and is merged across the contexts of a dsb_multi
 // (dsb_reductions.hip).  Internal: the public surface is include/desamba_amd.h.
@@ -20,9 +20,13 @@ struct DsbTaxa {
 };
 
 // coverage: a bitmap of one bit per reference base (each reference from a word boundary; off: the prefix sum of ceil(LN / 64),
-// n_ref + 1 words), the lengths, and the four counters per reference; one k_ref_cover launch per batch
+// n_ref + 1 words), the lengths, and the four counters per reference; one k_ref_cover launch per batch.
+// Windows (dsb_ctx_enable_coverage_windows; on exactly when win != 0): the window size, each reference's first
+// window (d_first: the prefix sum of ceil(LN / win), n_ref + 1 words), {starts, aligned_bases} per window (d_win, 16 bytes each, one
+// k_ref_windows launch per batch) and the covbases slot per window that a fetch fills (d_wcov)
 struct DsbCover {
 	uint64_t *d_bits = nullptr, *d_off = nullptr, *d_len = nullptr; dsb_ref_coverage *d_cov = nullptr; uint64_t words = 0;
+	uint32_t win = 0; uint64_t n_win = 0, *d_first = nullptr, *d_win = nullptr, *d_wcov = nullptr;
 };
 
 // abundance: the run's candidate sets (DsbEmSet + their elements, grown geometrically between batches), the store's counters,

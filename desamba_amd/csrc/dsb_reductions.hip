@@ -1,4 +1,4 @@
-// The run reductions of classify (dsb_reductions.h): per-read taxa, per-reference coverage and per-reference
+// The run reductions of classify (dsb_reductions.h): per-read taxa, per-reference coverage with its per-window profile and per-reference
 // abundance by EM with each read's assignment by its posterior, per-read LCA classification -- their kernels, the launches after a batch's last classify launch (reductions_run), the
 // host side of each, and their merges over the contexts of a dsb_multi.
 #include <algorithm>
@@ -129,6 +129,99 @@ __global__ void __launch_bounds__(256) k_cover_clear(dsb_ref_coverage *cov, uint
 __global__ void __launch_bounds__(256) k_cover_or(uint64_t *__restrict__ dst, const uint64_t *__restrict__ src, uint64_t nw)
 {
 	for (uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x; q < nw; q += (uint64_t)gridDim.x * 256) dst[q] |= src[q];
+}
+
+// ---- per-window coverage (dsb_ctx_enable_coverage_windows) ----
+// One wavefront per read, behind k_ref_cover on the same stream, over the same records with the same guards and the same clipped
+// interval [s, e).  Window j of a reference is [jW, min((j + 1)W, LN)); its counters are win[2 (first[ref] + j)] (starts) and the
+// word after it (aligned_bases).  The lanes stride over the windows s / W .. (e - 1) / W of a record: each adds the length of its
+// overlap, and the lane that holds window s / W adds the record's start.  Agent-scope no-return atomic adds throughout, for the reason
+// k_ref_cover gives: records of different workgroups share windows.
+__global__ void __launch_bounds__(256) k_ref_windows(const DsbReadOut *__restrict__ rout, const DsbHitOut *__restrict__ hout, const unsigned int *__restrict__ counters,
+                                                     uint32_t cap_hout, uint32_t n, const uint64_t *__restrict__ ref_len, const uint64_t *__restrict__ first,
+                                                     uint32_t n_ref, uint32_t W, uint64_t *win)
+{
+	const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+	if (i >= n) return;
+	const uint32_t nh = dsb_hits_out(counters[1], cap_hout);
+	const DsbReadOut r = rout[i];
+	const uint32_t nrec = dsb_hits_cut(r.first, r.n, nh) ? 0u : r.n;
+	if (!nrec) return;
+	const dsb_hit *h = reinterpret_cast<const dsb_hit *>(hout + r.first);
+	for (uint32_t k = 0; k < nrec; k++) {
+		const dsb_hit *c = h + k;
+		if (!dsb_sam_counted(c, k) || c->ref_ID >= n_ref) continue;
+		const uint64_t ln = ref_len[c->ref_ID];
+		const uint64_t s = c->t_st < ln ? c->t_st : ln, e = c->t_ed < ln ? c->t_ed : ln;
+		if (e <= s) continue;
+		uint64_t *w = win + 2 * first[c->ref_ID];
+		const uint64_t j0 = s / W, j1 = (e - 1) / W;               // (e <= LN: j1 is a window of the reference)
+		for (uint64_t j = j0 + lane; j <= j1; j += 64) {
+			const uint64_t lo = j * W > s ? j * W : s, hi = (j + 1) * W < e ? (j + 1) * W : e;
+			__hip_atomic_fetch_add(w + 2 * j + 1, hi - lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			if (j == j0) __hip_atomic_fetch_add(w + 2 * j, (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		}
+	}
+}
+
+// the set bits of bitmap word q of a reference (its bases [64 q, 64 q + 64)) that lie in the bases [y0, y1); the word must meet them
+__device__ inline uint32_t window_bits(uint64_t word, uint64_t q, uint64_t y0, uint64_t y1)
+{
+	const uint64_t lo = q * 64 < y0 ? y0 - q * 64 : 0, hi = q * 64 + 64 > y1 ? y1 - q * 64 : 64;
+	return (uint32_t)__popcll(word & (hi == 64 ? ~0ull : (1ull << hi) - 1) & (~0ull << lo));
+}
+
+// A fetch: the covbases of every window, from words [w0, w0 + nw) of the bitmap (bits[q - w0] holds word q), balanced by words as
+// k_cover_count is and with its walk over the references of a chunk.  The chunk's words of reference r are the bases [x0, x1) of r
+// (x1 clipped at LN), which meet the windows x0 / W .. (x1 - 1) / W; each of them gets the popcount of its bases INSIDE the chunk, so a
+// window cut by the chunk's ends -- a window of more than DSB_COVER_CHUNK words, or one across a chunk boundary of the merge of
+// dsb_multi_coverage_windows -- gets one partial sum per chunk, and a word that straddles windows is counted under a mask in each.
+// From DSB_WINDOW_WAVE bases (64 words) on, the wavefront takes the windows one after the other, the lanes striding over the
+// window's words, and lane 0 adds the reduced sum; below it each lane takes a window and walks its words (at most 65) alone.
+// Either way one atomic add per wavefront and window.
+#define DSB_WINDOW_WAVE 4096
+__global__ void __launch_bounds__(256) k_window_count(const uint64_t *__restrict__ bits, uint64_t w0, uint64_t nw, const uint64_t *__restrict__ word_off,
+                                                      const uint64_t *__restrict__ ref_len, const uint64_t *__restrict__ first, uint32_t n_ref, uint32_t W,
+                                                      uint64_t *wcov)
+{
+	const uint64_t a = w0 + ((uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * DSB_COVER_CHUNK, end = w0 + nw;
+	const uint32_t lane = threadIdx.x & 63;
+	if (a >= end) return;
+	const uint64_t b = a + DSB_COVER_CHUNK < end ? a + DSB_COVER_CHUNK : end;
+	uint32_t lo = 0, hi = n_ref;                           // word_off[lo] <= a < word_off[hi], as k_cover_count
+	while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (word_off[mid] <= a) lo = mid; else hi = mid; }
+	for (uint32_t r = lo;; r++) {
+		const uint64_t off = word_off[r], s = off > a ? off : a, e = word_off[r + 1] < b ? word_off[r + 1] : b;
+		if (e > s) {
+			const uint64_t ln = ref_len[r], x0 = (s - off) * 64, x1 = (e - off) * 64 < ln ? (e - off) * 64 : ln;   // (word e - 1 is one of r's: x1 > x0)
+			const uint64_t at = off - w0;                      // word q of r is bits[at + q] (modulo 2^64 where r began before w0: only q >= s - off is read)
+			uint64_t *o = wcov + first[r];
+			const uint64_t j0 = x0 / W, j1 = (x1 - 1) / W;
+			if (W >= DSB_WINDOW_WAVE) {
+				for (uint64_t j = j0; j <= j1; j++) {
+					const uint64_t y0 = j * W > x0 ? j * W : x0, y1 = (j + 1) * W < x1 ? (j + 1) * W : x1;
+					uint32_t sum = 0;                          // (at most 64 bits x DSB_COVER_CHUNK words)
+					for (uint64_t q = (y0 >> 6) + lane; q <= ((y1 - 1) >> 6); q += 64) sum += window_bits(bits[at + q], q, y0, y1);
+					for (int t = 32; t; t >>= 1) sum += __shfl_xor(sum, t, 64);
+					if (lane == 0 && sum) __hip_atomic_fetch_add(o + j, (uint64_t)sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+				}
+			} else {
+				for (uint64_t j = j0 + lane; j <= j1; j += 64) {
+					const uint64_t y0 = j * W > x0 ? j * W : x0, y1 = (j + 1) * W < x1 ? (j + 1) * W : x1;
+					uint32_t sum = 0;
+					for (uint64_t q = y0 >> 6; q <= ((y1 - 1) >> 6); q++) sum += window_bits(bits[at + q], q, y0, y1);
+					if (sum) __hip_atomic_fetch_add(o + j, (uint64_t)sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+				}
+			}
+		}
+		if (e >= b) break;
+	}
+}
+
+// before a count: the covbases slots = 0 (starts and aligned_bases stay)
+__global__ void __launch_bounds__(256) k_window_clear(uint64_t *wcov, uint64_t n_win)
+{
+	for (uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x; j < n_win; j += (uint64_t)gridDim.x * 256) wcov[j] = 0;
 }
 
 // ---- per-reference abundance by EM (dsb_ctx_enable_abundance) ----
@@ -566,8 +659,14 @@ extern "C" int dsb_batch_taxa(dsb_ctx *c, const dsb_read_taxon **out)
 }
 
 // ---- per-reference coverage ----
+static void windows_free(dsb_ctx *c)
+{
+	hipFree(c->cover.d_first); hipFree(c->cover.d_win); hipFree(c->cover.d_wcov);
+	c->cover.d_first = c->cover.d_win = c->cover.d_wcov = nullptr; c->cover.win = 0; c->cover.n_win = 0;
+}
 static void cover_free(dsb_ctx *c)
 {
+	windows_free(c);
 	hipFree(c->cover.d_bits); hipFree(c->cover.d_off); hipFree(c->cover.d_len); hipFree(c->cover.d_cov);
 	c->cover = DsbCover();
 }
@@ -579,6 +678,10 @@ extern "C" int dsb_ctx_reset_coverage(dsb_ctx *c)
 	const size_t n_ref = (size_t)dsb_index_n_ref(c->idx);
 	HIPCHK(hipMemsetAsync(c->cover.d_bits, 0, (c->cover.words ? c->cover.words : 1) * 8, c->stream));
 	HIPCHK(hipMemsetAsync(c->cover.d_cov, 0, (n_ref ? n_ref : 1) * sizeof(dsb_ref_coverage), c->stream));
+	if (c->cover.win) {                                        // (one state: the windows describe the reads the bitmap does)
+		HIPCHK(hipMemsetAsync(c->cover.d_win, 0, (c->cover.n_win ? c->cover.n_win : 1) * 16, c->stream));
+		HIPCHK(hipMemsetAsync(c->cover.d_wcov, 0, (c->cover.n_win ? c->cover.n_win : 1) * 8, c->stream));
+	}
 	HIPCHK(hipStreamSynchronize(c->stream));
 	return DSB_OK;
 }
@@ -627,6 +730,105 @@ extern "C" int dsb_ctx_coverage(dsb_ctx *c, dsb_ref_coverage *out)
 	HIPCHK(hipMemcpyAsync(out, c->cover.d_cov, n_ref * sizeof(dsb_ref_coverage), hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(hipStreamSynchronize(c->stream));
 	return DSB_OK;
+}
+
+// ---- per-window coverage ----
+extern "C" uint64_t dsb_coverage_n_windows(const dsb_index *idx, uint32_t window)
+{
+	if (!idx || !window) return 0;
+	const uint64_t n_ref = dsb_index_n_ref(idx);
+	uint64_t n = 0;
+	for (uint64_t r = 0; r < n_ref; r++) { const uint64_t ln = dsb_index_ref_len(idx, (uint32_t)r); n += ln / window + (ln % window != 0); }
+	return n;
+}
+
+extern "C" int dsb_ctx_enable_coverage_windows(dsb_ctx *c, uint32_t window)
+{
+	if (!c) return DSB_EINVAL;
+	HIPCHK(hipSetDevice(c->device));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	windows_free(c);
+	if (!window) return DSB_OK;
+	if (!c->cover.d_cov) return DSB_EINVAL;
+	const size_t n_ref = (size_t)dsb_index_n_ref(c->idx);
+	std::vector<uint64_t> first(n_ref + 1, 0);
+	for (size_t r = 0; r < n_ref; r++) { const uint64_t ln = dsb_index_ref_len(c->idx, (uint32_t)r); first[r + 1] = first[r] + ln / window + (ln % window != 0); }
+	const uint64_t nw = first[n_ref];
+	if (nw > (uint64_t)1 << 58) return DSB_ENOMEM;             // (24 bytes each)
+	if (hipMalloc((void **)&c->cover.d_first, first.size() * 8) != hipSuccess || hipMalloc((void **)&c->cover.d_win, (size_t)(nw ? nw : 1) * 16) != hipSuccess ||
+	    hipMalloc((void **)&c->cover.d_wcov, (size_t)(nw ? nw : 1) * 8) != hipSuccess) {
+		windows_free(c); (void)hipGetLastError(); return DSB_ENOMEM;
+	}
+	c->cover.win = window; c->cover.n_win = nw;
+	HIPCHK(hipMemcpy(c->cover.d_first, first.data(), first.size() * 8, hipMemcpyHostToDevice));
+	return dsb_ctx_reset_coverage(c);                          // bitmap, counters and windows: the same reads from here on
+}
+
+// covbases of the windows met by words [w0, w0 + nw) of the bitmap, held in bits[0 .. nw), added to c's covbases slots
+static void window_count(dsb_ctx *c, const uint64_t *bits, uint64_t w0, uint64_t nw, hipStream_t st)
+{
+	if (!nw) return;
+	const uint64_t waves = (nw + DSB_COVER_CHUNK - 1) / DSB_COVER_CHUNK;
+	hipLaunchKernelGGL(k_window_count, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, bits, w0, nw, (const uint64_t *)c->cover.d_off, (const uint64_t *)c->cover.d_len,
+	                   (const uint64_t *)c->cover.d_first, (uint32_t)dsb_index_n_ref(c->idx), c->cover.win, c->cover.d_wcov);
+}
+static void window_clear(dsb_ctx *c, hipStream_t st)
+{
+	if (!c->cover.n_win) return;
+	hipLaunchKernelGGL(k_window_clear, dim3((unsigned)std::min<uint64_t>((c->cover.n_win + 255) / 256, 8192)), dim3(256), 0, st, c->cover.d_wcov, c->cover.n_win);
+}
+
+// the n windows to the host: {starts, aligned_bases} from sa (on the current device) and covbases from wcov, a piece at a time through two
+// staging vectors, all on stream st
+static int windows_deliver(hipStream_t st, const uint64_t *sa, const uint64_t *wcov, uint64_t n, dsb_cov_window *out)
+{
+	const uint64_t piece = (uint64_t)1 << 20;
+	std::vector<uint64_t> h_sa((size_t)std::min(n, piece) * 2), h_cb((size_t)std::min(n, piece));
+	for (uint64_t j0 = 0; j0 < n; j0 += piece) {
+		const uint64_t k = n - j0 < piece ? n - j0 : piece;
+		HIPCHK(hipMemcpyAsync(h_sa.data(), sa + 2 * j0, k * 16, hipMemcpyDeviceToHost, st));
+		HIPCHK(hipMemcpyAsync(h_cb.data(), wcov + j0, k * 8, hipMemcpyDeviceToHost, st));
+		HIPCHK(hipStreamSynchronize(st));
+		for (uint64_t j = 0; j < k; j++) { dsb_cov_window &o = out[j0 + j]; o.starts = h_sa[2 * j]; o.aligned_bases = h_sa[2 * j + 1]; o.covbases = h_cb[j]; }
+	}
+	return DSB_OK;
+}
+
+extern "C" int dsb_ctx_coverage_windows(dsb_ctx *c, dsb_cov_window *out, size_t cap, size_t *n)
+{
+	if (!c || !n || !c->cover.win) return DSB_EINVAL;
+	*n = (size_t)c->cover.n_win;
+	if (!out) return DSB_OK;                                   // (count only)
+	if (cap < *n) return DSB_ECAP;
+	HIPCHK(hipSetDevice(c->device));
+	// on the ctx's stream, as dsb_ctx_coverage: k_ref_windows leaves the covbases slots alone, so a batch behind this changes nothing here
+	window_clear(c, c->stream);
+	window_count(c, c->cover.d_bits, 0, c->cover.words, c->stream);
+	HIPCHK(hipGetLastError());
+	return windows_deliver(c->stream, c->cover.d_win, c->cover.d_wcov, c->cover.n_win, out);
+}
+
+extern "C" long dsb_coverage_windows_format(const dsb_index *x, const dsb_ref_coverage *cov, const dsb_cov_window *win, uint32_t window, char *buf, size_t cap)
+{
+	if (!x || !cov || !win || !window || (!buf && cap)) return -1;
+	size_t o = 0; int w;
+#define EMIT(...) do { w = snprintf(buf + o, cap > o ? cap - o : 0, __VA_ARGS__); if (w < 0 || (size_t)w >= (cap > o ? cap - o : 0)) return -1; o += (size_t)w; } while (0)
+	EMIT("#rname\tstart\tend\tnumreads\tcovbases\tcoverage\tmeandepth\n");
+	const uint64_t n_ref = dsb_index_n_ref(x);
+	uint64_t first = 0;
+	for (uint64_t r = 0; r < n_ref; r++) {
+		const uint64_t ln = dsb_index_ref_len(x, (uint32_t)r), nw = ln / window + (ln % window != 0);
+		if (cov[r].numreads)
+			for (uint64_t j = 0; j < nw; j++) {
+				const dsb_cov_window &c = win[first + j];
+				const uint64_t s = j * window, e = s + window < ln ? s + window : ln;
+				EMIT("%s\t%llu\t%llu\t%llu\t%llu\t%g\t%g\n", dsb_index_ref_name(x, (uint32_t)r), (unsigned long long)s, (unsigned long long)e, (unsigned long long)c.starts,
+				     (unsigned long long)c.covbases, 100.0 * (double)c.covbases / (double)(e - s), (double)c.aligned_bases / (double)(e - s));
+			}
+		first += nw;
+	}
+#undef EMIT
+	return (long)o;
 }
 
 // ---- per-reference abundance ----
@@ -1045,6 +1247,10 @@ int reductions_run(dsb_ctx *c, const DsbBatchView &b)
 		// the per-reference coverage, after the same launches, whether or not a taxonomy is attached
 		hipLaunchKernelGGL(k_ref_cover, dim3((b.n + 3) / 4), dim3(256), 0, b.st, DSB_BATCH_HITS(b), b.n, (const uint64_t *)c->cover.d_len, (const uint64_t *)c->cover.d_off,
 		                   n_ref, c->cover.d_bits, c->cover.d_cov);
+		// and, when windows are on, the per-window starts and aligned bases of the same records
+		if (c->cover.win)
+			hipLaunchKernelGGL(k_ref_windows, dim3((b.n + 3) / 4), dim3(256), 0, b.st, DSB_BATCH_HITS(b), b.n, (const uint64_t *)c->cover.d_len, (const uint64_t *)c->cover.d_first,
+			                   n_ref, c->cover.win, c->cover.d_win);
 	}
 	if (c->em.d_cnt) {
 		// the candidate sets of the batch's reads, after the same launches.  Room for n records and for every hit the buffer can
@@ -1131,34 +1337,22 @@ extern "C" int dsb_multi_enable_coverage(dsb_multi *m, int on)
 	return multi_enable(m, [&](dsb_ctx *c, bool en) { return dsb_ctx_enable_coverage(c, en ? on : 0); });
 }
 
-// The contexts' coverage merged: the counters are added on the host; the bitmaps are ORed chunk by chunk into a buffer on the first
-// context's device -- read in place where a context shares that device, copied over (copy_to) where it does not -- and
-// each chunk is counted there.  The contexts' own bitmaps are left as they are.
-extern "C" int dsb_multi_coverage(dsb_multi *m, dsb_ref_coverage *out)
+// The contexts' bitmaps ORed chunk by chunk into a buffer on the first context's device -- read in place where a context shares
+// that device, copied over (copy_to) where it does not -- and each chunk counted there, on the first context's stream: per reference
+// into its covbases counters (refs), per window into its covbases slots (wins), both cleared first.  The contexts' own bitmaps are left
+// as they are; the caller has waited for every context's stream, and waits for the first one's before T, which holds the buffers, goes.
+static int multi_cover_count(dsb_multi *m, DevScratch &T, bool refs, bool wins)
 {
-	if (!m || !out || m->ctx.empty()) return DSB_EINVAL;
-	for (dsb_ctx *c : m->ctx) if (!c->cover.d_cov) return DSB_EINVAL;
 	dsb_ctx *c0 = m->ctx[0];
-	if (m->ctx.size() == 1) return dsb_ctx_coverage(c0, out);
 	const uint32_t n_ref = (uint32_t)dsb_index_n_ref(m->idx);
-	if (!n_ref) return DSB_OK;
-	memset(out, 0, n_ref * sizeof *out);
-	std::vector<dsb_ref_coverage> part(n_ref);
 	bool remote = false;
-	for (dsb_ctx *c : m->ctx) {
-		HIPCHK(hipSetDevice(c->device));
-		HIPCHK(hipStreamSynchronize(c->stream));
-		HIPCHK(hipMemcpy(part.data(), c->cover.d_cov, n_ref * sizeof(dsb_ref_coverage), hipMemcpyDeviceToHost));
-		for (uint32_t r = 0; r < n_ref; r++) { out[r].numreads += part[r].numreads; out[r].aligned_bases += part[r].aligned_bases; out[r].mapq_sum += part[r].mapq_sum; }
-		remote |= c->device != c0->device;
-	}
-	HIPCHK(hipSetDevice(c0->device));
+	for (dsb_ctx *c : m->ctx) remote |= c->device != c0->device;
 	const uint64_t nw = c0->cover.words, chunk = nw < (4ull << 20) ? nw : (4ull << 20);   // (32 MiB of words per chunk)
-	DevScratch T;
 	uint64_t *acc = nw ? T.get<uint64_t>(chunk) : nullptr, *buf = nw && remote ? T.get<uint64_t>(chunk) : nullptr;
 	if (nw && (!acc || (remote && !buf))) return DSB_ENOMEM;
 	const hipStream_t st = c0->stream;
-	hipLaunchKernelGGL(k_cover_clear, dim3((n_ref + 255) / 256), dim3(256), 0, st, c0->cover.d_cov, n_ref);
+	if (refs) hipLaunchKernelGGL(k_cover_clear, dim3((n_ref + 255) / 256), dim3(256), 0, st, c0->cover.d_cov, n_ref);
+	if (wins) window_clear(c0, st);
 	int rc = DSB_OK;
 	for (uint64_t w0 = 0; w0 < nw && !rc; w0 += chunk) {
 		const uint64_t k = nw - w0 < chunk ? nw - w0 : chunk;
@@ -1173,14 +1367,87 @@ extern "C" int dsb_multi_coverage(dsb_multi *m, dsb_ref_coverage *out)
 			}
 			hipLaunchKernelGGL(k_cover_or, dim3(grid), dim3(256), 0, st, acc, src, k);
 		}
-		if (!rc) cover_count(c0, acc, w0, k, st);
+		if (!rc && refs) cover_count(c0, acc, w0, k, st);
+		if (!rc && wins) window_count(c0, acc, w0, k, st);    // (a window cut by the chunk's end gets its other part from the next chunk)
 	}
 	if (!rc && hipGetLastError() != hipSuccess) rc = DSB_ENODEV;
+	return rc;
+}
+
+// The contexts' coverage merged: the counters are added on the host; covbases is counted from the merged bitmap (multi_cover_count).
+extern "C" int dsb_multi_coverage(dsb_multi *m, dsb_ref_coverage *out)
+{
+	if (!m || !out || m->ctx.empty()) return DSB_EINVAL;
+	for (dsb_ctx *c : m->ctx) if (!c->cover.d_cov) return DSB_EINVAL;
+	dsb_ctx *c0 = m->ctx[0];
+	if (m->ctx.size() == 1) return dsb_ctx_coverage(c0, out);
+	const uint32_t n_ref = (uint32_t)dsb_index_n_ref(m->idx);
+	if (!n_ref) return DSB_OK;
+	memset(out, 0, n_ref * sizeof *out);
+	std::vector<dsb_ref_coverage> part(n_ref);
+	for (dsb_ctx *c : m->ctx) {
+		HIPCHK(hipSetDevice(c->device));
+		HIPCHK(hipStreamSynchronize(c->stream));
+		HIPCHK(hipMemcpy(part.data(), c->cover.d_cov, n_ref * sizeof(dsb_ref_coverage), hipMemcpyDeviceToHost));
+		for (uint32_t r = 0; r < n_ref; r++) { out[r].numreads += part[r].numreads; out[r].aligned_bases += part[r].aligned_bases; out[r].mapq_sum += part[r].mapq_sum; }
+	}
+	HIPCHK(hipSetDevice(c0->device));
+	const hipStream_t st = c0->stream;
+	DevScratch T;
+	int rc = multi_cover_count(m, T, true, false);
 	if (!rc && hipMemcpyAsync(part.data(), c0->cover.d_cov, n_ref * sizeof(dsb_ref_coverage), hipMemcpyDeviceToHost, st) != hipSuccess) rc = DSB_ENODEV;
 	if (hipStreamSynchronize(st) != hipSuccess) rc = DSB_ENODEV;
 	if (rc) return rc;
 	for (uint32_t r = 0; r < n_ref; r++) out[r].covbases = part[r].covbases;
 	return DSB_OK;
+}
+
+extern "C" int dsb_multi_enable_coverage_windows(dsb_multi *m, uint32_t window)
+{
+	if (!m) return DSB_EINVAL;
+	return multi_enable(m, [&](dsb_ctx *c, bool en) { return dsb_ctx_enable_coverage_windows(c, en ? window : 0); });
+}
+
+// The contexts' windows merged: starts and aligned_bases are added into a table on the first context's device (k_lca_add is the u64
+// vector add; a context on another device is copied over first), covbases is counted per window from the merged bitmap
+// (multi_cover_count) into the first context's slots.  Integer sums and a union: what one context would have counted.
+extern "C" int dsb_multi_coverage_windows(dsb_multi *m, dsb_cov_window *out, size_t cap, size_t *n)
+{
+	if (!m || !n || m->ctx.empty()) return DSB_EINVAL;
+	dsb_ctx *c0 = m->ctx[0];
+	for (dsb_ctx *c : m->ctx) if (!c->cover.win || c->cover.win != c0->cover.win) return DSB_EINVAL;
+	if (m->ctx.size() == 1) return dsb_ctx_coverage_windows(c0, out, cap, n);
+	const uint64_t nwin = c0->cover.n_win;
+	*n = (size_t)nwin;
+	if (!out) return DSB_OK;                                   // (count only)
+	if (cap < *n) return DSB_ECAP;
+	if (!nwin) return DSB_OK;
+	bool remote = false;
+	for (dsb_ctx *c : m->ctx) {
+		HIPCHK(hipSetDevice(c->device));
+		HIPCHK(hipStreamSynchronize(c->stream));                // (the context's counters and bitmap are final)
+		remote |= c->device != c0->device;
+	}
+	HIPCHK(hipSetDevice(c0->device));
+	const hipStream_t st = c0->stream;
+	DevScratch T;
+	uint64_t *acc = T.get<uint64_t>(2 * nwin), *buf = remote ? T.get<uint64_t>(2 * nwin) : nullptr;
+	if (!acc || (remote && !buf)) return DSB_ENOMEM;
+	int rc = copy_to(acc, c0->device, c0->cover.d_win, c0->device, nwin * 16, st) == hipSuccess ? DSB_OK : DSB_ENODEV;
+	const unsigned grid = (unsigned)std::min<uint64_t>((2 * nwin + 255) / 256, 8192);
+	for (size_t i = 1; i < m->ctx.size() && !rc; i++) {
+		const dsb_ctx *c = m->ctx[i];
+		const uint64_t *src = c->cover.d_win;
+		if (c->device != c0->device) {
+			if (copy_to(buf, c0->device, src, c->device, nwin * 16, st) != hipSuccess) { rc = DSB_ENODEV; break; }
+			src = buf;
+		}
+		hipLaunchKernelGGL(k_lca_add, dim3(grid), dim3(256), 0, st, (unsigned long long *)acc, (const unsigned long long *)src, 2 * nwin);
+	}
+	if (!rc) rc = multi_cover_count(m, T, false, true);
+	if (!rc) rc = windows_deliver(st, acc, c0->cover.d_wcov, nwin, out);
+	if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = DSB_ENODEV;
+	return rc;
 }
 extern "C" int dsb_multi_enable_abundance(dsb_multi *m, int on, uint32_t min_permille)
 {

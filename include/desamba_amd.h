@@ -300,6 +300,38 @@ int  dsb_multi_coverage(dsb_multi *m, dsb_ref_coverage *out);  /* merged over th
  * numreads > 0, in ref_ID order.  Same return convention as dsb_format_sam. */
 long dsb_coverage_format(const dsb_index *idx, const dsb_ref_coverage *cov, char *buf, size_t cap);
 
+/* ---- per-window coverage: where on each reference the counted records lie.
+ * Window size W >= 1 bases.  Window j of reference r (LN = dsb_index_ref_len(r)) is [jW, min((j + 1)W, LN)), 0-based half-open, in the
+ * coordinates POS prints; r has ceil(LN / W) windows (none for LN 0), and the windows of all references form one array in which r's
+ * begin at first_r, the prefix sum of ceil(LN / W) in ref_ID order.  Counted are exactly the records of dsb_ref_coverage, each with
+ * its clipped interval [s, e) = [min(t_st, LN), min(t_ed, LN)); a record with e <= s adds to no window (it still counts in its
+ * reference's numreads).  Over the windows of a reference, aligned_bases and covbases sum to the reference's, and starts to its
+ * numreads minus its records with an empty interval.  Integers that do not depend on how the reads are split into batches, slots
+ * or contexts. */
+typedef struct {
+	uint64_t starts;          /* counted records with e > s whose s lies in the window */
+	uint64_t aligned_bases;   /* sum over the counted records of the length of [s, e) within the window */
+	uint64_t covbases;        /* bases of the window in the union of those intervals */
+} dsb_cov_window;
+uint64_t dsb_coverage_n_windows(const dsb_index *idx, uint32_t window);   /* the array's length; 0 for window 0 */
+/* Windows are part of the coverage state (one bitmap, shared with dsb_ctx_coverage): coverage must be on, else DSB_EINVAL.
+ * window > 0: allocate 24 bytes per window (DSB_ENOMEM if it does not fit; coverage stays on, windows off) and zero the WHOLE
+ * coverage state as dsb_ctx_reset_coverage does -- also when windows were on already, with this or another size -- so bitmap,
+ * per-reference counters and windows always describe the same reads.  window 0: off, freed; the rest of the state stays.
+ * dsb_ctx_reset_coverage zeroes the windows too, dsb_ctx_enable_coverage(ctx, 0) frees them.  While windows are on, every batch
+ * ends with k_ref_windows behind k_ref_cover; while they are off nothing is allocated or launched. */
+int  dsb_ctx_enable_coverage_windows(dsb_ctx *ctx, uint32_t window);
+/* *n = the number of windows; out NULL: that only; cap < *n: DSB_ECAP; windows off: DSB_EINVAL.  Everything since enable / reset.
+ * Fetching changes nothing on the device but the covbases slots it recomputes and does not disturb a batch in flight. */
+int  dsb_ctx_coverage_windows(dsb_ctx *ctx, dsb_cov_window *out, size_t cap, size_t *n);
+int  dsb_multi_enable_coverage_windows(dsb_multi *m, uint32_t window);
+int  dsb_multi_coverage_windows(dsb_multi *m, dsb_cov_window *out, size_t cap, size_t *n);   /* merged over the contexts: what one context would count */
+/* a header line "#rname start end numreads covbases coverage meandepth" (tabs), then for every reference with cov[r].numreads > 0,
+ * in ref_ID order, all its windows in order, those with all zeros included: start / end the window's bounds (BED convention),
+ * numreads = starts, coverage = 100 covbases / (end - start) and meandepth = aligned_bases / (end - start), both as %g.  win: the
+ * dsb_coverage_n_windows(idx, window) windows.  Same return convention as dsb_format_sam. */
+long dsb_coverage_windows_format(const dsb_index *idx, const dsb_ref_coverage *cov, const dsb_cov_window *win, uint32_t window, char *buf, size_t cap);
+
 /* ---- per-reference abundance of a run by expectation-maximisation on the GPU.
  * Every read with hits (those dsb_batch_fetch hands out, whatever max_sec_N is) has a candidate set: the references r < n_ref
  * whose best AS S_r has S_r * 1000 >= S_max * min_permille (S_max: the read's best AS), ascending, each once.  Reads are not
