@@ -32,7 +32,7 @@ struct UpStage { char *buf[2] = {nullptr, nullptr}; hipEvent_t ev[2] = {nullptr,
 // change them on a living context): nothing on the per-batch path calls getenv.  -1 / 0 = not set.
 struct DsbKnobs {
 	bool upload_text = false;          // DSB_UPLOAD_TEXT: dsb_batch_upload gathers the sequences as text (round 3's form) instead of packing them
-	bool debug = false, upload_trace = false, no_turn = false, turn_whole_run = false, no_group = false, heavy_first_set = false;
+	bool debug = false, upload_trace = false, no_turn = false, no_group = false, heavy_first_set = false;
 	long hout_cap = 0, sms_cap = 0, anc_cap_rt = 0, upload_chunk_kb = 0, step_limit_rt = 0, group_head = -1;
 	int upload_threads = 0, seed_scan = -1, heavy_mw = -1, heavy_first = 0;
 	bool heavy_preds_set = false; uint32_t heavy_preds = 0;
@@ -53,13 +53,13 @@ struct dsb_ctx {
 	DsbWordDesc *d_wd = nullptr; uint8_t *d_bin = nullptr; uint64_t *d_pk = nullptr; uint64_t *d_bits = nullptr;
 	size_t cap_wd = 0, cap_bin = 0, cap_pk = 0, cap_bits = 0;
 	DsbReadOut *d_rout = nullptr; DsbHitOut *d_hout = nullptr; size_t cap_rout = 0, cap_hout = 0;
-	unsigned int *d_counters = nullptr;            // u32: [0] work, [1] hits, [2..3] u64 table-1 probes, [4] early work, [6] listed reads, [7] work of the second run, [8] third run list, [9] its work; u64 x 4 at +16 (main launch), +24 (early launch), +32 (second runs): occ, MEM searches, SA lookups, reference bases
+	DsbCounters *d_counters = nullptr;             // the batch's counter block (dsb_device.h)
 	DsbSlotArena arena; int n_slots = 0, n_extra = 0;   // n_extra: slots behind the n_slots of the main launch, for the early launch of the heaviest reads (batches of >= 4096 reads)
 	DsbSlotArena arena_big; int n_slots_big = 0;  // second run of reads that outgrew an arena or their loop budget
 	DsbSlotArena arena_anc; int n_slots_anc = 0;  // k_anchor's slots (only the island walk's scratch)
 	DsbAncRec *d_arec = nullptr; DsbAnchor *d_apool = nullptr; size_t cap_arec = 0, cap_apool = 0;   // k_anchor's per-read records and anchor pool
 	uint32_t hint_len = 0;                           // the read length the caller announced (dsb_opts.max_read_len): arenas are never built for less
-	unsigned mw_reads = 16; bool mw_grown = false; int mw_calm = 0;   // reads of the early launch that get eight wavefronts each: follows what the batches of this ctx show (end of dsb_batch_run)
+	unsigned mw_reads = 16; bool mw_grown = false; int mw_calm = 0;   // reads of the early launch that get eight wavefronts each: follows what the batches of this ctx show (stage_adapt_mw)
 	uint32_t *d_score = nullptr, *d_order = nullptr, *d_heavy = nullptr; size_t cap_score = 0, cap_order = 0, cap_heavy = 0;
 	DsbSeed *d_seeds = nullptr; DsbSeedInfo *d_sinfo = nullptr; size_t cap_seeds = 0, cap_sinfo = 0;   // seed lists of the batch (k_seed_scan)
 	uint8_t *d_summ = nullptr; int summ_shift = 0;   // summary of exist table 0 in use (the staged index's, or none with synthetic tables)
@@ -69,7 +69,7 @@ struct dsb_ctx {
 	std::vector<DsbReadOut> h_rout; std::vector<DsbHitOut> h_hout;
 	std::vector<dsb_read_result> res_reads;
 	int hist_max = 0;
-	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; dsb_timing timing; unsigned long long p1 = 0;
+	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; dsb_timing timing;
 	hipStream_t stream3 = nullptr; hipEvent_t ev_heavy3 = nullptr;    // k_classify_heavy: several wavefronts on each of the very heaviest reads
 	hipStream_t stream2 = nullptr; hipEvent_t ev_order = nullptr, ev_heavy = nullptr, ev_hprobe = nullptr, ev_cls = nullptr, ev_cls_wait = nullptr;   // the heaviest reads run beside the seed probe
 	uint32_t *dbg_host = nullptr, *dbg_dev = nullptr;

@@ -81,6 +81,30 @@ struct DsbReadOut { uint32_t first, n; int32_t status; uint32_t fast; uint32_t n
 // the loop steps the walk spent and whether k_classify takes them (use = 0: it walks the islands itself, as without k_anchor)
 struct DsbAncRec { uint32_t off, n, lsteps, use; };
 
+// ---- the counter block of a batch (dsb_ctx::d_counters) -----------------------------------------
+// 256 bytes, zeroed at the start of every run.  The kernels get pointers to single members; the host copies the block back whole.
+struct DsbWorkStats { unsigned long long occ, mem, sa, ref_bases; };     // occ() calls, MEM searches, SA lookups, reference bases read
+struct DsbCounters {
+	unsigned int work_main;                   // work counter of the main k_classify
+	unsigned int hits;                        // hits the device wanted to write (dsb_hits_out / dsb_hits_cut)
+	unsigned long long probes_t1;             // table-1 probes of k_seed_probe
+	unsigned int work_early, pad5;            // work counter of k_classify_early
+	unsigned int n_retry, work_retry;         // reads listed for the second run; its work counter
+	unsigned int n_regrow, work_regrow;       // reads listed after a regrown hit buffer; that run's work counter
+	unsigned int work_mw, pad11;              // work counter of the early k_classify_heavy<8> launch
+	unsigned int n_heavy, work_heavy;         // reads given up as heavy (listed); work counter of their pass
+	unsigned int work_anchor, anc_pool_asked; // k_anchor's work counter; anchors it asked its pool for
+	DsbWorkStats st_main, st_early, st_rerun; // main launch (and k_anchor); early launch and both k_classify_heavy launches; second and third runs
+	unsigned long long scan_windows, scan_probes_t1;   // k_seed_scan: windows probed, probes that went on to table 1
+	unsigned int pad44[20];
+};
+#define DSB_CNT_AT(m, w) static_assert(offsetof(DsbCounters, m) == 4 * (w), "DsbCounters: " #m " moved")
+static_assert(sizeof(DsbCounters) == 256, "DsbCounters is 64 u32 words");
+DSB_CNT_AT(work_main, 0); DSB_CNT_AT(hits, 1); DSB_CNT_AT(probes_t1, 2); DSB_CNT_AT(work_early, 4); DSB_CNT_AT(n_retry, 6); DSB_CNT_AT(work_retry, 7);
+DSB_CNT_AT(n_regrow, 8); DSB_CNT_AT(work_regrow, 9); DSB_CNT_AT(work_mw, 10); DSB_CNT_AT(n_heavy, 12); DSB_CNT_AT(work_heavy, 13); DSB_CNT_AT(work_anchor, 14);
+DSB_CNT_AT(anc_pool_asked, 15); DSB_CNT_AT(st_main, 16); DSB_CNT_AT(st_early, 24); DSB_CNT_AT(st_rerun, 32); DSB_CNT_AT(scan_windows, 40); DSB_CNT_AT(scan_probes_t1, 42);
+#undef DSB_CNT_AT
+
 // ---- batch descriptors ----------------------------------------------------------------------
 struct DsbReadDesc {
 	uint64_t seq_off;      // into the ASCII blob

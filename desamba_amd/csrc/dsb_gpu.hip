@@ -903,7 +903,7 @@ static void knobs_read(DsbKnobs &k)
 	k = DsbKnobs();
 	k.debug = getenv("DSB_DEBUG") != nullptr; k.upload_trace = getenv("DSB_UPLOAD_TRACE") != nullptr;
 	k.upload_text = getenv("DSB_UPLOAD_TEXT") != nullptr;
-	k.no_turn = getenv("DSB_NO_TURN") != nullptr; k.turn_whole_run = getenv("DSB_TURN_WHOLE_RUN") != nullptr; k.no_group = getenv("DSB_NO_GROUP") != nullptr;
+	k.no_turn = getenv("DSB_NO_TURN") != nullptr; k.no_group = getenv("DSB_NO_GROUP") != nullptr;
 	k.hout_cap = num("DSB_HOUT_CAP", 0); if (getenv("DSB_HOUT_CAP") && k.hout_cap <= 0) k.hout_cap = 1;
 	k.sms_cap = num("DSB_SMS_CAP", 0); if (getenv("DSB_SMS_CAP") && k.sms_cap < 64) k.sms_cap = 64;
 	k.anc_cap_rt = num("DSB_ANC_CAP_RT", 0); if (getenv("DSB_ANC_CAP_RT")) { if (k.anc_cap_rt < 64) k.anc_cap_rt = 64; if (k.anc_cap_rt > DSB_ANC_CAP) k.anc_cap_rt = DSB_ANC_CAP; }
@@ -1007,7 +1007,7 @@ extern "C" int dsb_ctx_create(dsb_index *idx, int device_id, const dsb_opts *opt
 	if (rc == DSB_OK) {
 		c->dx = c->staged->dx; c->d_summ = c->staged->d_summ; c->summ_shift = c->staged->summ_shift; c->ek_dense = c->staged->ek_dense;
 		c->dx.filter_min_length = c->opts.L_min_matching; c->dx.filter_min_score = c->opts.min_score; c->dx.filter_min_score_LV3 = c->opts.min_score + 10;
-		if (hipMalloc((void **)&c->d_counters, 256) != hipSuccess) rc = DSB_ENOMEM;
+		if (hipMalloc((void **)&c->d_counters, sizeof(DsbCounters)) != hipSuccess) rc = DSB_ENOMEM;
 	}
 	if (rc == DSB_OK && c->knobs.debug) {
 		CK(hipHostMalloc((void **)&c->dbg_host, 32 * 65536 * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
@@ -1492,46 +1492,97 @@ extern "C" long dsb_batch_upload_fastq(dsb_ctx *c, const char *path, size_t skip
 
 // (group mode of k_classify: batches whose reads are all at most this long take 64 reads per work item)
 #define DSB_GROUP_MAX_LEN 400u
+
+// What a run decides before its first launch (batch_plan); the stages of batch_run_locked only read it
+struct BatchPlan {
+	bool dbg;                          // DSB_DEBUG: stage dumps, a synchronisation after every stage
+	unsigned n_heavy, n_mw;            // reads of the early launch; those of them that get eight wavefronts each
+	bool use_scan, grp, anc_k;         // seed lookup by k_seed_scan (else: hit bits); group mode; k_anchor in front of the main k_classify
+	unsigned slots;                    // grid of the main k_classify
+	uint32_t step_limit;
+	DsbDevIndex dx1, dxh, dx2;         // of the first-run launches; of the pass over reads given up as heavy; of the second and third runs
+};
+static BatchPlan batch_plan(const dsb_ctx *c, const InSlot &s)
+{
+	BatchPlan p; const size_t n = s.n_reads;
+	p.dbg = c->knobs.debug && c->dbg_dev;
+	// Head start for the tail: the kernel's duration is the duration of its heaviest read (tandem repeats: minutes of
+	// sparse DP on the CPU, ~0.2 s here).  The first n_heavy reads of the LPT order get their probes and their own
+	// k_classify launch on the second stream right away, beside the main seed probe, instead of after it.
+	p.n_heavy = 0;
+	if (!p.dbg && s.n_words_total && !c->seed_only) {
+		p.n_heavy = c->knobs.heavy_first_set ? (unsigned)c->knobs.heavy_first : (n >= 4096 ? (unsigned)(n / 64) : 0u);
+		if (p.n_heavy > (unsigned)c->n_extra) p.n_heavy = (unsigned)c->n_extra;
+		if (p.n_heavy > n / 2) p.n_heavy = (unsigned)(n / 2);
+	}
+	// the very heaviest of them (DSB_HEAVY_MW; by default 16, more once the batches of this ctx have ended in their tails,
+	// see stage_adapt_mw) get eight wavefronts each (k_classify_heavy) on a third stream
+	p.n_mw = 0;
+	if (p.n_heavy) {
+		p.n_mw = c->knobs.heavy_mw >= 0 ? (unsigned)c->knobs.heavy_mw : c->mw_reads;
+		if (p.n_mw > p.n_heavy) p.n_mw = p.n_heavy;
+	}
+	// Seed lookup of the main launch: k_seed_scan (a lane per strand, only the windows the reference's scan consumes, seed
+	// lists written by the kernel) for batches that fill the device, the all-windows probe + in-kernel scan of the hit
+	// bits otherwise (a strand is a serial chain of ~7000 round trips: a small batch would wait for it).  DSB_SEED_SCAN=0/1
+	// forces one or the other.  The early launch of the heaviest reads always takes the hit-bit path.
+	p.use_scan = n >= 2048;
+	if (c->knobs.seed_scan >= 0) p.use_scan = c->knobs.seed_scan != 0;
+	p.step_limit = DSB_STEP_LIMIT;
+	if (c->knobs.step_limit_rt > 0) p.step_limit = (uint32_t)c->knobs.step_limit_rt;   // diagnostics: a small budget forces second runs
+	p.dx1 = c->dx; p.dx1.sms_cap = c->arena.sms_cap; p.dx1.step_limit = p.step_limit;
+	// a read whose sparse DP scans more predecessors than this on one wavefront is given up there and run again by a
+	// workgroup of 8 wavefronts (k_classify_heavy) after the main launch; DSB_HEAVY_PREDS=0 switches that off
+	p.dx1.heavy_limit = DSB_HEAVY_PREDS;
+	if (p.dbg) p.dx1.heavy_limit = 0;                             // (stage dumps describe whole reads, unless the limit is asked for)
+	if (c->knobs.heavy_preds_set) p.dx1.heavy_limit = c->knobs.heavy_preds;
+	p.dxh = p.dx1; p.dxh.heavy_limit = 0;
+	p.dx2 = c->dx; p.dx2.sms_cap = c->arena_big.sms_cap; p.dx2.heavy_limit = 0; p.dx2.step_limit = p.step_limit > 0xffffffffu / 16 ? 0xffffffffu : p.step_limit * 16u;
+	p.slots = (unsigned)c->n_slots; if (p.slots > n - p.n_heavy) p.slots = (unsigned)(n - p.n_heavy);
+	// The anchor stage of the main launch's reads first, as a kernel of its own (k_anchor; timing.classify_ms covers both).  Not for
+	// stage dumps, short-read batches (group mode has its own anchor stage) and the hit-bit path (no seed lists).
+	p.grp = s.max_len <= DSB_GROUP_MAX_LEN && !c->knobs.no_group;
+	p.anc_k = p.use_scan && !p.dbg && !p.grp && c->knobs.anchor_kernel && c->arena_anc.base && c->n_slots_anc > 0 && c->arena_anc.anc_cap == c->arena.anc_cap
+	          && c->d_arec && c->cap_arec >= n && c->d_apool && n > p.n_heavy;
+	return p;
+}
+
 // one k_classify-family launch
 template <class K>
-static void launch_classify(K kern, dsb_ctx *c, hipStream_t st, unsigned grid, const DsbDevIndex &dx, const InSlot &s, uint32_t n_fixed, const unsigned int *n_ptr,
-                            const uint32_t *list, const DsbSlotArena &ar, unsigned int *work_counter, uint32_t *dbg, uint32_t item_base, uint32_t slot_base, int cnt_set,
+static void launch_classify(K kern, dsb_ctx *c, const InSlot &s, const BatchPlan &p, hipStream_t st, unsigned grid, const DsbDevIndex &dx, uint32_t n_fixed, const unsigned int *n_ptr,
+                            const uint32_t *list, const DsbSlotArena &ar, unsigned int *work_counter, uint32_t *dbg, uint32_t item_base, uint32_t slot_base, DsbWorkStats *stats,
                             bool pre_seeds, const DsbAncRec *arec = nullptr, const DsbAnchor *apool = nullptr)
 {
 	hipLaunchKernelGGL(kern, dim3(grid), dim3(64), 0, st, dx, (const DsbReadDesc *)s.d_rd, n_fixed, n_ptr, list, c->d_bin, (const uint64_t *)c->d_bits, ar, work_counter,
-	                   c->d_rout, c->d_hout, c->d_counters + 1, (uint32_t)c->cap_hout, dbg, item_base, slot_base, (unsigned long long *)(c->d_counters + 16 + 8 * cnt_set),
-	                   pre_seeds ? c->d_seeds : nullptr, (const DsbSeedInfo *)c->d_sinfo, (const uint64_t *)c->d_pk, (uint32_t)((pre_seeds && s.max_len <= DSB_GROUP_MAX_LEN && !c->knobs.no_group) ? (c->knobs.group_head >= 0 ? (unsigned)c->knobs.group_head : 8u * grid) : 0u), arec, apool);
+	                   c->d_rout, c->d_hout, &c->d_counters->hits, (uint32_t)c->cap_hout, dbg, item_base, slot_base, &stats->occ,
+	                   pre_seeds ? c->d_seeds : nullptr, (const DsbSeedInfo *)c->d_sinfo, (const uint64_t *)c->d_pk, (uint32_t)((pre_seeds && p.grp) ? (c->knobs.group_head >= 0 ? (unsigned)c->knobs.group_head : 8u * grid) : 0u), arec, apool);
+}
+// one k_classify_heavy launch (a workgroup of 8 wavefronts per read), in the slots of the main arena from slot_base on; its statistics go with the early launch's
+static void launch_heavy(dsb_ctx *c, const InSlot &s, hipStream_t st, unsigned grid, const DsbDevIndex &dx, uint32_t n_fixed, const unsigned int *n_ptr, const uint32_t *list,
+                         unsigned int *work_counter, uint32_t slot_base, bool pre_seeds)
+{
+	hipLaunchKernelGGL(k_classify_heavy<8>, dim3(grid), dim3(64 * 8), 0, st, dx, (const DsbReadDesc *)s.d_rd, n_fixed, n_ptr, list, c->d_bin,
+	                   (const uint64_t *)c->d_bits, c->arena, work_counter, c->d_rout, c->d_hout, &c->d_counters->hits, (uint32_t)c->cap_hout, slot_base,
+	                   &c->d_counters->st_early.occ, (const uint64_t *)c->d_pk, pre_seeds ? c->d_seeds : (DsbSeed *)nullptr, (const DsbSeedInfo *)c->d_sinfo);
+}
+// the reads whose status has a bit of `mask` are listed on the device (n_list of them) and run again from scratch in the big arena; an empty list drains at once
+static void launch_second(dsb_ctx *c, const InSlot &s, const BatchPlan &p, unsigned int *n_list, unsigned int *work_counter, int mask)
+{
+	hipLaunchKernelGGL(k_collect_retry, dim3((unsigned)((s.n_reads + 255) / 256)), dim3(256), 0, c->stream, (const DsbReadOut *)c->d_rout, (uint32_t)s.n_reads, c->d_score, n_list, mask, 0);
+	launch_classify(k_classify_second, c, s, p, c->stream, (unsigned)c->n_slots_big, p.dx2, 0u, n_list, (const uint32_t *)c->d_score, c->arena_big, work_counter, nullptr, 0u, 0u, &c->d_counters->st_rerun, p.use_scan);
 }
 
-static int batch_run_locked(dsb_ctx *c, std::unique_lock<std::mutex> *turn);
-extern "C" int dsb_batch_run(dsb_ctx *c)
+// ---- the stages of a run, in the order batch_run_locked calls them ----
+static int stage_encode_order(dsb_ctx *c, InSlot &s, const BatchPlan &p)
 {
-	if (!c) return DSB_EINVAL;
-	// Contexts that share a device take turns with their kernels: two batches side by side run 1.25x as long as one after
-	// the other (two persistent launches halve each other's wave slots and both end in their tails), while the uploads and
-	// fetches of the waiting context still overlap the running one's kernels -- which is what the second context is for.
-	if (c->staged && !c->knobs.no_turn) { std::unique_lock<std::mutex> g(c->staged->run_mu); return batch_run_locked(c, &g); }
-	return batch_run_locked(c, nullptr);
-}
-static int batch_run_locked(dsb_ctx *c, std::unique_lock<std::mutex> *turn)
-{
-	HIPCHK(hipSetDevice(c->device));
-	InSlot &s = c->in[c->cur];
-	size_t n = s.n_reads;
-	const bool ord_set = s.ord_set; s.ord_set = false;         // (dsb_ctx_set_batch_ordinal holds for this run alone)
-	memset(&c->timing, 0, sizeof c->timing);
-	c->timing.upload_bytes = s.upload_bytes;
-	c->taxa.run = c->taxa.tx != nullptr && n == 0; c->taxa.done = false;
-	c->lca.run = c->lca.d_direct != nullptr && n == 0; c->lca.done = false;
-	if (n == 0) return DSB_OK;
-	HIPCHK(hipMemsetAsync(c->d_counters, 0, 256, c->stream));
+	const size_t n = s.n_reads;
+	HIPCHK(hipMemsetAsync(c->d_counters, 0, sizeof(DsbCounters), c->stream));
 	HIPCHK(hipEventRecord(c->ev[0], c->stream));
 	if (s.packed) hipLaunchKernelGGL(k_encode_bytes_pk, dim3((unsigned)n), dim3(256), 0, c->stream, s.d_rd, (const uint8_t *)s.d_ascii, c->d_bin);
 	else hipLaunchKernelGGL(k_encode_bytes, dim3((unsigned)n), dim3(256), 0, c->stream, s.d_rd, s.d_ascii, c->d_bin);
 	hipLaunchKernelGGL(k_encode_pack, dim3((unsigned)n), dim3(256), 0, c->stream, s.d_rd, c->d_bin, c->d_pk);
 	HIPCHK(hipEventRecord(c->ev[1], c->stream));
-	const bool dbg = c->knobs.debug && c->dbg_dev;
-	if (dbg) { HIPCHK(hipStreamSynchronize(c->stream)); fprintf(stderr, "[dsb] encode done\n"); }
+	if (p.dbg) { HIPCHK(hipStreamSynchronize(c->stream)); fprintf(stderr, "[dsb] encode done\n"); }
 	// the LPT order needs only the packed reads.  (Run beside the seed probe its scoring kernel takes 90 ms instead
 	// of 12: both stream the packed reads.)
 	hipLaunchKernelGGL(k_repeat_score, dim3((unsigned)n), dim3(256), 0, c->stream, s.d_rd, c->d_pk, c->d_score);
@@ -1545,193 +1596,155 @@ static int batch_run_locked(dsb_ctx *c, std::unique_lock<std::mutex> *turn)
 		HIPCHK(hipStreamSynchronize(c->stream));
 	}
 	HIPCHK(hipEventRecord(c->ev_order, c->stream));
-	// Head start for the tail: the kernel's duration is the duration of its heaviest read (tandem repeats: minutes of
-	// sparse DP on the CPU, ~0.2 s here).  The first n_heavy reads of the LPT order get their probes and their own
-	// k_classify launch on the second stream right away, beside the main seed probe, instead of after it.
-	unsigned n_heavy = 0;
-	if (!dbg && s.n_words_total && !c->seed_only) {
-		n_heavy = c->knobs.heavy_first_set ? (unsigned)c->knobs.heavy_first : (n >= 4096 ? (unsigned)(n / 64) : 0u);
-		if (n_heavy > (unsigned)c->n_extra) n_heavy = (unsigned)c->n_extra;
-		if (n_heavy > n / 2) n_heavy = (unsigned)(n / 2);
+	return DSB_OK;
+}
+static int stage_early(dsb_ctx *c, InSlot &s, const BatchPlan &p)
+{
+	if (!p.n_heavy) return DSB_OK;
+	// their probes first, alone on the device (about a millisecond), then their classify launch on the second stream
+	hipLaunchKernelGGL(k_seed_probe_reads, dim3(p.n_heavy * DSB_HPROBE_SPLIT), dim3(256), 0, c->stream, c->dx, (const DsbReadDesc *)s.d_rd, (const uint32_t *)c->d_order, c->d_pk, c->d_bits, c->d_summ, c->summ_shift);
+	HIPCHK(hipEventRecord(c->ev_hprobe, c->stream));
+	HIPCHK(hipEventRecord(c->ev_order, c->stream));             // order_ms covers scoring, ordering and these probes
+	if (p.n_mw) {
+		HIPCHK(hipStreamWaitEvent(c->stream3, c->ev_hprobe, 0));
+		launch_heavy(c, s, c->stream3, p.n_mw, p.dx1, (uint32_t)p.n_mw, nullptr, (const uint32_t *)c->d_order, &c->d_counters->work_mw, (uint32_t)c->n_slots, false);
+		HIPCHK(hipEventRecord(c->ev_heavy3, c->stream3));
 	}
-	c->n_early = n_heavy;
-	// Seed lookup of the main launch: k_seed_scan (a lane per strand, only the windows the reference's scan consumes, seed
-	// lists written by the kernel) for batches that fill the device, the all-windows probe + in-kernel scan of the hit
-	// bits otherwise (a strand is a serial chain of ~7000 round trips: a small batch would wait for it).  DSB_SEED_SCAN=0/1
-	// forces one or the other.  The early launch of the heaviest reads always takes the hit-bit path.
-	bool use_scan = n >= 2048;
-	if (c->knobs.seed_scan >= 0) use_scan = c->knobs.seed_scan != 0;
-	c->bits_valid = !use_scan; c->seeds_valid = use_scan;
-	uint32_t step_limit = DSB_STEP_LIMIT;
-	if (c->knobs.step_limit_rt > 0) step_limit = (uint32_t)c->knobs.step_limit_rt;   // diagnostics: a small budget forces second runs
-	DsbDevIndex dx1 = c->dx; dx1.sms_cap = c->arena.sms_cap; dx1.step_limit = step_limit;
-	// a read whose sparse DP scans more predecessors than this on one wavefront is given up there and run again by a
-	// workgroup of 8 wavefronts (k_classify_heavy) after the main launch; DSB_HEAVY_PREDS=0 switches that off
-	dx1.heavy_limit = DSB_HEAVY_PREDS;
-	if (dbg) dx1.heavy_limit = 0;                                 // (stage dumps describe whole reads, unless the limit is asked for)
-	if (c->knobs.heavy_preds_set) dx1.heavy_limit = c->knobs.heavy_preds;
-	if (n_heavy) {
-		// their probes first, alone on the device (about a millisecond), then their classify launch on the second stream
-		hipLaunchKernelGGL(k_seed_probe_reads, dim3(n_heavy * DSB_HPROBE_SPLIT), dim3(256), 0, c->stream, c->dx, (const DsbReadDesc *)s.d_rd, (const uint32_t *)c->d_order, c->d_pk, c->d_bits, c->d_summ, c->summ_shift);
-		HIPCHK(hipEventRecord(c->ev_hprobe, c->stream));
-		HIPCHK(hipEventRecord(c->ev_order, c->stream));             // order_ms covers scoring, ordering and these probes
-		// the very heaviest of them (DSB_HEAVY_MW; by default 16, more once the batches of this ctx have ended in their tails,
-		// see the end of this function) get eight wavefronts each (k_classify_heavy) on a third stream
-		unsigned n_mw = c->mw_reads;
-		if (c->knobs.heavy_mw >= 0) n_mw = (unsigned)c->knobs.heavy_mw;
-		if (n_mw > n_heavy) n_mw = n_heavy;
-		c->timing.n_heavy_mw = n_mw;
-		if (n_mw) {
-			HIPCHK(hipStreamWaitEvent(c->stream3, c->ev_hprobe, 0));
-			hipLaunchKernelGGL(k_classify_heavy<8>, dim3(n_mw), dim3(64 * 8), 0, c->stream3, dx1, (const DsbReadDesc *)s.d_rd, (uint32_t)n_mw, (const unsigned int *)nullptr, (const uint32_t *)c->d_order, c->d_bin,
-			                   (const uint64_t *)c->d_bits, c->arena, c->d_counters + 10, c->d_rout, c->d_hout, c->d_counters + 1, (uint32_t)c->cap_hout, (uint32_t)c->n_slots,
-			                   (unsigned long long *)(c->d_counters + 16 + 8), (const uint64_t *)c->d_pk, (DsbSeed *)nullptr, (const DsbSeedInfo *)c->d_sinfo);
-			HIPCHK(hipEventRecord(c->ev_heavy3, c->stream3));
-		}
-		HIPCHK(hipStreamWaitEvent(c->stream2, c->ev_hprobe, 0));
-		if (n_heavy > n_mw)
-			launch_classify(k_classify_early, c, c->stream2, n_heavy - n_mw, dx1, s, (uint32_t)n_heavy, nullptr, (const uint32_t *)c->d_order, c->arena, c->d_counters + 4, nullptr, n_mw, (uint32_t)c->n_slots + n_mw, 1, false);
-		HIPCHK(hipEventRecord(c->ev_heavy, c->stream2));
-	}
-	if (use_scan) {
+	HIPCHK(hipStreamWaitEvent(c->stream2, c->ev_hprobe, 0));
+	if (p.n_heavy > p.n_mw)
+		launch_classify(k_classify_early, c, s, p, c->stream2, p.n_heavy - p.n_mw, p.dx1, (uint32_t)p.n_heavy, nullptr, (const uint32_t *)c->d_order, c->arena, &c->d_counters->work_early, nullptr, p.n_mw, (uint32_t)c->n_slots + p.n_mw, &c->d_counters->st_early, false);
+	HIPCHK(hipEventRecord(c->ev_heavy, c->stream2));
+	return DSB_OK;
+}
+static int stage_seed_lookup(dsb_ctx *c, InSlot &s, const BatchPlan &p)
+{
+	const size_t n = s.n_reads;
+	if (p.use_scan) {
 		hipLaunchKernelGGL(k_seed_scan, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), 0, c->stream, c->dx, (const DsbReadDesc *)s.d_rd, (const uint32_t *)(s.ragged ? s.d_scan_order : nullptr),
-		                   (uint32_t)n, (const uint64_t *)c->d_pk, c->d_seeds, c->d_sinfo, (const uint8_t *)c->d_summ, c->summ_shift, (unsigned long long *)(c->d_counters + 40),
+		                   (uint32_t)n, (const uint64_t *)c->d_pk, c->d_seeds, c->d_sinfo, (const uint8_t *)c->d_summ, c->summ_shift, &c->d_counters->scan_windows,
 		                   c->knobs.scan_look_set ? c->knobs.scan_look : dsb_scan_look_for((c->dx.ek_mask + 1) / 8, c->ek_dense));
 	} else if (s.n_words_total) {
 		uint64_t waves = (s.n_words_total + DSB_PROBE_UN - 1) / DSB_PROBE_UN; unsigned blocks = (unsigned)((waves + 3) / 4);
 		if (blocks > 256u * 32u) blocks = 256u * 32u;       // >= 8 blocks of 4 waves per CU, grid-stride beyond
 		hipLaunchKernelGGL(k_build_wd, dim3((unsigned)n), dim3(256), 0, c->stream, s.d_rd, c->d_wd);
 		hipLaunchKernelGGL(k_seed_probe, dim3(blocks), dim3(256), 0, c->stream, c->dx, (const DsbReadDesc *)s.d_rd, (const DsbWordDesc *)c->d_wd, s.n_words_total, c->d_pk, c->d_bits,
-		                   (unsigned long long *)(c->d_counters + 2), c->d_summ, c->summ_shift);
+		                   &c->d_counters->probes_t1, c->d_summ, c->summ_shift);
 	}
 	HIPCHK(hipEventRecord(c->ev[2], c->stream));
-	if (c->seed_only) {
-		// synthetic filter tables (dsb_ctx_use_synthetic_filter): the measurement ends here
-		HIPCHK(hipStreamSynchronize(c->stream));
-		hipEventElapsedTime(&c->timing.encode_ms, c->ev[0], c->ev[1]);
-		hipEventElapsedTime(&c->timing.order_ms, c->ev[1], c->ev_order);
-		hipEventElapsedTime(&c->timing.seed_probe_ms, c->ev_order, c->ev[2]);
-		unsigned long long pc[2] = {0, 0};
-		HIPCHK(hipMemcpy(pc, use_scan ? c->d_counters + 40 : c->d_counters + 2, use_scan ? 16 : 8, hipMemcpyDeviceToHost));
-		c->timing.windows = use_scan ? pc[0] : s.total_windows; c->timing.probes_t1 = use_scan ? pc[1] : pc[0]; c->timing.bases = s.total_bases;
-		c->timing.seed_scan = use_scan ? 1 : 0; c->timing.total_ms = c->timing.encode_ms + c->timing.order_ms + c->timing.seed_probe_ms;
-		return DSB_OK;
+	return DSB_OK;
+}
+static int stage_main(dsb_ctx *c, InSlot &s, const BatchPlan &p)
+{
+	const size_t n = s.n_reads;
+	if (p.dbg) { HIPCHK(hipStreamSynchronize(c->stream)); fprintf(stderr, "[dsb] seed probe done\n"); }
+	uint32_t *dbgp = p.dbg ? c->dbg_dev : nullptr;
+	if (p.dbg) memset(c->dbg_host, 0, 32 * 65536 * sizeof(uint32_t));
+	if (p.anc_k) {
+		unsigned ga = (unsigned)c->n_slots_anc; if (ga > n - p.n_heavy) ga = (unsigned)(n - p.n_heavy);
+		hipLaunchKernelGGL(k_anchor, dim3(ga), dim3(64), 0, c->stream, p.dx1, (const DsbReadDesc *)s.d_rd, (uint32_t)n, (uint32_t)p.n_heavy, (const uint32_t *)c->d_order, c->d_bin, c->arena_anc,
+		                   &c->d_counters->work_anchor, c->d_seeds, (const DsbSeedInfo *)c->d_sinfo, c->d_arec, c->d_apool, &c->d_counters->anc_pool_asked, (uint32_t)c->cap_apool, &c->d_counters->st_main.occ);
 	}
-	if (dbg) { HIPCHK(hipStreamSynchronize(c->stream)); fprintf(stderr, "[dsb] seed probe done\n"); }
-	unsigned slots = (unsigned)c->n_slots; if (slots > n - n_heavy) slots = (unsigned)(n - n_heavy);
-	{
-		uint32_t *dbgp = dbg ? c->dbg_dev : nullptr;
-		if (dbg) memset(c->dbg_host, 0, 32 * 65536 * sizeof(uint32_t));
-		// The anchor stage of the main launch's reads first, as a kernel of its own (k_anchor; timing.classify_ms covers both).  Not for
-		// stage dumps, short-read batches (group mode has its own anchor stage) and the hit-bit path (no seed lists).
-		const bool grp = s.max_len <= DSB_GROUP_MAX_LEN && !c->knobs.no_group;
-		const bool anc_k = use_scan && !dbg && !grp && c->knobs.anchor_kernel && c->arena_anc.base && c->n_slots_anc > 0 && c->arena_anc.anc_cap == c->arena.anc_cap
-		                   && c->d_arec && c->cap_arec >= n && c->d_apool && n > n_heavy;
-		if (anc_k) {
-			unsigned ga = (unsigned)c->n_slots_anc; if (ga > n - n_heavy) ga = (unsigned)(n - n_heavy);
-			hipLaunchKernelGGL(k_anchor, dim3(ga), dim3(64), 0, c->stream, dx1, (const DsbReadDesc *)s.d_rd, (uint32_t)n, (uint32_t)n_heavy, (const uint32_t *)c->d_order, c->d_bin, c->arena_anc,
-			                   c->d_counters + 14, c->d_seeds, (const DsbSeedInfo *)c->d_sinfo, c->d_arec, c->d_apool, c->d_counters + 15, (uint32_t)c->cap_apool, (unsigned long long *)(c->d_counters + 16));
-		}
-		launch_classify(k_classify, c, c->stream, slots, dx1, s, (uint32_t)n, nullptr, (const uint32_t *)c->d_order, c->arena, c->d_counters, dbgp, (uint32_t)n_heavy, 0u, 0, use_scan,
-		                anc_k ? c->d_arec : nullptr, anc_k ? c->d_apool : nullptr);
-		HIPCHK(hipEventRecord(c->ev_cls, c->stream));
-		HIPCHK(hipEventRecord(c->ev_cls_wait, c->stream));
-		if (n_heavy) { HIPCHK(hipStreamWaitEvent(c->stream, c->ev_heavy, 0)); if (c->timing.n_heavy_mw) HIPCHK(hipStreamWaitEvent(c->stream, c->ev_heavy3, 0)); }
-		if (dbg) {
-			// watchdog: poll the stream; dump the progress words of every slot if the kernel runs long
-			for (int sec = 0; sec < 60; sec++) {
-				if (hipStreamQuery(c->stream) == hipSuccess) break;
-				usleep(1000000);
-				if (sec % 5 == 4) {
-					fprintf(stderr, "[dsb] classify still running after %d s; slot: code steps read\n", sec + 1);
-					for (unsigned sI = 0; sI < slots && sI < 24; sI++) fprintf(stderr, "   slot %u: %u %u %u\n", sI, c->dbg_host[4 * sI], c->dbg_host[4 * sI + 1], c->dbg_host[4 * sI + 2]);
-				}
+	launch_classify(k_classify, c, s, p, c->stream, p.slots, p.dx1, (uint32_t)n, nullptr, (const uint32_t *)c->d_order, c->arena, &c->d_counters->work_main, dbgp, (uint32_t)p.n_heavy, 0u, &c->d_counters->st_main, p.use_scan,
+	                p.anc_k ? c->d_arec : nullptr, p.anc_k ? c->d_apool : nullptr);
+	HIPCHK(hipEventRecord(c->ev_cls, c->stream));
+	HIPCHK(hipEventRecord(c->ev_cls_wait, c->stream));
+	if (p.n_heavy) { HIPCHK(hipStreamWaitEvent(c->stream, c->ev_heavy, 0)); if (p.n_mw) HIPCHK(hipStreamWaitEvent(c->stream, c->ev_heavy3, 0)); }
+	if (p.dbg) {
+		// watchdog: poll the stream; dump the progress words of every slot if the kernel runs long
+		for (int sec = 0; sec < 60; sec++) {
+			if (hipStreamQuery(c->stream) == hipSuccess) break;
+			usleep(1000000);
+			if (sec % 5 == 4) {
+				fprintf(stderr, "[dsb] classify still running after %d s; slot: code steps read\n", sec + 1);
+				for (unsigned sI = 0; sI < p.slots && sI < 24; sI++) fprintf(stderr, "   slot %u: %u %u %u\n", sI, c->dbg_host[4 * sI], c->dbg_host[4 * sI + 1], c->dbg_host[4 * sI + 2]);
 			}
 		}
 	}
+	return DSB_OK;
+}
+static int stage_reruns(dsb_ctx *c, InSlot &s, const BatchPlan &p)
+{
 	// Second run.  The reference's per-read vectors are unbounded and it has no loop budget; a wave slot here holds 2 match
 	// nodes per base of the longest read (dsb_sms_cap_for), DSB_ANC_CAP anchors, DSB_HIT_CAP chains, and a read may spend
 	// DSB_STEP_LIMIT loop iterations.  Reads that outgrew any of these are listed on the device and run again from
 	// scratch in DSB_RETRY_SLOTS slots with DSB_RETRY_GROW times the match nodes, 8x the anchors, 4x the chains and 16x
-	// the budget; with an empty list the launch drains at once.  counters: [6] listed reads, [7] work counter of the second run.
+	// the budget; with an empty list the launch drains at once.
 	// Reads given up as heavy (DSB_ST_HEAVY): listed on the device, then one workgroup of 8 wavefronts per read in
-	// the slots the finished launches left free.  counters: [12] listed reads, [13] work counter.  An empty list drains at once.
-	if (dx1.heavy_limit) {
-		DsbDevIndex dxh = dx1; dxh.heavy_limit = 0;
+	// the slots the finished launches left free.  An empty list drains at once.
+	if (p.dx1.heavy_limit) {
 		unsigned gh = (unsigned)(c->n_slots + c->n_extra); if (gh > 256u) gh = 256u;
-		hipLaunchKernelGGL(k_collect_retry, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const DsbReadOut *)c->d_rout, (uint32_t)n, c->d_heavy, c->d_counters + 12, DSB_ST_HEAVY, 0);
-		hipLaunchKernelGGL(k_classify_heavy<8>, dim3(gh), dim3(64 * 8), 0, c->stream, dxh, (const DsbReadDesc *)s.d_rd, 0u, (const unsigned int *)(c->d_counters + 12), (const uint32_t *)c->d_heavy, c->d_bin,
-		                   (const uint64_t *)c->d_bits, c->arena, c->d_counters + 13, c->d_rout, c->d_hout, c->d_counters + 1, (uint32_t)c->cap_hout, 0u,
-		                   (unsigned long long *)(c->d_counters + 16 + 8), (const uint64_t *)c->d_pk, use_scan ? c->d_seeds : (DsbSeed *)nullptr, (const DsbSeedInfo *)c->d_sinfo);
+		hipLaunchKernelGGL(k_collect_retry, dim3((unsigned)((s.n_reads + 255) / 256)), dim3(256), 0, c->stream, (const DsbReadOut *)c->d_rout, (uint32_t)s.n_reads, c->d_heavy, &c->d_counters->n_heavy, DSB_ST_HEAVY, 0);
+		launch_heavy(c, s, c->stream, gh, p.dxh, 0u, &c->d_counters->n_heavy, (const uint32_t *)c->d_heavy, &c->d_counters->work_heavy, 0u, p.use_scan);
 	}
-	DsbDevIndex dx2 = c->dx; dx2.sms_cap = c->arena_big.sms_cap; dx2.heavy_limit = 0; dx2.step_limit = step_limit > 0xffffffffu / 16 ? 0xffffffffu : step_limit * 16u;
-	const int retry_mask = DSB_ST_SMS_OVF | DSB_ST_ANC_OVF | DSB_ST_HIT_OVF | DSB_ST_TIMEOUT;
-	hipLaunchKernelGGL(k_collect_retry, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const DsbReadOut *)c->d_rout, (uint32_t)n, c->d_score, c->d_counters + 6, retry_mask, 0);
-	launch_classify(k_classify_second, c, c->stream, (unsigned)c->n_slots_big, dx2, s, 0u, (const unsigned int *)(c->d_counters + 6), (const uint32_t *)c->d_score, c->arena_big, c->d_counters + 7, nullptr, 0u, 0u, 2, use_scan);
+	launch_second(c, s, p, &c->d_counters->n_retry, &c->d_counters->work_retry, DSB_ST_SMS_OVF | DSB_ST_ANC_OVF | DSB_ST_HIT_OVF | DSB_ST_TIMEOUT);
 	HIPCHK(hipEventRecord(c->ev[3], c->stream));
-	// The device's turn ends with the main launch: what may still follow it -- the early launch's last reads (tandem repeats: a
-	// handful of wavefronts), the pass over the reads given up as heavy, the second run -- leaves most of the device idle, and the
-	// other context's next batch starts with its HBM-bound seed lookup.  (DSB_TURN_WHOLE_RUN=1: the turn lasts to the end, as before.)
-	if (turn && !c->knobs.turn_whole_run) { HIPCHK(hipEventSynchronize(c->ev_cls_wait)); turn->unlock(); }
-	HIPCHK(hipEventSynchronize(c->ev[3]));
-	{
-		// The hit buffer holds 16 n + 4096 records (the reference's lists are unbounded).  The device counts every
-		// hit it wanted to write; if that is more than the buffer holds, the buffer is regrown (contents kept) and
-		// the reads that found it full run once more -- rare enough for a host round trip.
-		unsigned int cnt[2] = {0, 0};
-		HIPCHK(hipMemcpy(cnt, c->d_counters, 8, hipMemcpyDeviceToHost));
-		if (cnt[1] > c->cap_hout) {
-			const size_t new_cap = 2 * (size_t)cnt[1] + 4096;
-			DsbHitOut *nh = nullptr;
-			if (hipMalloc((void **)&nh, new_cap * sizeof(DsbHitOut)) != hipSuccess) return DSB_ENOMEM;
-			HIPCHK(hipMemcpy(nh, c->d_hout, c->cap_hout * sizeof(DsbHitOut), hipMemcpyDeviceToDevice));
-			hipFree(c->d_hout); c->d_hout = nh; c->cap_hout = new_cap;
-			hipLaunchKernelGGL(k_collect_retry, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const DsbReadOut *)c->d_rout, (uint32_t)n, c->d_score, c->d_counters + 8, DSB_ST_OUT_OVF, 0);
-			launch_classify(k_classify_second, c, c->stream, (unsigned)c->n_slots_big, dx2, s, 0u, (const unsigned int *)(c->d_counters + 8), (const uint32_t *)c->d_score, c->arena_big, c->d_counters + 9, nullptr, 0u, 0u, 2, use_scan);
-			HIPCHK(hipStreamSynchronize(c->stream));
-			unsigned int n3 = 0; HIPCHK(hipMemcpy(&n3, c->d_counters + 8, 4, hipMemcpyDeviceToHost));
-			c->timing.n_regrow = n3;
-		}
+	return DSB_OK;
+}
+static int stage_regrow(dsb_ctx *c, InSlot &s, const BatchPlan &p)
+{
+	// The hit buffer holds 16 n + 4096 records (the reference's lists are unbounded).  The device counts every
+	// hit it wanted to write; if that is more than the buffer holds, the buffer is regrown (contents kept) and
+	// the reads that found it full run once more -- rare enough for a host round trip.
+	DsbCounters h = {};
+	HIPCHK(hipMemcpy(&h, c->d_counters, offsetof(DsbCounters, probes_t1), hipMemcpyDeviceToHost));      // work_main and hits
+	if (h.hits <= c->cap_hout) return DSB_OK;
+	const size_t new_cap = 2 * (size_t)h.hits + 4096;
+	DsbHitOut *nh = nullptr;
+	if (hipMalloc((void **)&nh, new_cap * sizeof(DsbHitOut)) != hipSuccess) return DSB_ENOMEM;
+	HIPCHK(hipMemcpy(nh, c->d_hout, c->cap_hout * sizeof(DsbHitOut), hipMemcpyDeviceToDevice));
+	hipFree(c->d_hout); c->d_hout = nh; c->cap_hout = new_cap;
+	launch_second(c, s, p, &c->d_counters->n_regrow, &c->d_counters->work_regrow, DSB_ST_OUT_OVF);
+	HIPCHK(hipStreamSynchronize(c->stream));
+	return DSB_OK;
+}
+static void stage_debug_report(dsb_ctx *c, InSlot &s, const BatchPlan &p)
+{
+	if (!p.dbg) return;
+	const size_t n = s.n_reads;
+	static const char *nm[10] = {"seed_vector", "fast_classify", "resolve_tree", "slow+resolve", "hash_build", "sdp_middle", "sdp_right", "sdp_left", "sort/filter", "primary"};
+	double tot[10] = {0}, all = 0; unsigned sl = (unsigned)c->n_slots; if (sl > n) sl = (unsigned)n;
+	double sub[4] = {0};
+	for (unsigned sI = 0; sI < sl; sI++) { for (int i = 0; i < 10; i++) { tot[i] += c->dbg_host[4 * 65536 + 14 * sI + i]; all += c->dbg_host[4 * 65536 + 14 * sI + i]; } for (int i = 0; i < 4; i++) sub[i] += c->dbg_host[4 * 65536 + 14 * sI + 10 + i]; }
+	fprintf(stderr, "[dsb] inside sdp_right (ms, -DDSB_TIMERS builds): sdp_match %.1f  dp %.1f  combine %.1f | fast_classify commit phase %.1f\n", sub[0] / 1e3, sub[1] / 1e3, sub[2] / 1e3, sub[3] / 1e3);
+	{ double tx[10] = {0}; for (unsigned sI = 0; sI < sl; sI++) for (int i = 0; i < 10; i++) tx[i] += c->dbg_host[8 * 65536 + 10 * sI + i];
+	  fprintf(stderr, "[dsb] fine (ms, -DDSB_TIMERS builds): table build %.1f  probe %.1f  block DP: old predecessors %.1f, inside the block %.1f  sdp_match in sdp_left %.1f  dp in sdp_left %.1f  gap-per-lane phase of sdp_middle %.1f | of the old predecessors: beyond the first 64 (sdp_batch_old) %.1f in %.0f blocks; rounds over the first 64: %.0f\n",
+	          tx[0] / 1e3, tx[1] / 1e3, tx[2] / 1e3, tx[6] / 100.0 / 1e3, tx[3] / 1e3, tx[4] / 1e3, tx[5] / 1e3, tx[9] / 100.0 / 1e3, tx[7], tx[8]); }
+	{	// stage split of the slowest read of the batch (as it ran, i.e. under load)
+		size_t worst = 0; uint64_t wsum = 0;
+		for (size_t r = 0; r < n && r < 65536; r++) { uint64_t sm = 0; for (int i = 0; i < 10; i++) sm += c->dbg_host[16 * 65536 + 14 * r + i]; if (sm > wsum) { wsum = sm; worst = r; } }
+		fprintf(stderr, "[dsb] slowest read %zu: %.1f ms:", worst, wsum / 1e3);
+		for (int i = 0; i < 10; i++) fprintf(stderr, " %s %.1f", nm[i], c->dbg_host[16 * 65536 + 14 * worst + i] / 1e3);
+		fprintf(stderr, " | in right/left: sdp_match %.1f dp %.1f combine %.1f\n", c->dbg_host[16 * 65536 + 14 * worst + 10] / 1e3, c->dbg_host[16 * 65536 + 14 * worst + 11] / 1e3, c->dbg_host[16 * 65536 + 14 * worst + 12] / 1e3);
 	}
-	// the run reductions (dsb_reductions.hip), after every classify launch of the batch
-	const DsbBatchView hits = {c->stream, c->d_rout, c->d_hout, c->d_counters, c->cap_hout, s.d_rd, (uint32_t)n, ord_set, s.ord_first};
-	if (int rc = reductions_run(c, hits)) return rc;
-	if (dbg) {
-		static const char *nm[10] = {"seed_vector", "fast_classify", "resolve_tree", "slow+resolve", "hash_build", "sdp_middle", "sdp_right", "sdp_left", "sort/filter", "primary"};
-		double tot[10] = {0}, all = 0; unsigned sl = (unsigned)c->n_slots; if (sl > n) sl = (unsigned)n;
-		double sub[4] = {0};
-		for (unsigned sI = 0; sI < sl; sI++) { for (int i = 0; i < 10; i++) { tot[i] += c->dbg_host[4 * 65536 + 14 * sI + i]; all += c->dbg_host[4 * 65536 + 14 * sI + i]; } for (int i = 0; i < 4; i++) sub[i] += c->dbg_host[4 * 65536 + 14 * sI + 10 + i]; }
-		fprintf(stderr, "[dsb] inside sdp_right (ms, -DDSB_TIMERS builds): sdp_match %.1f  dp %.1f  combine %.1f | fast_classify commit phase %.1f\n", sub[0] / 1e3, sub[1] / 1e3, sub[2] / 1e3, sub[3] / 1e3);
-		{ double tx[10] = {0}; for (unsigned sI = 0; sI < sl; sI++) for (int i = 0; i < 10; i++) tx[i] += c->dbg_host[8 * 65536 + 10 * sI + i];
-		  fprintf(stderr, "[dsb] fine (ms, -DDSB_TIMERS builds): table build %.1f  probe %.1f  block DP: old predecessors %.1f, inside the block %.1f  sdp_match in sdp_left %.1f  dp in sdp_left %.1f  gap-per-lane phase of sdp_middle %.1f | of the old predecessors: beyond the first 64 (sdp_batch_old) %.1f in %.0f blocks; rounds over the first 64: %.0f\n",
-		          tx[0] / 1e3, tx[1] / 1e3, tx[2] / 1e3, tx[6] / 100.0 / 1e3, tx[3] / 1e3, tx[4] / 1e3, tx[5] / 1e3, tx[9] / 100.0 / 1e3, tx[7], tx[8]); }
-		{	// stage split of the slowest read of the batch (as it ran, i.e. under load)
-			size_t worst = 0; uint64_t wsum = 0;
-			for (size_t r = 0; r < n && r < 65536; r++) { uint64_t sm = 0; for (int i = 0; i < 10; i++) sm += c->dbg_host[16 * 65536 + 14 * r + i]; if (sm > wsum) { wsum = sm; worst = r; } }
-			fprintf(stderr, "[dsb] slowest read %zu: %.1f ms:", worst, wsum / 1e3);
-			for (int i = 0; i < 10; i++) fprintf(stderr, " %s %.1f", nm[i], c->dbg_host[16 * 65536 + 14 * worst + i] / 1e3);
-			fprintf(stderr, " | in right/left: sdp_match %.1f dp %.1f combine %.1f\n", c->dbg_host[16 * 65536 + 14 * worst + 10] / 1e3, c->dbg_host[16 * 65536 + 14 * worst + 11] / 1e3, c->dbg_host[16 * 65536 + 14 * worst + 12] / 1e3);
-		}
-		fprintf(stderr, "[dsb] classify stage time (wave-seconds, %% of total %.2f s):", all / 1e6);
-		for (int i = 0; i < 10; i++) fprintf(stderr, " %s %.1f%%", nm[i], 100.0 * tot[i] / (all > 0 ? all : 1));
-		fprintf(stderr, "\n");
-	}
-	HIPCHK(hipGetLastError());
-	hipEventElapsedTime(&c->timing.encode_ms, c->ev[0], c->ev[1]);
-	hipEventElapsedTime(&c->timing.order_ms, c->ev[1], c->ev_order);
-	hipEventElapsedTime(&c->timing.seed_probe_ms, c->ev_order, c->ev[2]);
-	hipEventElapsedTime(&c->timing.classify_ms, c->ev[2], c->ev_cls);       // the main k_classify launch alone
-	hipEventElapsedTime(&c->timing.tail_ms, c->ev_cls, c->ev[3]);           // waiting for the early launch, if it is still running
-	c->timing.n_early = c->n_early;
-	hipEventElapsedTime(&c->timing.total_ms, c->ev[0], c->ev[3]);
-	unsigned long long wk[12] = {0};                   // work counters: main launch, early launch, second runs
-	HIPCHK(hipMemcpy(&c->p1, c->d_counters + 2, 8, hipMemcpyDeviceToHost));
-	HIPCHK(hipMemcpy(&c->timing.n_retry, c->d_counters + 6, 4, hipMemcpyDeviceToHost));
-	{	// counters [12] reads handed over as heavy, [15] anchors k_anchor asked its pool for: one copy
-		unsigned int h[4] = {0, 0, 0, 0};
-		HIPCHK(hipMemcpy(h, c->d_counters + 12, sizeof h, hipMemcpyDeviceToHost));
-		c->timing.n_requeue = h[0]; c->timing.anc_pool_asked = h[3]; c->timing.anc_pool_cap = c->cap_apool;
-	}
+	fprintf(stderr, "[dsb] classify stage time (wave-seconds, %% of total %.2f s):", all / 1e6);
+	for (int i = 0; i < 10; i++) fprintf(stderr, " %s %.1f%%", nm[i], 100.0 * tot[i] / (all > 0 ? all : 1));
+	fprintf(stderr, "\n");
+}
+// timing of the run from its events and one copy of the counter block; a seed_only run ended with the seed lookup
+static int stage_timing(dsb_ctx *c, InSlot &s, const BatchPlan &p)
+{
+	dsb_timing &t = c->timing;
+	hipEventElapsedTime(&t.encode_ms, c->ev[0], c->ev[1]);
+	hipEventElapsedTime(&t.order_ms, c->ev[1], c->ev_order);
+	hipEventElapsedTime(&t.seed_probe_ms, c->ev_order, c->ev[2]);
+	DsbCounters h;
+	HIPCHK(hipMemcpy(&h, c->d_counters, sizeof h, hipMemcpyDeviceToHost));
+	// k_seed_scan counts the probes it issued (low-complexity windows excluded), and those that went on to table 1
+	t.windows = p.use_scan ? h.scan_windows : s.total_windows; t.probes_t1 = p.use_scan ? h.scan_probes_t1 : h.probes_t1; t.bases = s.total_bases;
+	t.seed_scan = p.use_scan ? 1 : 0;
+	if (c->seed_only) { t.total_ms = t.encode_ms + t.order_ms + t.seed_probe_ms; return DSB_OK; }
+	hipEventElapsedTime(&t.classify_ms, c->ev[2], c->ev_cls);       // the main k_classify launch alone
+	hipEventElapsedTime(&t.tail_ms, c->ev_cls, c->ev[3]);           // waiting for the early launch, if it is still running
+	hipEventElapsedTime(&t.total_ms, c->ev[0], c->ev[3]);
+	t.n_early = c->n_early; t.n_retry = h.n_retry; t.n_regrow = h.n_regrow; t.n_requeue = h.n_heavy;
+	t.anc_pool_asked = h.anc_pool_asked; t.anc_pool_cap = c->cap_apool;
+	const DsbWorkStats &a = h.st_main, &b = h.st_early, &d = h.st_rerun;
+	t.n_occ = a.occ + b.occ + d.occ; t.n_mem = a.mem + b.mem + d.mem; t.n_sa = a.sa + b.sa + d.sa; t.ref_bases = a.ref_bases + b.ref_bases + d.ref_bases;
+	t.main_occ = a.occ; t.main_mem = a.mem; t.main_sa = a.sa; t.main_ref_bases = a.ref_bases;
+	return DSB_OK;
+}
+static void stage_adapt_mw(dsb_ctx *c, InSlot &, const BatchPlan &)
+{
 	// A batch that made the device wait for its early launches (no read handed over, nothing run again: the wait was for the
 	// heaviest reads themselves -- on the demo index one read in a thousand lies in a tandem repeat and takes 150 ms on a
 	// wavefront, longer than the main launch) gets more of its heaviest reads onto eight wavefronts next time: 16 -> 32 -> 64.
@@ -1742,16 +1755,64 @@ static int batch_run_locked(dsb_ctx *c, std::unique_lock<std::mutex> *turn)
 		if (c->mw_reads < 64) c->mw_reads = c->mw_reads ? c->mw_reads * 2 : 16;
 		c->mw_grown = true; c->mw_calm = 0;
 	} else if (c->timing.tail_ms < 0.5f && !c->mw_grown && c->mw_reads && c->timing.n_early && ++c->mw_calm >= 4) c->mw_reads = 0;
-	HIPCHK(hipMemcpy(wk, c->d_counters + 16, 96, hipMemcpyDeviceToHost));
-	c->timing.windows = s.total_windows; c->timing.probes_t1 = c->p1; c->timing.bases = s.total_bases;
-	c->timing.seed_scan = use_scan ? 1 : 0;
-	if (use_scan) {	// probes the scan issued (low-complexity windows excluded), and those that went on to table 1
-		unsigned long long pc[2] = {0, 0};
-		HIPCHK(hipMemcpy(pc, c->d_counters + 40, 16, hipMemcpyDeviceToHost));
-		c->timing.windows = pc[0]; c->timing.probes_t1 = pc[1];
+}
+
+static int batch_run_locked(dsb_ctx *c, std::unique_lock<std::mutex> *turn);
+extern "C" int dsb_batch_run(dsb_ctx *c)
+{
+	if (!c) return DSB_EINVAL;
+	// Contexts that share a device take turns with their kernels: two batches side by side run 1.25x as long as one after
+	// the other (two persistent launches halve each other's wave slots and both end in their tails), while the uploads and
+	// fetches of the waiting context still overlap the running one's kernels -- which is what the second context is for.
+	if (c->staged && !c->knobs.no_turn) { std::unique_lock<std::mutex> g(c->staged->run_mu); return batch_run_locked(c, &g); }
+	return batch_run_locked(c, nullptr);
+}
+// The schedule of a batch on the device.  What must not move when a stage changes:
+//  - s.ord_set is consumed at entry, even for n == 0; the n == 0 exit sets taxa.run / lca.run (the reductions have nothing to launch)
+//  - ev_order is recorded twice when there is an early launch: the second record makes order_ms cover the heavy probes
+//  - ev_hprobe gates both extra streams (stream2: k_classify_early, stream3: k_classify_heavy<8>)
+//  - ev_cls and ev_cls_wait are recorded before the main stream waits on ev_heavy / ev_heavy3
+//  - the device turn is given up after ev_cls_wait, before the wait on ev[3]
+//  - the regrow decision reads the counters only after ev[3]; reductions_run comes after the regrow's third run
+//  - every early return (HIPCHK) releases the turn through the caller's unique_lock: no stage unlocks or keeps it
+static int batch_run_locked(dsb_ctx *c, std::unique_lock<std::mutex> *turn)
+{
+	HIPCHK(hipSetDevice(c->device));
+	InSlot &s = c->in[c->cur];
+	const size_t n = s.n_reads;
+	const bool ord_set = s.ord_set; s.ord_set = false;         // (dsb_ctx_set_batch_ordinal holds for this run alone)
+	memset(&c->timing, 0, sizeof c->timing);
+	c->timing.upload_bytes = s.upload_bytes;
+	c->taxa.run = c->taxa.tx != nullptr && n == 0; c->taxa.done = false;
+	c->lca.run = c->lca.d_direct != nullptr && n == 0; c->lca.done = false;
+	if (n == 0) return DSB_OK;
+	const BatchPlan p = batch_plan(c, s);
+	c->n_early = p.n_heavy; c->timing.n_heavy_mw = p.n_mw;
+	c->bits_valid = !p.use_scan; c->seeds_valid = p.use_scan;
+	int rc;
+	if ((rc = stage_encode_order(c, s, p))) return rc;
+	if ((rc = stage_early(c, s, p))) return rc;
+	if ((rc = stage_seed_lookup(c, s, p))) return rc;
+	if (c->seed_only) {
+		// synthetic filter tables (dsb_ctx_use_synthetic_filter): the measurement ends here
+		HIPCHK(hipStreamSynchronize(c->stream));
+		return stage_timing(c, s, p);
 	}
-	c->timing.n_occ = wk[0] + wk[4] + wk[8]; c->timing.n_mem = wk[1] + wk[5] + wk[9]; c->timing.n_sa = wk[2] + wk[6] + wk[10]; c->timing.ref_bases = wk[3] + wk[7] + wk[11];
-	c->timing.main_occ = wk[0]; c->timing.main_mem = wk[1]; c->timing.main_sa = wk[2]; c->timing.main_ref_bases = wk[3];
+	if ((rc = stage_main(c, s, p))) return rc;
+	if ((rc = stage_reruns(c, s, p))) return rc;
+	// The device's turn ends with the main launch: what may still follow it -- the early launch's last reads (tandem repeats: a
+	// handful of wavefronts), the pass over the reads given up as heavy, the second run -- leaves most of the device idle, and the
+	// other context's next batch starts with its HBM-bound seed lookup.
+	if (turn) { HIPCHK(hipEventSynchronize(c->ev_cls_wait)); turn->unlock(); }
+	HIPCHK(hipEventSynchronize(c->ev[3]));
+	if ((rc = stage_regrow(c, s, p))) return rc;
+	// the run reductions (dsb_reductions.hip), after every classify launch of the batch
+	const DsbBatchView hits = {c->stream, c->d_rout, c->d_hout, c->d_counters, c->cap_hout, s.d_rd, (uint32_t)n, ord_set, s.ord_first};
+	if ((rc = reductions_run(c, hits))) return rc;
+	stage_debug_report(c, s, p);
+	HIPCHK(hipGetLastError());
+	if ((rc = stage_timing(c, s, p))) return rc;
+	stage_adapt_mw(c, s, p);
 	return DSB_OK;
 }
 
@@ -1761,13 +1822,13 @@ extern "C" int dsb_batch_fetch(dsb_ctx *c, dsb_result *out)
 	HIPCHK(hipSetDevice(c->device));
 	const size_t n = c->in[c->cur].n_reads;
 	c->h_rout.resize(n); c->res_reads.resize(n);
-	unsigned int cnt[2] = {0, 0};
+	DsbCounters h = {};
 	if (n) {
-		HIPCHK(hipMemcpyAsync(cnt, c->d_counters, 8, hipMemcpyDeviceToHost, c->stream));
+		HIPCHK(hipMemcpyAsync(&h, c->d_counters, offsetof(DsbCounters, probes_t1), hipMemcpyDeviceToHost, c->stream));      // work_main and hits
 		HIPCHK(hipMemcpyAsync(c->h_rout.data(), c->d_rout, n * sizeof(DsbReadOut), hipMemcpyDeviceToHost, c->stream));
 		HIPCHK(hipStreamSynchronize(c->stream));
 	}
-	const size_t nh = dsb_hits_out(cnt[1], c->cap_hout);
+	const size_t nh = dsb_hits_out(h.hits, c->cap_hout);
 	c->h_hout.resize(nh);
 	if (nh) HIPCHK(hipMemcpyAsync(c->h_hout.data(), c->d_hout, nh * sizeof(DsbHitOut), hipMemcpyDeviceToHost, c->stream));
 	// The hits of a read lie together in the device's hit buffer, in the order the reads finished; dsb_hit has the

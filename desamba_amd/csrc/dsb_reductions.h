@@ -53,7 +53,7 @@ struct DsbLca {
 // a batch's results on the device after its last classify launch (the second runs and the run after a regrown hit buffer included)
 struct DsbBatchView {
 	hipStream_t st;
-	const DsbReadOut *rout; const DsbHitOut *hout; const unsigned int *counters; size_t cap_hout;
+	const DsbReadOut *rout; const DsbHitOut *hout; const DsbCounters *counters; size_t cap_hout;
 	const DsbReadDesc *rd; uint32_t n;
 	bool ord_set; uint64_t ord_first;             // dsb_ctx_set_batch_ordinal was called for this batch / with this ordinal
 };

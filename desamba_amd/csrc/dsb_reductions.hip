@@ -16,13 +16,13 @@
 // host must walk itself is flagged DSB_TAXON_HOST: a first record with score 0 or a taxid above max_tid (the read ends
 // there and its other records become reads of their own), a reference whose name does not come back from the SAM as it
 // is, or a walk that ran out of steps.
-__global__ void __launch_bounds__(256) k_read_taxon(const DsbReadOut *__restrict__ rout, const DsbHitOut *__restrict__ hout, const unsigned int *__restrict__ counters,
+__global__ void __launch_bounds__(256) k_read_taxon(const DsbReadOut *__restrict__ rout, const DsbHitOut *__restrict__ hout, const DsbCounters *__restrict__ counters,
                                                     uint32_t cap_hout, const DsbReadDesc *__restrict__ rd, uint32_t n, const uint32_t *__restrict__ parent,
                                                     const uint32_t *__restrict__ ref_tid, uint32_t n_ref, uint32_t max_tid, uint32_t bound, int max_sec, dsb_read_taxon *__restrict__ out)
 {
 	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
 	if (i >= n) return;
-	const uint32_t nh = dsb_hits_out(counters[1], cap_hout);
+	const uint32_t nh = dsb_hits_out(counters->hits, cap_hout);
 	const DsbReadOut r = rout[i];
 	dsb_read_taxon t; t.taxid = 0; t.score = 0; t.len = 0; t.mapq = 0; t.flags = 0; t.pad = 0;
 	const uint32_t nrec = dsb_hits_cut(r.first, r.n, nh) ? 0u : r.n;
@@ -61,13 +61,13 @@ __global__ void __launch_bounds__(256) k_read_taxon(const DsbReadOut *__restrict
 // [min(t_st, LN), min(t_ed, LN)), the lanes striding over its words.  The bits are set by agent-scope atomic ORs, never by plain
 // stores: two records may share a word, and their workgroups may sit on XCDs whose L2s are not coherent with each other.  A
 // reference's bits start at word word_off[ref]; bits at LN and beyond are never set.
-__global__ void __launch_bounds__(256) k_ref_cover(const DsbReadOut *__restrict__ rout, const DsbHitOut *__restrict__ hout, const unsigned int *__restrict__ counters,
+__global__ void __launch_bounds__(256) k_ref_cover(const DsbReadOut *__restrict__ rout, const DsbHitOut *__restrict__ hout, const DsbCounters *__restrict__ counters,
                                                    uint32_t cap_hout, uint32_t n, const uint64_t *__restrict__ ref_len, const uint64_t *__restrict__ word_off,
                                                    uint32_t n_ref, uint64_t *bits, dsb_ref_coverage *cov)
 {
 	const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
 	if (i >= n) return;
-	const uint32_t nh = dsb_hits_out(counters[1], cap_hout);
+	const uint32_t nh = dsb_hits_out(counters->hits, cap_hout);
 	const DsbReadOut r = rout[i];
 	const uint32_t nrec = dsb_hits_cut(r.first, r.n, nh) ? 0u : r.n;
 	if (!nrec) return;
@@ -137,13 +137,13 @@ __global__ void __launch_bounds__(256) k_cover_or(uint64_t *__restrict__ dst, co
 // word after it (aligned_bases).  The lanes stride over the windows s / W .. (e - 1) / W of a record: each adds the length of its
 // overlap, and the lane that holds window s / W adds the record's start.  Agent-scope no-return atomic adds throughout, for the reason
 // k_ref_cover gives: records of different workgroups share windows.
-__global__ void __launch_bounds__(256) k_ref_windows(const DsbReadOut *__restrict__ rout, const DsbHitOut *__restrict__ hout, const unsigned int *__restrict__ counters,
+__global__ void __launch_bounds__(256) k_ref_windows(const DsbReadOut *__restrict__ rout, const DsbHitOut *__restrict__ hout, const DsbCounters *__restrict__ counters,
                                                      uint32_t cap_hout, uint32_t n, const uint64_t *__restrict__ ref_len, const uint64_t *__restrict__ first,
                                                      uint32_t n_ref, uint32_t W, uint64_t *win)
 {
 	const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
 	if (i >= n) return;
-	const uint32_t nh = dsb_hits_out(counters[1], cap_hout);
+	const uint32_t nh = dsb_hits_out(counters->hits, cap_hout);
 	const DsbReadOut r = rout[i];
 	const uint32_t nrec = dsb_hits_cut(r.first, r.n, nh) ? 0u : r.n;
 	if (!nrec) return;
@@ -250,13 +250,13 @@ __device__ inline uint32_t wave_max_u32(uint32_t v) { for (int o = 32; o; o >>= 
 // (|C| + 1 rounds over the hits).  Lane j keeps element j for the first 64; a longer set is selected a second time as it is written.
 // The host reserved n records and cap_hout elements behind (base_s, base_e); thread 0 of the grid moves the counters past them.
 // hash_mask keeps the low DSB_EM_HASH_BITS of the hash (all 64 by default; a hash of 0 becomes 1 either way).
-__global__ void __launch_bounds__(256) k_em_collect(const DsbReadOut *__restrict__ rout, const DsbHitOut *__restrict__ hout, const unsigned int *__restrict__ counters,
+__global__ void __launch_bounds__(256) k_em_collect(const DsbReadOut *__restrict__ rout, const DsbHitOut *__restrict__ hout, const DsbCounters *__restrict__ counters,
                                                     uint32_t cap_hout, uint32_t n, uint32_t n_ref, uint32_t min_permille, DsbEmSet *__restrict__ sets,
                                                     uint32_t *__restrict__ elems, unsigned long long *em_cnt, uint64_t base_s, uint64_t base_e,
                                                     uint64_t cap_sets, uint64_t cap_elems, uint64_t hash_mask)
 {
 	const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-	const uint32_t nh = dsb_hits_out(counters[1], cap_hout);
+	const uint32_t nh = dsb_hits_out(counters->hits, cap_hout);
 	if (blockIdx.x == 0 && threadIdx.x == 0) { em_cnt[0] = base_s + n; em_cnt[1] = base_e + nh; }
 	if (i >= n) return;
 	const DsbReadOut r = rout[i];
@@ -490,14 +490,14 @@ __device__ inline uint32_t lca_join(uint32_t a, uint32_t da, uint32_t b, uint32_
 // rooted (depth table) is folded into the lane's LCA; n_pass is the sum of the rounds' ballots.  Then a 6-step xor butterfly with
 // lca_join as the operator -- it is associative, commutative and idempotent, so every lane ends with the LCA of all.  AMBIGUOUS: a
 // lane saw two taxids, or a ballot finds a lane whose first taxid is not the first lane's.  Lane 0 writes the record.
-__global__ void __launch_bounds__(256) k_read_lca(const DsbReadOut *__restrict__ rout, const DsbHitOut *__restrict__ hout, const unsigned int *__restrict__ counters,
+__global__ void __launch_bounds__(256) k_read_lca(const DsbReadOut *__restrict__ rout, const DsbHitOut *__restrict__ hout, const DsbCounters *__restrict__ counters,
                                                   uint32_t cap_hout, uint32_t n, const uint32_t *__restrict__ parent, const uint16_t *__restrict__ depth,
                                                   const uint32_t *__restrict__ ref_tid, uint32_t n_ref, uint32_t max_tid, uint32_t bound, uint32_t min_permille,
                                                   dsb_read_lca *__restrict__ out)
 {
 	const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
 	if (i >= n) return;
-	const uint32_t nh = dsb_hits_out(counters[1], cap_hout);
+	const uint32_t nh = dsb_hits_out(counters->hits, cap_hout);
 	const DsbReadOut r = rout[i];
 	const uint32_t nrec = dsb_hits_cut(r.first, r.n, nh) ? 0u : r.n;
 	const DsbHitOut *h = hout + r.first;
@@ -1229,7 +1229,7 @@ extern "C" int dsb_ctx_lca_counts(dsb_ctx *c, dsb_taxon_count *out, size_t cap, 
 }
 
 // ---- the seam with the classify driver (dsb_gpu.hip) ----
-// the hit buffer's arguments of k_read_taxon, k_ref_cover and k_em_collect
+// the hit buffer's arguments of the per-read kernels: k_read_taxon, k_ref_cover, k_ref_windows, k_em_collect and k_read_lca
 #define DSB_BATCH_HITS(b) (b).rout, (b).hout, (b).counters, (uint32_t)(b).cap_hout
 
 int reductions_run(dsb_ctx *c, const DsbBatchView &b)
