@@ -475,6 +475,21 @@ DV uint64_t lv_word_q(uint64_t body, int32_t len, uint32_t before)     // before
 #define DSB_SPHASH 1024u
 struct SpSet { uint64_t *tab; int l, m; uint32_t gen; };      // gen: taken from and given back to the LCtx by the walk that owns the set
 DV void sp_set_reset(SpSet &s) { s.l = 0; s.gen++; }
+// The 20-bit generation must not wrap while entries of the wrapped-over generations are in a table: an entry written 2^20 bumps ago would count as current, and
+// a generation field of 0 over slots never written makes every slot look taken by row 0 (the probe loop above would not end).  A launch zeroes the sets and starts at 0;
+// a wavefront then takes read after read, so nothing bounds the bumps of a launch.  sp_gen_guard() is called in front of every read's anchor stage (classify_read,
+// fast_classify_lane, k_anchor): from DSB_SPGEN_RESET on it zeroes the sets and starts over at 0, so the wrap needs 2^19 bumps inside one read.
+#define DSB_SPGEN_RESET (1u << 19)
+DV void sp_gen_guard(WCtxL &w)
+{
+	if (w.sp_gen < DSB_SPGEN_RESET) return;
+	wave_sync();
+	for (uint32_t i = (uint32_t)DSB_LANE; i < (uint32_t)DSB_WAVE * DSB_SPHASH; i += DSB_WAVE) w.lane_spset[i] = 0;
+	for (uint32_t i = (uint32_t)DSB_LANE; i < DSB_SPHASH; i += DSB_WAVE) w.spset[i] = 0;
+	wave_sync();
+	w.sp_gen = 0;
+	wave_sync();
+}
 DV int sp_set_insert(uint64_t node, SpSet &s)
 {
 	if (s.l == s.m) sp_set_reset(s);
@@ -3502,6 +3517,7 @@ DN void detect_primary(WCtxL &w, uint32_t read_len)
 DN void fast_classify_lane(WCtxL &w, bool valid, uint8_t *bin, uint32_t read_len, DsbSeed *seeds, const DsbSeedInfo *info, uint32_t *n_anc_out, uint32_t *ovf_out)
 {
 	DsbXP x = w.x; const int lane = DSB_LANE;
+	sp_gen_guard(w);
 	LCtx l = lctx_main(w);
 	l.k.uni = 0;
 	l.anc = w.lane_anc + (size_t)lane * DSB_LANE_ANC_CAP; l.n_anc = 0; l.anc_cap = DSB_LANE_ANC_CAP;
@@ -3541,6 +3557,7 @@ DN uint32_t classify_read(WCtxL &w, const uint64_t *bitsF, const uint64_t *bitsR
 	if (have_anchors) w.lsteps = anc_lsteps;
 	uint32_t fast = 1;
 	if (read_len < 40) return fast;
+	sp_gen_guard(w);
 	SDirL *sd = w.sd;
 	uint32_t n = read_len - w.x->ek_len + 1;
 	w.stage = 1; MARK(w, 1); if (w.dbg) w.tlast = DSB_CLOCK();

@@ -638,6 +638,7 @@ __global__ void __launch_bounds__(64, DSB_ANCHOR_WPE) k_anchor(DsbDevIndex x, co
 		if (d.len >= 40) {
 			const uint32_t cnt0 = lane < 4 ? lds_cnt[lane] : 0u;
 			w.bin = bin + d.bin_off + DSB_QPAD_L; w.L = d.len; w.status = 0; w.n_anc = 0; w.steps = 0; w.lsteps = 0;
+			dsb_g64::sp_gen_guard(w);
 			const DsbSeedInfo si = sinfo[r];
 			dsb_g64::SDirL *sd = w.sd;
 			DsbSeed *sv = seed_blob + d.seed_off;

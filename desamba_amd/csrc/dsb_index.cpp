@@ -14,6 +14,8 @@
 struct dsb_index { DsbHostIndex h; };
 
 const DsbHostIndex *dsb_index_host(const dsb_index *idx) { return &idx->h; }
+// (tests only: the same view by a name a test can look up in the library, for tests/stage/dsb_stage.hip's upload of what the island walks read)
+extern "C" const void *dsb_index_host_view(const dsb_index *idx) { return &idx->h; }
 
 static FILE *open_ext(const char *dir, const char *ext)
 {

@@ -43,7 +43,7 @@ typedef struct { uint32_t t_pos, q_pos, len, score; } sms_t;
 typedef struct { uint32_t kmer, next, pos; } sah_t;                 /* sparse_align_HASH */
 typedef struct { uint16_t next; uint16_t seed_ID:15, s_or_e:1; } sch_t; /* seed_con_hash */
 typedef struct { int match_len; uint64_t sp, sa_sp; int sa_sp_l; int kmer_index; int read_offset; } mem_t;
-typedef struct { uint64_t *set; int l, m; } spset_t;
+typedef struct { uint64_t *set; int l, m; int hits, restarts; } spset_t;   /* hits: inserts that found the row; restarts: the set started over at m */
 typedef struct { ora_seed_t *seed_v; uint32_t l_seed_v; uint8_t *bin_read; uint64_t *kmer; uint32_t direction, total_score; } sdir_t;
 
 /* what ora_ext_stage records of one sdp_right_M2 / sdp_left_M2: why the loop ended (1 reference end, 2 last_search, 3 empty window, 4 the
@@ -66,6 +66,7 @@ struct ora_ctx {
 	uint64_t cnt[8];      /* P0,P1,OCC,SA,RW,MEMS */
 	uint64_t ref_bases;   /* bases of the 2-bit reference text (U6) */
 	struct ext_trace *xt;  /* ora_ext_stage: how an extension ran (null: not recorded) */
+	ora_anchor_trace_t *at; int64_t at_isl;   /* ora_anchor_stage: how the anchor stage ran (null: not recorded); the island being walked */
 	uint32_t *gap_nodes; uint32_t n_gap_nodes;   /* ora_gap_stage: match nodes sdp_match produced per gap of sdp_middle_M2 (null: not recorded) */
 	void *sort_tmp; size_t m_sort_tmp;
 };
@@ -344,9 +345,9 @@ int32_t ora_lv_extd(const uint8_t *ref_padded, int32_t ref_length, const uint8_t
 /* ---- FM index search, src/cly.c:1286-1447 --------------------------------------------- */
 static inline int sp_set_insert(uint64_t node, spset_t *s)
 {
-	if (s->l == s->m) s->l = 0;
+	if (s->l == s->m) { s->l = 0; s->restarts++; }
 	int i = 0;
-	for (; i < s->l; i++) if (s->set[i] == node) return 0;
+	for (; i < s->l; i++) if (s->set[i] == node) { s->hits++; return 0; }
 	s->set[i] = node; s->l++;
 	return 1;
 }
@@ -369,7 +370,7 @@ static void bwt_single_search(ora_ctx_t *c, const ora_idx_t *x, uint64_t sp, con
 	m->sp = sp; m->match_len = match_len; m->sa_sp = sa_sp; m->sa_sp_l = sa_sp_l;
 }
 
-static int bwt_MEM_search(ora_ctx_t *c, const ora_idx_t *x, const uint8_t *string, uint64_t pre_v, int max_rst, int l_min_mth, int l_max_mth, spset_t *sp_set, mem_t *mem)
+static int bwt_MEM_search_core(ora_ctx_t *c, const ora_idx_t *x, const uint8_t *string, uint64_t pre_v, int max_rst, int l_min_mth, int l_max_mth, spset_t *sp_set, mem_t *mem)
 {
 	int n_rst = 0; const uint64_t *rank = x->rank;
 	uint64_t sp = x->hash_index[pre_v], ep = x->hash_index[pre_v + 1], new_sp, new_ep;
@@ -401,6 +402,25 @@ static int bwt_MEM_search(ora_ctx_t *c, const ora_idx_t *x, const uint8_t *strin
 		}
 	}
 	return n_rst;
+}
+
+/* what fast_classify and slow_classify call: the search above, and one record of it for ora_anchor_stage (rows of ORA_AT_MEM) */
+static int bwt_MEM_search(ora_ctx_t *c, const ora_idx_t *x, const uint8_t *string, uint64_t pre_v, int max_rst, int l_min_mth, int l_max_mth, spset_t *sp_set, mem_t *mem)
+{
+	const int h0 = sp_set->hits, r0 = sp_set->restarts;
+	const int n = bwt_MEM_search_core(c, x, string, pre_v, max_rst, l_min_mth, l_max_mth, sp_set, mem);
+	ora_anchor_trace_t *t = c->at;
+	if (t) {
+		if (t->n_mem < t->max_mem) {
+			int64_t *r = t->mem + (size_t)ORA_AT_MEM * t->n_mem;
+			memset(r, 0, sizeof(int64_t) * ORA_AT_MEM);
+			r[0] = c->at_isl; r[1] = l_max_mth; r[2] = (int64_t)pre_v; r[3] = max_rst; r[4] = l_min_mth; r[5] = n;
+			r[6] = sp_set->hits - h0; r[7] = sp_set->restarts - r0;
+			for (int i = 0; i < n && i < 8; i++) { r[8 + 4 * i] = (int64_t)mem[i].sp; r[9 + 4 * i] = mem[i].match_len; r[10 + 4 * i] = (int64_t)mem[i].sa_sp; r[11 + 4 * i] = mem[i].sa_sp_l; }
+		}
+		t->n_mem++;
+	}
+	return n;
 }
 
 static anchor_t *push_anchor(ora_ctx_t *c)
@@ -459,6 +479,19 @@ static void get_new_ed(ora_ctx_t *c, const ora_idx_t *x, uint32_t *e_d, uint32_t
 
 typedef struct { uint8_t *bin_read; uint32_t read_L; uint16_t seed_ID; bool direction; } seedinfo_t;
 
+/* one record per map_seed call for ora_anchor_stage (rows of ORA_AT_MAP; the codes and flags: oracle.h) */
+static void map_seed_record(ora_ctx_t *c, const mem_t *m_r, int why, int ret, int64_t n_pos, uint32_t pushed, int fl)
+{
+	ora_anchor_trace_t *t = c->at;
+	if (!t) return;
+	if (m_r->read_offset == -1) fl |= ORA_MS_Q_MINUS1;
+	if (t->n_map < t->max_map) {
+		int64_t *r = t->map + (size_t)ORA_AT_MAP * t->n_map;
+		r[0] = c->at_isl; r[1] = why; r[2] = ret; r[3] = n_pos; r[4] = pushed; r[5] = fl; r[6] = m_r->read_offset; r[7] = m_r->match_len;
+	}
+	t->n_map++;
+}
+
 /* a-8 map_seed, src/cly.c:706-939 */
 static int32_t map_seed(ora_ctx_t *c, const ora_idx_t *x, mem_t *m_r, seedinfo_t *s_i)
 {
@@ -467,6 +500,7 @@ static int32_t map_seed(ora_ctx_t *c, const ora_idx_t *x, mem_t *m_r, seedinfo_t
 	int64_t uni = -1; uint32_t u_off = 0; uint64_t t_off = 0;
 	uint32_t l_pre, l_suf = 0, d_pre, d_suf = 0; int32_t s = 0, max_s = 0;
 	const int *Q_MEM = x->Q_MEM;
+	int why = 0, fl = (m_r->sa_sp != U64MAX ? ORA_MS_SA_SP : 0) | (q_off + 1 < 12 ? ORA_MS_SHORT_PRE : 0); const uint32_t anc0 = c->n_anc;   /* (the record of ora_anchor_stage) */
 	do {
 		uint8_t q_pre_[LVPAD + 16], *q_pre = q_pre_ + LVPAD, t_pre_[LVPAD + 16], *t_pre = t_pre_ + LVPAD, *q_suf, t_suf_[LVPAD + 16], *t_suf = t_suf_ + LVPAD;
 		memset(q_pre_, LVPAD_Q, LVPAD); memset(t_pre_, LVPAD_T, LVPAD); memset(t_suf_, LVPAD_T, LVPAD);
@@ -488,17 +522,17 @@ static int32_t map_seed(ora_ctx_t *c, const ora_idx_t *x, mem_t *m_r, seedinfo_t
 			else l_pre = s_l;
 		}
 		if (uni >= 0) {
-			if (x->uni[uni].length < 35) break;
+			if (x->uni[uni].length < 35) { why = ORA_MS_UNI_EARLY; break; }
 			l_pre = MINV(l_pre, u_off);
 			get_ref(c, t_b, t_pre, t_off - 1, l_pre, false);
 		}
 		d_pre = lv_extd(t_pre, l_pre, q_pre, l_pre);
 		s = Q_MEM[l_m] + x->Q_LV[d_pre][l_pre];
-		if (s < 12 && l_pre == 12 && uni < 0) { s = 0; break; }
+		if (s < 12 && l_pre == 12 && uni < 0) { s = 0; why = ORA_MS_PRE12; break; }
 		if (uni < 0) {
 			while (b_p & 7) { uint8_t ch = 0xff; b_p = occ_c(c, x, b_p, &ch) + x->rank[ch]; s_l++; }
 			uni = get_uni(c, x, b_p, s_l, &t_off, &u_off);
-			if (x->uni[uni].length < 35) { s = 0; break; }
+			if (x->uni[uni].length < 35) { s = 0; why = ORA_MS_UNI_LATE; break; }
 		}
 		int32_t q_off_r = q_off + l_m + 1;
 		uint32_t l_max_suf = MINV(x->uni[uni].length - u_off - l_m, s_i->read_L - q_off_r);
@@ -520,15 +554,18 @@ static int32_t map_seed(ora_ctx_t *c, const ora_idx_t *x, mem_t *m_r, seedinfo_t
 			}
 			d_suf = lv_extd(t_suf, l_suf, q_suf, l_suf);
 			s += x->Q_LV[d_suf][l_suf];
-		} else l_suf = d_suf = 0;
-		if (s <= 20 && l_suf == 12) { s = 0; break; }
+		} else { l_suf = d_suf = 0; fl |= ORA_MS_NO_SUF; }
+		if (s <= 20 && l_suf == 12) { s = 0; why = ORA_MS_SUF12; break; }
 	} while (0);
 
+	int64_t n_pos = 0;
 	if (s > 0) {
 		amap_t a_m = {l_m, s, l_pre, d_pre, l_suf, d_suf};
 		uint32_t rp_s = x->uni[uni].ref_list, rp_e = x->uni[uni + 1].ref_list;
 		bool ref_search_l = (l_pre < 12 || d_pre == 0), ref_search_r = (l_suf < 12 || d_suf == 0);
-		if ((int64_t)rp_e - (int64_t)rp_s > 50) { if (!((int64_t)rp_e - (int64_t)rp_s < 1000)) return 50; }
+		n_pos = (int64_t)rp_e - (int64_t)rp_s;
+		fl |= (ref_search_l ? ORA_MS_SEARCH_L : 0) | (ref_search_r ? ORA_MS_SEARCH_R : 0);
+		if ((int64_t)rp_e - (int64_t)rp_s > 50) { if (!((int64_t)rp_e - (int64_t)rp_s < 1000)) { map_seed_record(c, m_r, ORA_MS_LIST_1000, 50, n_pos, 0, fl); return 50; } }
 		for (uint32_t r = rp_s; r < rp_e; r++) {
 			uint64_t rp = x->refpos[r];
 			uint64_t rp_go = rp & 0xFFFFFFFFFFULL; uint32_t rp_ref = (rp >> 40) & 0x7FFFFF;
@@ -550,6 +587,7 @@ static int32_t map_seed(ora_ctx_t *c, const ora_idx_t *x, mem_t *m_r, seedinfo_t
 			max_s = MAXV(max_s, a_m.score);
 			anchor_t *a = push_anchor(c);
 			a->direction = s_i->direction;
+			if (l_m_ext_l > 0) fl |= ORA_MS_EXT_L;
 			a->index_in_read = q_off + 1 - l_m_ext_l;
 			a->global_offset = rp_go + u_off - l_m_ext_l;
 			a->ref_ID = rp_ref;
@@ -557,7 +595,21 @@ static int32_t map_seed(ora_ctx_t *c, const ora_idx_t *x, mem_t *m_r, seedinfo_t
 			a->a_m = a_m; a->seed_ID = s_i->seed_ID; a->duplicate = 0; a->pre = -1;
 		}
 	}
+	if (!why) why = s <= 0 ? ORA_MS_NO_SCORE : n_pos > 50 ? ORA_MS_LIST_51 : c->n_anc > anc0 ? ORA_MS_PUSHED : ORA_MS_ALL_DROPPED;
+	map_seed_record(c, m_r, why, max_s, n_pos, c->n_anc - anc0, fl);
 	return max_s;
+}
+
+/* one record per walked island (fast) or per seed that was searched (slow) for ora_anchor_stage: rows of ORA_AT_ISL */
+static void island_record(ora_ctx_t *c, int64_t seed, int n_search, int skip, uint32_t first, int max_score, uint32_t direction, int n_mems, int tie)
+{
+	ora_anchor_trace_t *t = c->at;
+	if (!t) return;
+	if (t->n_isl < t->max_isl) {
+		int64_t *r = t->isl + (size_t)ORA_AT_ISL * t->n_isl;
+		r[0] = seed; r[1] = n_search; r[2] = skip; r[3] = first; r[4] = c->n_anc; r[5] = max_score; r[6] = direction; r[7] = n_mems; r[8] = tie; r[9] = 0;
+	}
+	t->n_isl++;
 }
 
 /* a-4 fast_classify, src/cly.c:1478-1546 */
@@ -574,11 +626,14 @@ static void fast_classify(ora_ctx_t *c, const ora_idx_t *x, sdir_t *s_d, uint32_
 		sp_set.l = 0;
 		s_i.seed_ID = c_sv - sv_b;
 		uint32_t a_b_idx = c->n_anc;
+		int n_search = 0, isl_max = 0, isl_skip = 0; const int64_t isl_seed = c_sv - sv_b;
+		if (c->at) c->at_isl = c->at->n_isl;
 		for (int j = c_sv->len - 1; j >= min_index;) {
 			int kmer_index = c_sv->offset + j;
 			uint64_t prefixValue = kmer[kmer_index] & 0x3FFFFFF;
 			int string_index = kmer_index + l_ek - 1;
 			int n = bwt_MEM_search(c, x, bin_read + string_index, prefixValue, 2, 21 - 1, string_index, &sp_set, m_r);
+			n_search++;
 			if (n == 0) { j -= 2; continue; }
 			j -= 3;
 			int max_score = 0;
@@ -587,12 +642,14 @@ static void fast_classify(ora_ctx_t *c, const ora_idx_t *x, sdir_t *s_d, uint32_
 				int sc = map_seed(c, x, c_mr, &s_i);
 				max_score = MAXV(sc, max_score);
 			}
+			isl_max = MAXV(isl_max, max_score);
 			if (max_score > 35) j -= 7;
-			if (max_score > 256) { if (max_score > 512) c_sv++; break; }
+			if (max_score > 256) { if (max_score > 512) { c_sv++; isl_skip = 1; } break; }
 		}
 		int top_score = 35;
 		for (uint32_t i = a_b_idx; i < c->n_anc; i++) top_score = MAXV(top_score, c->anc[i].a_m.score);
 		for (uint32_t i = a_b_idx; i < c->n_anc; i++) c->anc[i].anchor_useless = (c->anc[i].a_m.score < top_score) ? 1 : 0;
+		island_record(c, isl_seed, n_search, isl_skip, a_b_idx, isl_max, s_d->direction, 0, 0);
 	}
 }
 
@@ -609,15 +666,18 @@ static void slow_classify(ora_ctx_t *c, const ora_idx_t *x, sdir_t *sd, uint32_t
 		if ((int)(sv_f[i].len) < 3 && sv_f->top == 0) continue;
 		int min_match_len = MINV(20 - 1, l_ek + 1);
 		sp_set.l = 0; mem_rst_num = 0;
+		int n_search = 0;
+		if (c->at) c->at_isl = c->at->n_isl;
 		for (int j = sv_f[i].len - 1; j >= 1; j -= 2) {
 			int k_idx = sv_f[i].offset + j;
 			uint64_t pre_v = kmer[k_idx] & 0x3FFFFFF;
 			int s_idx = k_idx + l_ek - 1;
 			int n = bwt_MEM_search(c, x, bin_read + s_idx, pre_v, 8, min_match_len, s_idx, &sp_set, mem_rst + mem_rst_num);
+			n_search++;
 			for (int q = mem_rst_num; q < mem_rst_num + n; q++) mem_rst[q].read_offset = k_idx + l_ek - 1 - mem_rst[q].match_len;
 			mem_rst_num += n;
 		}
-		if (mem_rst_num == 0) continue;
+		if (mem_rst_num == 0) { island_record(c, i, n_search, 0, c->n_anc, 0, sd->direction, 0, 0); continue; }
 		if (mem_rst_num > 1) glibc_qsort(c, mem_rst, mem_rst_num, sizeof(mem_t), mem_cmp_len);
 		s_i.seed_ID = i;
 		uint32_t a_b_idx = c->n_anc;
@@ -626,6 +686,7 @@ static void slow_classify(ora_ctx_t *c, const ora_idx_t *x, sdir_t *sd, uint32_t
 		int top_score = 35;
 		for (uint32_t q = a_b_idx; q < c->n_anc; q++) top_score = MAXV(top_score, c->anc[q].a_m.score);
 		for (uint32_t q = a_b_idx; q < c->n_anc; q++) c->anc[q].anchor_useless = (c->anc[q].a_m.score < top_score) ? 1 : 0;
+		island_record(c, i, n_search, 0, a_b_idx, 0, sd->direction, mem_rst_num, mem_rst_num > 8 && mem_rst[7].match_len == mem_rst[8].match_len);
 	}
 }
 
@@ -1517,6 +1578,46 @@ int ora_last_anchors(const ora_ctx_t *c, ora_anchor_t *out, int max)
 		out[i].score = a->a_m.score; out[i].mtch_len = a->a_m.mtch_len; out[i].direction = a->direction;
 		out[i].useless = a->anchor_useless; out[i].seed_ID = a->seed_ID;
 		out[i].left_len = a->a_m.left_len; out[i].left_ED = a->a_m.left_ED; out[i].rigt_len = a->a_m.rigt_len; out[i].rigt_ED = a->a_m.rigt_ED;
+	}
+	return (int)c->n_anc;
+}
+
+/* The anchor stage on its own (tests/test_stage_anchor.py): the seed lists of both strands as get_island makes them, then fast_classify
+ * (what 0) or slow_classify (what 1) on the strand asked for, or (what 2) fast_classify as ora_classify calls it: on the strand with the
+ * larger total first (the swap of get_island) and on the other one too when the both-direction rule says so.  Every anchor in order with
+ * its global_offset, and through t how the stage ran (oracle.h).  Returns the number of anchors. */
+int ora_anchor_stage(ora_ctx_t *c, const ora_idx_t *x, const char *seq, uint32_t read_len, int what, int strand, ora_anchor_trace_t *t)
+{
+	c->n_anc = 0; c->n_hit = 0; c->read_len = read_len;
+	c->ref_bases = x->n_refbin * 4;
+	memset(c->cnt, 0, sizeof c->cnt);
+	c->sd[0].l_seed_v = c->sd[1].l_seed_v = 0;
+	t->n_isl = t->n_mem = t->n_map = t->n_anc = 0; t->n_seed[0] = t->n_seed[1] = t->total[0] = t->total[1] = 0; t->both = 0; t->first = FORWARD;
+	if (read_len < 40) return 0;
+	sdir_t *sd = c->sd;
+	get_island(c, x, seq, read_len, sd);
+	for (int k = 0; k < 2; k++) {                      /* [0]: the forward strand's list, [1]: the reverse strand's */
+		const sdir_t *d = sd[0].direction == (uint32_t)(k == 0 ? FORWARD : REVERSE) ? sd : sd + 1;
+		t->n_seed[k] = d->l_seed_v; t->total[k] = d->total_score;
+		for (uint32_t i = 0; i < d->l_seed_v && i < t->max_seed; i++) t->seeds[k][i] = d->seed_v[i];
+	}
+	t->both = ((sd[0].total_score - sd[1].total_score) <= (sd[0].total_score >> 3)); t->first = sd[0].direction;
+	c->at = t; c->at_isl = -1;
+	if (what == 2) {
+		fast_classify(c, x, sd, read_len);
+		if (t->both) fast_classify(c, x, sd + 1, read_len);
+	} else {
+		sdir_t *d = sd[0].direction == (uint32_t)strand ? sd : sd + 1;
+		if (what == 0) fast_classify(c, x, d, read_len); else slow_classify(c, x, d, read_len);
+	}
+	c->at = NULL;
+	t->n_anc = c->n_anc;
+	for (uint32_t i = 0; i < c->n_anc && i < t->max_anc; i++) {
+		const anchor_t *a = c->anc + i; ora_anchor_t *o = &t->anc[i].a;
+		o->index_in_read = a->index_in_read; o->ref_ID = a->ref_ID; o->ref_offset = a->ref_offset;
+		o->score = a->a_m.score; o->mtch_len = a->a_m.mtch_len; o->direction = a->direction; o->useless = a->anchor_useless; o->seed_ID = a->seed_ID;
+		o->left_len = a->a_m.left_len; o->left_ED = a->a_m.left_ED; o->rigt_len = a->a_m.rigt_len; o->rigt_ED = a->a_m.rigt_ED;
+		t->anc[i].global_offset = a->global_offset;
 	}
 	return (int)c->n_anc;
 }

@@ -125,6 +125,34 @@ int ora_resolve_stage(ora_ctx_t *c, const uint32_t *anchors, uint32_t n, int m3,
 int ora_finish_stage(ora_ctx_t *c, ora_chain_t *chains, uint32_t n, uint32_t read_len, int *max_read_l, int min_length, int min_score,
                      int min_score_LV3, ora_chain_t *tail, uint32_t *n_cut);
 void ora_sort_stage(ora_ctx_t *c, ora_chain_t *chains, uint32_t n, int which);
+/* a-4 .. a-8 on their own (tests/test_stage_anchor.py): fast_classify (what 0) or slow_classify (what 1) on one strand (1 = F, 0 = R), or
+ * (what 2) fast_classify on the read as ora_classify calls it, with the strand swap and the both-direction rule.  The caller owns the
+ * arrays of the trace and states their sizes (max_*); a count (n_*) beyond its size says that the array was too small.
+ *   isl  one row per walked island (fast) or searched seed (slow): seed index, searches, skip flag (the next seed is jumped over), first
+ *        anchor, last anchor + 1, largest map_seed score of a search, strand, MEMs collected (slow), 8th and 9th MEM of equal length (slow), 0
+ *   mem  one row per bwt_MEM_search: row of isl, string index (= l_max), 13-mer prefix, max_rst, l_min, number of MEMs, set hits (a row
+ *        seen before ended a walk), set restarts (the 500-entry set started over), then per MEM (at most 8) sp, match_len, sa_sp, sa_sp_l
+ *   map  one row per map_seed: row of isl, reason (ORA_MS_*), return value, length of the reference-position list (0: not reached),
+ *        anchors pushed, flags (ORA_MS_* bits), read_offset, match_len of the MEM */
+#define ORA_AT_ISL 10
+#define ORA_AT_MEM 40
+#define ORA_AT_MAP 8
+enum { ORA_MS_UNI_EARLY = 1, ORA_MS_UNI_LATE = 2, ORA_MS_PRE12 = 3, ORA_MS_SUF12 = 4, ORA_MS_LIST_1000 = 5, ORA_MS_LIST_51 = 6, ORA_MS_PUSHED = 7,
+       ORA_MS_ALL_DROPPED = 8, ORA_MS_NO_SCORE = 9 };   /* unitig < 35 met early / late; s < 12 && l_pre == 12 without a unitig; s <= 20 && l_suf == 12; a list
+       of >= 1000 positions (returns 50); a list of 51 .. 999 (anchors pushed or not: see the count); anchors pushed from a list of <= 50; every position of
+       such a list dropped by score < 20; the score before the list was not positive */
+enum { ORA_MS_SA_SP = 1, ORA_MS_SEARCH_L = 2, ORA_MS_SEARCH_R = 4, ORA_MS_EXT_L = 8, ORA_MS_Q_MINUS1 = 16, ORA_MS_NO_SUF = 32, ORA_MS_SHORT_PRE = 64 };
+       /* sa_sp set; ref_search_l; ref_search_r; l_m_ext_l > 0 at a pushed anchor; the MEM reaches base 0 (q_off = -1); l_max_suf == 0; l_pre < 12 from the read */
+typedef struct { ora_anchor_t a; uint64_t global_offset; } ora_anchor_full_t;
+typedef struct {
+	ora_seed_t *seeds[2]; uint32_t n_seed[2], total[2], max_seed;     /* [0] forward strand, [1] reverse strand */
+	uint32_t both, first;                                             /* the both-direction rule; the strand with the larger total (walked first) */
+	ora_anchor_full_t *anc; uint32_t n_anc, max_anc;
+	int64_t *isl; uint32_t n_isl, max_isl;
+	int64_t *mem; uint32_t n_mem, max_mem;
+	int64_t *map; uint32_t n_map, max_map;
+} ora_anchor_trace_t;
+int ora_anchor_stage(ora_ctx_t *c, const ora_idx_t *idx, const char *seq, uint32_t len, int what, int strand, ora_anchor_trace_t *t);
 #ifdef __cplusplus
 }
 #endif

@@ -501,3 +501,79 @@ extern "C" int emu_stage_finish(StageFin *cases, uint32_t n, DsbChain *chains, D
 	for (uint32_t k = 0; k < n; k++) { j.fc = cases + k; stage2_run(j); }
 	return 0;
 }
+
+// ---- the anchor stage form by form (tests/stage/dsb_stage_forms.h, tests/test_stage_anchor.py): the FM search, fast_island, fast_classify, fast_classify_lane and
+// slow_classify on a loaded index; the descriptor is the one emu_new builds, on the host view of the index
+struct Stage3Index { dsb_index *idx; DsbDevIndex dx; };
+extern "C" void *emu_stage_anchor_index(dsb_index *idx)
+{
+	const DsbHostIndex *h = dsb_index_host(idx);
+	Stage3Index *s = new Stage3Index(); s->idx = idx;
+	DsbDevIndex &dx = s->dx; memset(&dx, 0, sizeof dx);
+	dx.ek0 = h->ek0; dx.ek1 = h->ek1; dx.ek_mask = h->ek_mask; dx.ek_len = h->ek_len; dx.single_base_max = h->single_base_max;
+	dx.fm = h->fm; dx.fm_sb = h->fm_sb; dx.bwt_len = h->bwt_len; memcpy(dx.rank, h->rank, sizeof dx.rank); dx.dollar_pos = h->dollar_pos; dx.dollar_row = h->dollar_row;
+	dx.hash_index = h->hash_c ? nullptr : h->hash_index; dx.hash_c = h->hash_c; dx.sa = (const uint2 *)h->sa; dx.uni = (const uint2 *)h->uni; dx.refpos = h->refpos; dx.refbin = h->refbin; dx.ref_bases = h->n_refbin * 4;
+	dx.refinfo = h->refinfo; dx.qmem = h->Q_MEM; dx.qlv = &h->Q_LV[0][0];
+	return s;
+}
+extern "C" void emu_stage_anchor_index_free(void *p) { delete (Stage3Index *)p; }
+// what the index was opened as: [0] the 13-mer table is the compressed one, [1] the rank lines have superblocks, [2] the filter's k-mer length
+extern "C" void emu_stage_anchor_index_info(void *p, uint32_t *out) { const DsbDevIndex &dx = ((Stage3Index *)p)->dx; out[0] = dx.hash_c != nullptr; out[1] = dx.fm_sb != nullptr; out[2] = (uint32_t)dx.ek_len; }
+struct Stage3Job { StageHost *h; uint8_t *slice; const DsbDevIndex *dx; StageAnc *c, *cases; uint32_t k0, n; const uint8_t *bin; DsbSeed *seeds; DsbAnchor *anchors; const int32_t *calls; int64_t *mems; };
+static void stage3_lane(void *p)
+{
+	Stage3Job *j = (Stage3Job *)p; StageHost *h = j->h;
+	stage_ctx(h->w, &h->sx, j->slice, h->wtab, h->ring, h->red, h->cnt, &h->ri);
+	if (j->c) stage_anchor(h->w, &h->sx, j->dx, j->c, j->bin, j->seeds, j->anchors, j->calls, j->mems, j->slice);
+	else stage_anchor_lane(h->w, &h->sx, j->dx, j->cases, j->k0, j->n, j->bin, j->seeds, j->anchors, j->slice);
+}
+static std::vector<uint8_t> g_stage3_slice;
+extern "C" uint32_t emu_stage_sizes3(uint32_t *out)
+{
+	out[0] = sizeof(StageAnc); out[1] = sizeof(DsbAnchor); out[2] = sizeof(DsbSeed); out[3] = DSB_LANE_ANC_CAP; out[4] = DSB_LANE_STEPS; out[5] = STAGE3_GUARD; out[6] = STAGE3_MEM; out[7] = DSB_EMU_LANES;
+	out[8] = DSB_SPSET_CAP; out[9] = STAGE3_MAX_SEEDS;
+	return 10;
+}
+extern "C" int emu_stage_anchor(void *index, StageAnc *cases, uint32_t n, const uint8_t *bin, size_t bin_bytes, DsbSeed *seeds, size_t n_seeds, DsbAnchor *anchors, size_t n_anchors,
+                                const int32_t *calls, size_t n_calls, int64_t *mems, size_t n_mems)
+{
+	Stage3Index *si = (Stage3Index *)index;
+	if (stage_anchor_check(cases, n, bin_bytes, n_seeds, n_anchors, calls, n_calls, n_mems, seeds, si->dx.ek_len)) return __LINE__;
+	if (!n) return 0;
+	for (uint32_t k = 0; k < n; k++) if ((cases[k].form == ANC_LANE) != (cases[0].form == ANC_LANE)) return __LINE__;
+	if (g_stage3_slice.empty()) g_stage3_slice.assign(STAGE3_SLICE, 0);
+	Stage3Job j; memset(&j, 0, sizeof j); j.h = stage_host(); j.slice = g_stage3_slice.data(); j.dx = &si->dx; j.cases = cases; j.n = n; j.bin = bin; j.seeds = seeds; j.anchors = anchors; j.calls = calls; j.mems = mems;
+#if DSB_EMU_LANES == 64
+	{
+		StageHost *h = j.h; uint8_t *s = j.slice; const DsbHostIndex *x = dsb_index_host(si->idx);
+		dsb_emu_regions_clear();
+		// (the detector looks an address up in this list front to back: what the walks read most comes first)
+		dsb_emu_region(x->fm, x->n_fm * sizeof(DsbFmBlock), "rank lines");
+		if (x->fm_sb) dsb_emu_region(x->fm_sb, x->n_fm_sb * 40, "rank superblocks");
+		if (x->hash_c) dsb_emu_region(x->hash_c, (size_t)x->n_hash_c * sizeof(DsbHiLine), "13-mer table (compressed)"); else dsb_emu_region(x->hash_index, (((size_t)1 << 26) + 1) * 8, "13-mer table");
+		dsb_emu_region(x->sa, x->sa_size * 8, "SA samples"); dsb_emu_region(x->uni, (x->n_uni + 1) * 8, "unitigs"); dsb_emu_region(x->refpos, (x->n_refpos + 1) * 8, "reference positions");
+		dsb_emu_region(x->refbin, x->n_refbin + 4096, "reference text"); dsb_emu_region(x->refinfo, x->n_ref * sizeof(DsbRefInfo), "reference info (index)");
+		dsb_emu_region(x->Q_MEM, 2000 * sizeof(int), "Q_MEM"); dsb_emu_region(&x->Q_LV[0][0], 400 * sizeof(int), "Q_LV");
+		dsb_emu_region(&j, sizeof j, "job"); dsb_emu_region(h->wtab, sizeof h->wtab, "LDS window table"); dsb_emu_region(h->ring, sizeof h->ring, "LDS ring");
+		dsb_emu_region(h->red, sizeof h->red, "LDS red"); dsb_emu_region(h->cnt, sizeof h->cnt, "LDS counters"); dsb_emu_region(&h->sx, sizeof h->sx, "index descriptor");
+		dsb_emu_region(&h->w, sizeof h->w, "context"); dsb_emu_region(&h->ri, sizeof h->ri, "reference info"); dsb_emu_region(&h->dpb, sizeof h->dpb, "LDS DP batch");
+		dsb_emu_region(&si->dx, sizeof si->dx, "index descriptor (source)");
+		dsb_emu_region(s + STAGE3_OFF_SPSET, DSB_SPHASH * 8u, "visited rows"); dsb_emu_region(s + STAGE3_OFF_LANE_SP, 64u * DSB_SPHASH * 8u, "lane visited rows");
+		dsb_emu_region(s + STAGE3_OFF_LANE_ANC, 64u * DSB_LANE_ANC_CAP * 40u, "lane anchors"); dsb_emu_region(s + STAGE3_OFF_TOP, STAGE3_MAX_SEEDS * 4u, "top islands");
+		dsb_emu_region(s + STAGE3_OFF_ROUND, STAGE3_MAX_SEEDS * 4u, "island records"); dsb_emu_region(s + STAGE3_OFF_ORD, STAGE3_MAX_SEEDS * 4u, "island order");
+		dsb_emu_region(s + STAGE3_OFF_MEM, DSB_MEMSLOW_CAP * 32u, "slow-path MEMs");
+		dsb_emu_region(cases, (size_t)n * sizeof(StageAnc), "cases"); dsb_emu_region(bin, bin_bytes, "byte strands"); dsb_emu_region(seeds, n_seeds * sizeof(DsbSeed), "seeds");
+		dsb_emu_region(anchors, n_anchors * sizeof(DsbAnchor), "anchors"); dsb_emu_region(calls, n_calls * 16, "search calls"); dsb_emu_region(mems, n_mems * STAGE3_MEM * 8, "search results");
+	}
+#endif
+	auto run = [&]() {
+#if DSB_EMU_LANES == 64
+		dsb_emu_run(stage3_lane, &j);
+#else
+		stage3_lane(&j);
+#endif
+	};
+	if (cases[0].form == ANC_LANE) for (uint32_t k = 0; k < n; k += DSB_WAVE) { j.c = nullptr; j.k0 = k; run(); }
+	else for (uint32_t k = 0; k < n; k++) { j.c = cases + k; run(); }
+	return 0;
+}

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
 #include "dsb_device.h"
 #define DSB_GROUP 64
 #define DSB_NS dsb_stage
@@ -329,5 +330,101 @@ extern "C" int stage_dev_finish(StageFin *cases, uint32_t n, DsbChain *chains, D
 	CK(hipGetLastError() != hipSuccess);
 	CK(hipDeviceSynchronize() != hipSuccess);
 	if (n && n_chains) { CK(dc.down(cases)); CK(dh.down(chains)); CK(dt.down(tail)); } else if (n) CK(dc.down(cases));
+	return 0;
+}
+
+// ---- the anchor stage (a-4 .. a-8): the FM search, fast_island, fast_classify, fast_classify_lane, slow_classify on a loaded index (tests/test_stage_anchor.py).
+// The index comes from the host view of an opened index (dsb_index_host: the test passes the pointer): what the walk reads of it is uploaded once.
+#include "dsb_host.h"
+#define STAGE3_GRID 256u     /* workgroups and scratch slices (1.4 MB each) per launch */
+#define STAGE3_KERNEL_CTX                                                                                          \
+	__shared__ DsbDevIndex sx;                                                                                     \
+	__shared__ uint4 lds_ring[DSB_RING];                                                                           \
+	__shared__ __attribute__((aligned(16))) uint32_t lds_wtab[DSB_WTAB_SLOTS];                                     \
+	__shared__ uint32_t lds_red[2];                                                                                \
+	__shared__ uint32_t lds_cnt[4];                                                                                \
+	__shared__ DpBatch lds_dpb;                                                                                    \
+	__shared__ WCtx s_w;                                                                                           \
+	WCtxL &w = *(WCtxL *)&s_w;                                                                                     \
+	if (threadIdx.x < 4) lds_cnt[threadIdx.x] = 0;                                                                 \
+	__syncthreads();                                                                                               \
+	w.dpb = (DpBatchL *)&lds_dpb;                                                                                  \
+	uint8_t *const slice = slices + (size_t)blockIdx.x * STAGE3_SLICE;                                             \
+	stage_ctx(w, (DSB_LDS_AS DsbDevIndex *)&sx, slice, lds_wtab, lds_ring, lds_red, lds_cnt, dx->refinfo);         \
+	__syncthreads();
+static_assert(STAGE3_SLICE >= STAGE_SLICE, "stage_ctx points the a-12 arrays into the slice before stage3_ctx lays it out anew");
+
+__global__ void __launch_bounds__(64) k_stage_anchor(const DsbDevIndex *dx, StageAnc *cases, uint32_t base, uint32_t n, const uint8_t *bin, DsbSeed *seeds, DsbAnchor *anchors, const int32_t *calls,
+                                                     int64_t *mems, uint8_t *slices)
+{
+	const uint32_t k = base + blockIdx.x;
+	if (k >= n) return;
+	STAGE3_KERNEL_CTX
+	stage_anchor(w, (DSB_LDS_AS DsbDevIndex *)&sx, dx, cases + k, bin, seeds, anchors, calls, mems, slice);
+}
+__global__ void __launch_bounds__(64) k_stage_anchor_lane(const DsbDevIndex *dx, StageAnc *cases, uint32_t base, uint32_t n, const uint8_t *bin, DsbSeed *seeds, DsbAnchor *anchors, uint8_t *slices)
+{
+	const uint32_t k0 = base + 64u * blockIdx.x;
+	if (k0 >= n) return;
+	STAGE3_KERNEL_CTX
+	stage_anchor_lane(w, (DSB_LDS_AS DsbDevIndex *)&sx, dx, cases, k0, n, bin, seeds, anchors, slice);
+}
+struct Stage3DevIndex { DevBuf fm, fm_sb, hash, sa, uni, refpos, refbin, refinfo, qmem, qlv, dx; int ek_len; uint32_t info[3]; };
+extern "C" void *stage_dev_anchor_index(const DsbHostIndex *h)
+{
+	Stage3DevIndex *s = new Stage3DevIndex();
+	DsbDevIndex dx; memset(&dx, 0, sizeof dx);
+	bool bad = false;
+	bad |= s->fm.up(h->fm, h->n_fm * sizeof(DsbFmBlock)) != 0;
+	if (h->fm_sb) bad |= s->fm_sb.up(h->fm_sb, h->n_fm_sb * 40) != 0;
+	if (h->hash_c) bad |= s->hash.up(h->hash_c, (size_t)h->n_hash_c * sizeof(DsbHiLine)) != 0; else bad |= s->hash.up(h->hash_index, (((size_t)1 << 26) + 1) * 8) != 0;
+	bad |= s->sa.up(h->sa, h->sa_size * 8) != 0; bad |= s->uni.up(h->uni, (h->n_uni + 1) * 8) != 0; bad |= s->refpos.up(h->refpos, (h->n_refpos + 1) * 8) != 0;
+	bad |= s->refbin.up(h->refbin, h->n_refbin + 4096) != 0; bad |= s->refinfo.up(h->refinfo, h->n_ref * sizeof(DsbRefInfo)) != 0;
+	bad |= s->qmem.up(h->Q_MEM, 2000 * sizeof(int)) != 0; bad |= s->qlv.up(&h->Q_LV[0][0], 400 * sizeof(int)) != 0;
+	dx.ek_mask = h->ek_mask; dx.ek_len = h->ek_len; dx.single_base_max = h->single_base_max;          // (the filter tables are not uploaded: the walk does not read them)
+	dx.fm = (const DsbFmBlock *)s->fm.p; dx.fm_sb = h->fm_sb ? (const uint64_t *)s->fm_sb.p : nullptr; dx.bwt_len = h->bwt_len; memcpy(dx.rank, h->rank, sizeof dx.rank);
+	dx.dollar_pos = h->dollar_pos; dx.dollar_row = h->dollar_row;
+	dx.hash_index = h->hash_c ? nullptr : (const uint64_t *)s->hash.p; dx.hash_c = h->hash_c ? (const DsbHiLine *)s->hash.p : nullptr;
+	dx.sa = (const uint2 *)s->sa.p; dx.uni = (const uint2 *)s->uni.p; dx.refpos = (const uint64_t *)s->refpos.p; dx.refbin = (const uint8_t *)s->refbin.p; dx.ref_bases = h->n_refbin * 4;
+	dx.refinfo = (const DsbRefInfo *)s->refinfo.p; dx.qmem = (const int *)s->qmem.p; dx.qlv = (const int *)s->qlv.p;
+	bad |= s->dx.up(&dx, sizeof dx) != 0;
+	s->ek_len = h->ek_len; s->info[0] = h->hash_c != nullptr; s->info[1] = h->fm_sb != nullptr; s->info[2] = (uint32_t)h->ek_len;
+	if (bad) { fprintf(stderr, "dsb_stage: uploading the index failed (%s)\n", hipGetErrorString(hipGetLastError())); delete s; return nullptr; }
+	return s;
+}
+extern "C" void stage_dev_anchor_index_free(void *p) { delete (Stage3DevIndex *)p; }
+extern "C" void stage_dev_anchor_index_info(void *p, uint32_t *out) { memcpy(out, ((Stage3DevIndex *)p)->info, 12); }
+extern "C" uint32_t stage_dev_sizes3(uint32_t *out)
+{
+	out[0] = sizeof(StageAnc); out[1] = sizeof(DsbAnchor); out[2] = sizeof(DsbSeed); out[3] = DSB_LANE_ANC_CAP; out[4] = DSB_LANE_STEPS; out[5] = STAGE3_GUARD; out[6] = STAGE3_MEM; out[7] = 64;
+	out[8] = DSB_SPSET_CAP; out[9] = STAGE3_MAX_SEEDS;
+	return 10;
+}
+// all cases of one call are ANC_LANE (64 reads per workgroup, one per lane) or none is
+extern "C" int stage_dev_anchor(void *index, StageAnc *cases, uint32_t n, const uint8_t *bin, size_t bin_bytes, DsbSeed *seeds, size_t n_seeds, DsbAnchor *anchors, size_t n_anchors,
+                                const int32_t *calls, size_t n_calls, int64_t *mems, size_t n_mems)
+{
+	Stage3DevIndex *si = (Stage3DevIndex *)index;
+	DevBuf dc, db, dsd, da, dq, dm, ds;
+	CK(!si);
+	CK(stage_anchor_check(cases, n, bin_bytes, n_seeds, n_anchors, calls, n_calls, n_mems, seeds, si->ek_len));
+	if (!n) return 0;
+	const bool lanes = cases[0].form == ANC_LANE;
+	for (uint32_t k = 0; k < n; k++) CK((cases[k].form == ANC_LANE) != lanes);
+	CK(hipMalloc(&ds.p, (size_t)STAGE3_GRID * STAGE3_SLICE) != hipSuccess);
+	ds.n = (size_t)STAGE3_GRID * STAGE3_SLICE;
+	CK(hipMemset(ds.p, 0, ds.n) != hipSuccess);
+	CK(dc.up(cases, (size_t)n * sizeof(StageAnc))); CK(db.up(bin, bin_bytes)); CK(dsd.up(seeds, n_seeds * sizeof(DsbSeed))); CK(da.up(anchors, n_anchors * sizeof(DsbAnchor)));
+	CK(dq.up(calls, n_calls * 16)); CK(dm.up(mems, n_mems * STAGE3_MEM * 8));
+	const uint32_t per = lanes ? 64u * STAGE3_GRID : STAGE3_GRID;
+	for (uint32_t base = 0; base < n; base += per) {
+		const uint32_t rest = n - base, grid = lanes ? ((rest < per ? rest : per) + 63u) / 64u : (rest < per ? rest : per);
+		if (lanes) hipLaunchKernelGGL(k_stage_anchor_lane, dim3(grid), dim3(64), 0, 0, (const DsbDevIndex *)si->dx.p, (StageAnc *)dc.p, base, n, (const uint8_t *)db.p, (DsbSeed *)dsd.p, (DsbAnchor *)da.p, (uint8_t *)ds.p);
+		else hipLaunchKernelGGL(k_stage_anchor, dim3(grid), dim3(64), 0, 0, (const DsbDevIndex *)si->dx.p, (StageAnc *)dc.p, base, n, (const uint8_t *)db.p, (DsbSeed *)dsd.p, (DsbAnchor *)da.p,
+		                        (const int32_t *)dq.p, (int64_t *)dm.p, (uint8_t *)ds.p);
+	}
+	CK(hipGetLastError() != hipSuccess);
+	CK(hipDeviceSynchronize() != hipSuccess);
+	CK(dc.down(cases)); CK(da.down(anchors)); if (n_mems) CK(dm.down(mems));
 	return 0;
 }

@@ -507,4 +507,145 @@ static inline int stage_finish_check(const StageFin *cs, uint32_t n, size_t n_ch
 	return 0;
 }
 
+// ---- the anchor stage a-4 .. a-8 (tests/test_stage_anchor.py): the FM search, fast_island, fast_classify, fast_classify_lane and slow_classify, called
+// as they are on a read's byte strands, its seed lists and a loaded index.
+//   dx      the index descriptor (host pointers in the emulation, device pointers on the GPU): copied to the LDS descriptor before each case
+//   seeds   per read (L >> 1) + 64 DsbSeed: the forward strand's list at seed_off, the reverse strand's at seed_off + (L >> 2) (the product's layout)
+//   anchors one region of anc_cap + STAGE3_GUARD DsbAnchor per case, filled with a pattern by the test: w.anc itself (ANC_LANE: the lane's scratch, copied)
+//   calls   form ANC_MEM: rows of 4 (string_index, max_rst, l_min, l_max), the searches of one walk in its order: the visited-row set carries over
+//   mems    form ANC_MEM: per call a row of STAGE3_MEM int64 in the layout of the oracle's trace: [5] MEMs found, [8 + 4 i ..] sp, match_len, sa_sp, sa_sp_l
+enum { ANC_MEM = 0, ANC_ISLAND = 1, ANC_FAST = 2, ANC_LANE = 3, ANC_SLOW = 4, ANC_WHOLE = 5 };
+#define STAGE3_GUARD 4u
+#define STAGE3_MEM 40u
+#define STAGE3_MAX_SEEDS 16384u    /* entries of the island lists of a slice: reads of up to 2 * (16384 - 64) bases */
+struct StageAnc {
+	uint32_t L, form, strand, anc_cap, step_limit, sp_gen, q0, n_q;       // q0, n_q: ANC_MEM the calls [q0, q0 + n_q); ANC_ISLAND q0 = the seed's index
+	uint32_t n_seed[2], total[2];                                         // [0] forward strand, [1] reverse strand
+	uint64_t bin_off, seed_off, anc_off, mem_off;
+	uint32_t n_anc, status, flag, lsteps, steps, sp_gen_out, defined, pad1;   // out; flag: fast_island's return value, fast_classify_lane's ovf
+};
+// its own slice: the visited-row sets (zeroed by the host entries once, as the kernels zero theirs once per launch), the lane scratch, the island
+// lists, fast_classify's order (w.sortidx), slow_classify's MEM list
+#define STAGE3_OFF_SPSET 0u
+#define STAGE3_OFF_LANE_SP (STAGE3_OFF_SPSET + DSB_SPHASH * 8u)
+#define STAGE3_OFF_LANE_ANC (STAGE3_OFF_LANE_SP + 64u * DSB_SPHASH * 8u)
+#define STAGE3_OFF_TOP (STAGE3_OFF_LANE_ANC + 64u * DSB_LANE_ANC_CAP * 40u)
+#define STAGE3_OFF_ROUND (STAGE3_OFF_TOP + STAGE3_MAX_SEEDS * 4u)
+#define STAGE3_OFF_ORD (STAGE3_OFF_ROUND + STAGE3_MAX_SEEDS * 4u)
+#define STAGE3_OFF_MEM (STAGE3_OFF_ORD + STAGE3_MAX_SEEDS * 4u)
+#define STAGE3_SLICE (STAGE3_OFF_MEM + ((DSB_MEMSLOW_CAP * 32u + 255u) & ~255u))
+static_assert(sizeof(DsbMem) == 32 && sizeof(DsbAnchor) == 40 && sizeof(DsbSeed) == 8, "slice of the anchor stage");
+
+DV void stage3_ctx(WCtxL &w, DSB_LDS_AS DsbDevIndex *sx, const DsbDevIndex *dx, uint8_t *slice, const StageAnc &c, DsbAnchor *anchors)
+{
+	wave_sync();
+	for (uint32_t i = (uint32_t)DSB_LANE; i < sizeof(DsbDevIndex) / 4u; i += DSB_WAVE) reinterpret_cast<DSB_LDS_AS uint32_t *>(sx)[i] = reinterpret_cast<const uint32_t *>(dx)[i];
+	wave_sync();
+	sx->step_limit = c.step_limit; sx->heavy_limit = 0;
+	w.spset = (uint64_t *)(slice + STAGE3_OFF_SPSET); w.lane_spset = (uint64_t *)(slice + STAGE3_OFF_LANE_SP); w.lane_anc = (DsbAnchor *)(slice + STAGE3_OFF_LANE_ANC);
+	w.top_idx = (uint32_t *)(slice + STAGE3_OFF_TOP); w.round_info = (uint32_t *)(slice + STAGE3_OFF_ROUND); w.sortidx = (uint32_t *)(slice + STAGE3_OFF_ORD);
+	w.mem_slow = (DsbMem *)(slice + STAGE3_OFF_MEM);
+	// (a case starts with empty sets whatever generation it starts at: the case before it on this slice may have used the same generations; the lanes' own
+	// sets are used by the lane-parallel forms only)
+	for (uint32_t i = (uint32_t)DSB_LANE; i < DSB_SPHASH; i += DSB_WAVE) w.spset[i] = 0;
+	if (c.form == ANC_FAST || c.form == ANC_WHOLE || c.form == ANC_LANE) for (uint32_t i = (uint32_t)DSB_LANE; i < (uint32_t)DSB_WAVE * DSB_SPHASH; i += DSB_WAVE) w.lane_spset[i] = 0;
+	w.anc = anchors + c.anc_off; w.anc_cap = w.anc_cap_main = c.anc_cap; w.n_anc = 0; w.status = 0; w.steps = w.lsteps = 0; w.step_limit = c.step_limit; w.sp_gen = c.sp_gen;
+	w.k.uni = 1;
+	wave_sync();
+}
+// forms (a), (b), (c), (e) and the whole read on one case
+DN void stage_anchor(WCtxL &w, DSB_LDS_AS DsbDevIndex *sx, const DsbDevIndex *dx, StageAnc *cs, const uint8_t *bin, DsbSeed *seeds, DsbAnchor *anchors, const int32_t *calls, int64_t *mems, uint8_t *slice)
+{
+	const StageAnc c = *cs;
+	const int lane = DSB_LANE;
+	stage3_ctx(w, sx, dx, slice, c, anchors);
+	w.bin = const_cast<uint8_t *>(bin) + c.bin_off + DSB_QPAD_L; w.L = c.L;
+	DsbXP x = w.x;
+	DsbSeed *const svF = seeds + c.seed_off, *const svR = svF + (c.L >> 2);
+	uint8_t *const binF = w.bin, *const binR = w.bin + c.L;
+	const bool fwd = c.strand == D_FORWARD;
+	SDirL *sd = w.sd;
+	uint32_t flag = 0, defined = 1;
+	if (c.L < 40) defined = c.form == ANC_WHOLE;                             // (classify_read returns before the anchor stage)
+	else if (c.form == ANC_MEM) {
+		LCtx l = lctx_main(w);
+		SpSet sp_set = {l.spset, 0, DSB_SPSET_CAP, l.sp_gen};
+		sp_set_reset(sp_set);
+		const uint8_t *bin_read = fwd ? binF : binR;
+		for (uint32_t q = 0; q < c.n_q; q++) {
+			const int32_t *r = calls + 4 * (size_t)(c.q0 + q);
+			DsbMem mem[8];
+			const int n = bwt_MEM_search(x, l.k, bin_read + r[0], prefix13(bin_read, r[0]), r[1], r[2], r[3], sp_set, mem);
+			wave_sync();
+			if (lane == 0) {
+				int64_t *o = mems + STAGE3_MEM * (c.mem_off + q);
+				o[5] = n;
+				for (int i = 0; i < n && i < 8; i++) { o[8 + 4 * i] = (int64_t)mem[i].sp; o[9 + 4 * i] = mem[i].match_len; o[10 + 4 * i] = (int64_t)mem[i].sa_sp; o[11 + 4 * i] = mem[i].sa_sp_l; }
+			}
+		}
+		l.sp_gen = sp_set.gen; lctx_done(w, l);
+	} else if (c.form == ANC_ISLAND) {
+		// the redo form of fast_classify's commit: the whole wavefront walks one island straight into the main array
+		const SDirV s_d = {fwd ? svF : svR, fwd ? binF : binR, c.strand};
+		LCtx l = lctx_main(w); l.anc_cap = w.anc_cap_main;
+		flag = (uint32_t)fast_island(x, l, s_d, c.L, c.q0);
+		lctx_done(w, l);
+	} else if (c.form == ANC_FAST || c.form == ANC_SLOW) {
+		sdir_set(sd, fwd ? svF : svR, c.n_seed[fwd ? 0 : 1], fwd ? binF : binR, nullptr, c.strand, c.total[fwd ? 0 : 1]);
+		wave_sync();
+		if (c.form == ANC_FAST) fast_classify(w, sd, c.L); else slow_classify(w, sd, c.L);
+	} else if (c.form == ANC_WHOLE) {
+		// RESTATED, not called: the strand swap and the both-direction rule of classify_read and k_anchor (dsb_gpu.hip) around fast_classify; a change
+		// of theirs shows in the whole-read tests, not here
+		sdir_set(sd, svF, c.n_seed[0], binF, nullptr, D_FORWARD, c.total[0]);
+		sdir_set(sd + 1, svR, c.n_seed[1], binR, nullptr, D_REVERSE, c.total[1]);
+		wave_sync();
+		if (sd[0].total_score < sd[1].total_score) sdir_swap(sd, sd + 1);
+		wave_sync();
+		const bool both_direction = ((sd[0].total_score - sd[1].total_score) <= (sd[0].total_score >> 3));
+		fast_classify(w, sd, c.L);
+		if (both_direction) fast_classify(w, sd + 1, c.L);
+	} else defined = 0;
+	wave_sync();
+	if (lane == 0) { cs->n_anc = w.n_anc; cs->status = (uint32_t)w.status; cs->flag = flag; cs->lsteps = w.lsteps; cs->steps = w.steps; cs->sp_gen_out = w.sp_gen; cs->defined = defined; }
+	wave_sync();
+}
+// form (d): fast_classify_lane, one read per lane: the cases [k0, k0 + DSB_WAVE) of the list, each lane's anchors copied from its scratch to its case's region
+DN void stage_anchor_lane(WCtxL &w, DSB_LDS_AS DsbDevIndex *sx, const DsbDevIndex *dx, StageAnc *cases, uint32_t k0, uint32_t n, const uint8_t *bin, DsbSeed *seeds, DsbAnchor *anchors, uint8_t *slice)
+{
+	const int lane = DSB_LANE;
+	const bool valid = k0 + (uint32_t)lane < n;
+	StageAnc c = cases[valid ? k0 + (uint32_t)lane : k0];
+	{ StageAnc c0 = cases[k0]; c0.anc_off = 0; stage3_ctx(w, sx, dx, slice, c0, anchors); }     // (wave-uniform: the first case's budget and generation)
+	DsbSeedInfo si; si.n_seed[0] = c.n_seed[0]; si.n_seed[1] = c.n_seed[1]; si.total[0] = c.total[0]; si.total[1] = c.total[1]; si.flags = 0; si.pad = 0;
+	uint32_t na = 0, ovf = 0;
+	fast_classify_lane(w, valid, const_cast<uint8_t *>(bin) + c.bin_off + DSB_QPAD_L, c.L, seeds + c.seed_off, &si, &na, &ovf);
+	if (valid) {
+		const DsbAnchor *src = w.lane_anc + (size_t)lane * DSB_LANE_ANC_CAP;
+		DsbAnchor *dst = anchors + c.anc_off;
+		for (uint32_t i = 0; i < na && i < c.anc_cap; i++) dst[i] = src[i];
+		StageAnc *o = cases + k0 + lane;
+		o->n_anc = na; o->flag = ovf; o->status = 0; o->defined = c.anc_cap >= DSB_LANE_ANC_CAP; o->sp_gen_out = w.sp_gen; o->lsteps = 0; o->steps = 0;
+	}
+	wave_sync();
+}
+static inline int stage_anchor_check(const StageAnc *cs, uint32_t n, size_t bin_bytes, size_t n_seeds, size_t n_anchors, const int32_t *calls, size_t n_calls, size_t n_mems, const DsbSeed *seeds, int ek_len)
+{
+	for (uint32_t k = 0; k < n; k++) {
+		const StageAnc &c = cs[k];
+		if (c.form > ANC_WHOLE || c.strand > 1 || c.bin_off + DSB_QPAD_L + 2 * (size_t)c.L + DSB_QPAD_R > bin_bytes || c.seed_off + (c.L >> 1) + 64 > n_seeds) return 1;
+		if ((c.L >> 1) + 64 > STAGE3_MAX_SEEDS || c.n_seed[0] > (c.L >> 2) || c.n_seed[1] > (c.L >> 2) + 64 || c.anc_cap < 1 || c.anc_off + c.anc_cap + STAGE3_GUARD > n_anchors) return 1;
+		if (c.form == ANC_LANE && c.anc_cap < DSB_LANE_ANC_CAP) return 1;
+		if (c.L < 40) continue;
+		for (int s = 0; s < 2; s++)                                          // every window of a seed lies in the read
+			for (uint32_t i = 0; i < c.n_seed[s]; i++) { const DsbSeed &v = seeds[c.seed_off + (s ? (c.L >> 2) : 0) + i]; if (v.len < 1 || v.len > 61 || (size_t)v.offset + v.len + (size_t)ek_len - 1 > c.L) return 1; }
+		if (c.form == ANC_ISLAND && c.q0 >= c.n_seed[c.strand == D_FORWARD ? 0 : 1]) return 1;
+		if (c.form == ANC_MEM) {
+			if ((size_t)c.q0 + c.n_q > n_calls || c.mem_off + c.n_q > n_mems) return 1;
+			for (uint32_t q = 0; q < c.n_q; q++) { const int32_t *r = calls + 4 * (size_t)(c.q0 + q); if (r[0] < 12 || (uint32_t)r[0] >= c.L || r[1] < 1 || r[1] > 8 || r[3] != r[0]) return 1; }
+		}
+	}
+	return 0;
+}
+
 }  // namespace
