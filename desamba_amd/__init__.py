@@ -114,6 +114,17 @@ class DsbLcaSummary(C.Structure):
 LCA_SUMMARY_FIELDS = ("reads", "classified", "no_taxon", "ambiguous", "min_permille")
 
 
+class DsbHitIdentity(C.Structure):
+    _fields_ = [("edits", C.c_uint32), ("q_len", C.c_uint32), ("t_len", C.c_uint32), ("flags", C.c_uint32)]
+
+
+DSB_IDENT_EXACT, DSB_IDENT_OVER, DSB_IDENT_SKEW, DSB_IDENT_EMPTY = 1, 2, 4, 8
+DSB_IDENT_MAX_SKEW, DSB_IDENT_MAX_BAND, DSB_IDENT_BAND_DEFAULT, DSB_IDENT_PERMILLE_DEFAULT = 4096, 1024, 256, 300
+HIT_IDENTITY_DTYPE = [("edits", "<u4"), ("q_len", "<u4"), ("t_len", "<u4"), ("flags", "<u4")]
+REF_IDENTITY_FIELDS = ("records", "q_bases", "t_bases", "edits", "exact", "unaligned")
+REF_IDENTITY_DTYPE = [(f, "<u8") for f in REF_IDENTITY_FIELDS]
+
+
 class DsbChunk(C.Structure):
     _fields_ = [("start", C.c_uint64), ("end", C.c_uint64), ("hist_max_before", C.c_uint32), ("rank", C.c_int32)]
 
@@ -133,7 +144,9 @@ EXPORTS = ["dsb_index_open", "dsb_index_close", "dsb_index_n_ref", "dsb_index_re
            "dsb_multi_abundance", "dsb_abundance_format",
            "dsb_ctx_set_batch_ordinal", "dsb_ctx_abundance_assign", "dsb_multi_abundance_assign", "dsb_format_assign",
            "dsb_ctx_enable_lca", "dsb_ctx_reset_lca", "dsb_batch_lca", "dsb_ctx_lca_counts", "dsb_multi_enable_lca", "dsb_multi_lca",
-           "dsb_multi_lca_counts", "dsb_taxnames_load", "dsb_taxnames_close", "dsb_format_kraken", "dsb_lca_report_format"]
+           "dsb_multi_lca_counts", "dsb_taxnames_load", "dsb_taxnames_close", "dsb_format_kraken", "dsb_lca_report_format",
+           "dsb_ctx_enable_identity", "dsb_ctx_reset_identity", "dsb_batch_identity", "dsb_ctx_identity", "dsb_multi_enable_identity",
+           "dsb_multi_identity", "dsb_multi_ref_identity", "dsb_format_identity", "dsb_identity_format", "dsb_index_ref_bases", "dsb_ctx_edit_pairs"]
 
 _lib = None
 
@@ -235,6 +248,17 @@ def lib():
     L.dsb_taxnames_close.argtypes = [C.c_void_p]; L.dsb_taxnames_close.restype = None
     L.dsb_format_kraken.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]; L.dsb_format_kraken.restype = C.c_long
     L.dsb_lca_report_format.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_char_p, C.c_size_t]; L.dsb_lca_report_format.restype = C.c_long
+    L.dsb_ctx_enable_identity.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32]
+    L.dsb_ctx_reset_identity.argtypes = [C.c_void_p]
+    L.dsb_batch_identity.argtypes = [C.c_void_p, C.POINTER(C.POINTER(DsbHitIdentity))]
+    L.dsb_ctx_identity.argtypes = [C.c_void_p, C.c_void_p]
+    L.dsb_multi_enable_identity.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32]
+    L.dsb_multi_identity.argtypes = [C.c_void_p, C.POINTER(C.POINTER(DsbHitIdentity))]
+    L.dsb_multi_ref_identity.argtypes = [C.c_void_p, C.c_void_p]
+    L.dsb_format_identity.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]; L.dsb_format_identity.restype = C.c_long
+    L.dsb_identity_format.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]; L.dsb_identity_format.restype = C.c_long
+    L.dsb_index_ref_bases.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p]
+    L.dsb_ctx_edit_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p]
     L.dsb_strerror.argtypes = [C.c_int]; L.dsb_strerror.restype = C.c_char_p
     L.dsb_version.restype = C.c_char_p
     _lib = L
@@ -274,6 +298,15 @@ class Index:
 
     def ref_len(self, i):
         return int(lib().dsb_index_ref_len(self.h, i))
+
+    def ref_bases(self, i, start, length):
+        """bases [start, start + length) of reference i from the host copy of the 2-bit text: numpy u8 codes (0 A, 1 C, 2 G, 3 T)"""
+        import numpy as np
+        out = np.zeros(int(length), dtype=np.uint8)
+        rc = lib().dsb_index_ref_bases(self.h, int(i), int(start), int(length), out.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            raise DsbError(rc, "dsb_index_ref_bases(%d, %d, %d)" % (i, start, length))
+        return out
 
     def occ_host(self, r, c):
         cc = C.c_uint8(c)
@@ -507,6 +540,52 @@ class Ctx:
         """everything since enable / reset: (the taxa with clade_reads > 0 in ascending taxid, TAXON_COUNT_DTYPE; summary dict)"""
         return _lca_counts(lib().dsb_ctx_lca_counts, self.h, "dsb_ctx_lca_counts")
 
+    def enable_identity(self, on=True, band=None, max_frac=None):
+        """per-hit edit distance and per-reference identity from now on (banded alignment of every primary and supplementary record),
+        or off (freed).  band: diagonals on either side of the corridor, 0 .. 1024 [256]; max_frac: a record with more edits than
+        max_frac x its length is reported as over the cap, 0 < max_frac <= 1 in steps of 0.001 [0.3]"""
+        b = DSB_IDENT_BAND_DEFAULT if band is None else int(band)
+        p = DSB_IDENT_PERMILLE_DEFAULT if max_frac is None else _permille(max_frac)
+        rc = lib().dsb_ctx_enable_identity(self.h, 1 if on else 0, b if on else 0, p if on else 0)
+        if rc != 0:
+            raise DsbError(rc, "dsb_ctx_enable_identity")
+
+    def reset_identity(self):
+        rc = lib().dsb_ctx_reset_identity(self.h)
+        if rc != 0:
+            raise DsbError(rc, "dsb_ctx_reset_identity")
+
+    def identity(self, n_hits):
+        """the identity record of each hit of the last batch (n_hits = its result's n_hits): numpy structured array (HIT_IDENTITY_DTYPE)"""
+        p = C.POINTER(DsbHitIdentity)()
+        rc = lib().dsb_batch_identity(self.h, C.byref(p))
+        if rc != 0:
+            raise DsbError(rc, "dsb_batch_identity")
+        return _hit_identity(p, int(n_hits))
+
+    def ref_identity(self):
+        """everything since enable / reset: numpy structured array of n_ref rows (REF_IDENTITY_FIELDS, u64)"""
+        return _ref_identity(lib().dsb_ctx_identity, self.h, self.index.n_ref, "dsb_ctx_identity")
+
+    def edit_pairs(self, q_codes, q_off, q_len, t_codes, t_off, t_len, band=DSB_IDENT_BAND_DEFAULT, max_permille=DSB_IDENT_PERMILLE_DEFAULT):
+        """dsb_ctx_edit_pairs: pair p aligns q_codes[q_off[p] : q_off[p] + q_len[p]] with t_codes[t_off[p] : ...] (u8 codes 0 .. 3) by the
+        device function of k_hit_edits; returns a numpy structured array of one record per pair (HIT_IDENTITY_DTYPE)"""
+        import numpy as np
+        qc = np.ascontiguousarray(q_codes, dtype=np.uint8); tc = np.ascontiguousarray(t_codes, dtype=np.uint8)
+        qo = np.ascontiguousarray(q_off, dtype=np.uint64); to = np.ascontiguousarray(t_off, dtype=np.uint64)
+        ql = np.ascontiguousarray(q_len, dtype=np.uint32); tl = np.ascontiguousarray(t_len, dtype=np.uint32)
+        n = len(qo)
+        if not (len(to) == len(ql) == len(tl) == n):
+            raise ValueError("edit_pairs: the four offset and length arrays differ in length")
+        if n and (int((qo + ql).max()) > len(qc) or int((to + tl).max()) > len(tc)):
+            raise ValueError("edit_pairs: a pair reaches beyond its codes")
+        out = np.zeros(n, dtype=HIT_IDENTITY_DTYPE)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        rc = lib().dsb_ctx_edit_pairs(self.h, p(qc), p(qo), p(ql), p(tc), p(to), p(tl), n, int(band), int(max_permille), p(out))
+        if rc != 0:
+            raise DsbError(rc, "dsb_ctx_edit_pairs")
+        return out
+
     def in_last_batch(self):
         return self.ran[1]
 
@@ -630,6 +709,25 @@ class Multi:
     def lca_counts(self):
         """Ctx.lca_counts over the contexts' reads together"""
         return _lca_counts(lib().dsb_multi_lca_counts, self.h, "dsb_multi_lca_counts")
+
+    def enable_identity(self, on=True, band=None, max_frac=None):
+        b = DSB_IDENT_BAND_DEFAULT if band is None else int(band)
+        p = DSB_IDENT_PERMILLE_DEFAULT if max_frac is None else _permille(max_frac)
+        rc = lib().dsb_multi_enable_identity(self.h, 1 if on else 0, b if on else 0, p if on else 0)
+        if rc != 0:
+            raise DsbError(rc, "dsb_multi_enable_identity")
+
+    def identity(self, n_hits):
+        """Ctx.identity for the last classify(): one record per hit of its result"""
+        p = C.POINTER(DsbHitIdentity)()
+        rc = lib().dsb_multi_identity(self.h, C.byref(p))
+        if rc != 0:
+            raise DsbError(rc, "dsb_multi_identity")
+        return _hit_identity(p, int(n_hits))
+
+    def ref_identity(self):
+        """Ctx.ref_identity added over the contexts"""
+        return _ref_identity(lib().dsb_multi_ref_identity, self.h, self.index.n_ref, "dsb_multi_ref_identity")
 
     def taxa(self, records=False):
         """Ctx.taxa for the last classify(), in input order"""
@@ -807,6 +905,61 @@ def _lca_counts(fn, h, what):
         if rc != 0:
             raise DsbError(rc, what)
     return out, {f: getattr(s, f) for f in LCA_SUMMARY_FIELDS}
+
+
+def _hit_identity(p, n):
+    import numpy as np
+    out = np.zeros(n, dtype=HIT_IDENTITY_DTYPE)
+    if n:
+        C.memmove(out.ctypes.data, p, n * C.sizeof(DsbHitIdentity))
+    return out
+
+
+def _ref_identity(fn, h, n_ref, what):
+    import numpy as np
+    out = np.zeros(n_ref, dtype=REF_IDENTITY_DTYPE)
+    rc = fn(h, out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise DsbError(rc, what)
+    return out
+
+
+def format_identity(index, reads, res, ident):
+    """dsb_format_identity over a batch: the per-record lines (bytes) of make_reads()'s array, its result and Ctx/Multi.identity()'s records"""
+    import numpy as np
+    ident = np.ascontiguousarray(ident, dtype=HIT_IDENTITY_DTYPE)
+    if len(ident) != res.n_hits:
+        raise ValueError("format_identity: %d records for %d hits" % (len(ident), res.n_hits))
+    out = []
+    for i in range(len(reads)):
+        rr = res.reads[i]
+        hits = C.byref(res.hits.contents, rr.first * C.sizeof(DsbHit)) if rr.n else None
+        idp = ident[rr.first:rr.first + rr.n].ctypes.data_as(C.c_void_p) if rr.n else None
+        cap = 512 + 256 * rr.n + len(reads[i].name) * (rr.n + 1)
+        while True:
+            buf = C.create_string_buffer(cap)
+            n = lib().dsb_format_identity(index.h, C.byref(reads[i]), C.byref(rr), hits, idp, buf, cap)
+            if n >= 0:
+                out.append(buf.raw[:n]); break
+            if cap > (1 << 26):
+                raise DsbError(DSB_EINVAL, "dsb_format_identity")
+            cap *= 4
+    return b"".join(out)
+
+
+def format_ref_identity(index, tab):
+    """dsb_identity_format: the per-reference identity table (bytes) of Ctx/Multi.ref_identity()'s array"""
+    import numpy as np
+    tab = np.ascontiguousarray(tab, dtype=REF_IDENTITY_DTYPE)
+    if len(tab) != index.n_ref:
+        raise ValueError("format_ref_identity: %d rows for %d references" % (len(tab), index.n_ref))
+    cap = 1 << 16
+    while True:
+        buf = C.create_string_buffer(cap)
+        n = lib().dsb_identity_format(index.h, tab.ctypes.data_as(C.c_void_p), buf, cap)
+        if n >= 0:
+            return buf.raw[:n]
+        cap *= 4
 
 
 def format_kraken(reads, lca):

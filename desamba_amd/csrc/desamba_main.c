@@ -63,6 +63,7 @@ typedef struct {
 	dsb_read_result *rr; dsb_hit *hits; size_t cap_rr, cap_hits, n_hits;
 	dsb_read_taxon *taxa; size_t cap_taxa;            /* --report: the device's per-read taxa of the batch */
 	dsb_read_lca *lca; size_t cap_lca;                /* --kraken-out / --kraken-report: the device's per-read LCA records of the batch */
+	dsb_hit_identity *ident; size_t cap_ident;        /* --identity: the device's per-hit identity records of the batch (parallel to hits) */
 } batch_t;
 
 typedef struct { batch_t *slot[N_BATCH + 2]; int head, n, closed; pthread_mutex_t mu; pthread_cond_t cv; } queue_t;
@@ -136,6 +137,8 @@ typedef struct {
 	dsb_taxonomy *tx; dsb_report *rep; FILE *rep_out[2];
 	/* --kraken-out / --kraken-report: LCA classification on; the per-read lines are written by the writer in input order */
 	int lca_on; FILE *kr_out;
+	/* --identity / --identity-refs: per-hit edit distance on; the per-record lines are written by the writer in input order */
+	int ident_on; FILE *id_out;
 	/* --abundance-reads: each batch runs under the input index of its first read, and the writer keeps every read's
 	 * QNAME, NUL-terminated, in input order, for the lines written when the run ends */
 	int keep_names; char *qnames; size_t qnames_len, qnames_cap;
@@ -774,6 +777,12 @@ static void *gpu_main(void *arg)
 				if (b->n > b->cap_lca) { b->cap_lca = b->n * 2; b->lca = xrealloc(b->lca, b->cap_lca * sizeof *b->lca); }
 				memcpy(b->lca, t, b->n * sizeof *b->lca);
 			}
+			if (a->id_out) {
+				const dsb_hit_identity *t; int rt = dsb_batch_identity(ctx, &t);
+				if (rt) { fprintf(stderr, "[dsb_batch_identity] %s\n", dsb_strerror(rt)); exit(1); }
+				if (res.n_hits > b->cap_ident) { b->cap_ident = res.n_hits * 2; b->ident = xrealloc(b->ident, b->cap_ident * sizeof *b->ident); }
+				if (res.n_hits) memcpy(b->ident, t, res.n_hits * sizeof *b->ident);
+			}
 			t_idle = now();
 		}
 		q_push(&a->done_q, b);
@@ -846,6 +855,21 @@ static void *writer_main(void *arg)
 				if (fwrite(kb, 1, (size_t)w, a->kr_out) != (size_t)w) die("[classify] cannot write the per-read classifications");
 			}
 		}
+		if (a->id_out) {
+			/* the identity lines of the batch's counted records, from the device's records, in input order */
+			static char *ib; static size_t icap;
+			for (size_t i = 0; i < b->n; i++) {
+				const dsb_read_result *rr = &b->rr[i];
+				const size_t need = (strlen(b->reads[i].name) + 384) * ((size_t)rr->n + 1);
+				if (need > icap) { icap = need * 2; ib = xrealloc(ib, icap); }
+				long w;   /* (reference names are not bounded by the estimate: a buffer too small grows) */
+				while ((w = dsb_format_identity(a->idx, &b->reads[i], rr, b->hits + rr->first, b->ident + rr->first, ib, icap)) < 0) {
+					if (icap > ((size_t)1 << 30)) die("[dsb_format_identity] cannot format a record");
+					icap *= 4; ib = xrealloc(ib, icap);
+				}
+				if (fwrite(ib, 1, (size_t)w, a->id_out) != (size_t)w) die("[classify] cannot write the per-record identities");
+			}
+		}
 		if (a->keep_names)
 			for (size_t i = 0; i < b->n; i++) {
 				const size_t l = strlen(b->reads[i].name) + 1;
@@ -893,7 +917,13 @@ static void usage(void)
 	fprintf(stderr, "                     puts its k-mer string in that fifth column; the first four are Kraken's)\n");
 	fprintf(stderr, "    --kraken-report FILE  write the reads per taxon of that classification into FILE in the format of `kraken2 --report` (needs --taxonomy)\n");
 	fprintf(stderr, "    --names FILE     names.dmp: the report prints scientific names instead of taxids\n");
-	fprintf(stderr, "    --lca-min-frac F  near-best: hits whose AS is at least F x the read's best AS, 0 < F <= 1 [0.95]\n\n");
+	fprintf(stderr, "    --lca-min-frac F  near-best: hits whose AS is at least F x the read's best AS, 0 < F <= 1 [0.95]\n");
+	fprintf(stderr, "    --identity FILE  align every primary and supplementary record to its reference interval on the GPU (banded edit distance) and\n");
+	fprintf(stderr, "                     write one line per record into FILE: read name, reference, strand, qs, qe, ts, te, AS, edits, identity, flags\n");
+	fprintf(stderr, "                     (flags: 1 the band did not matter, 2 over the edit cap, 4 lengths too different, 8 empty interval)\n");
+	fprintf(stderr, "    --identity-refs FILE  write records, bases, edits and identity per reference of those alignments into FILE when the run ends\n");
+	fprintf(stderr, "    --identity-band N  diagonals on either side of the corridor between the record's corners, 0 <= N <= 1024 [256]\n");
+	fprintf(stderr, "    --identity-max-frac F  stop aligning a record after F x its length edits (it is reported as over the cap), 0 < F <= 1 [0.3]\n\n");
 }
 
 static double now(void) { struct timeval tv; gettimeofday(&tv, NULL); return tv.tv_sec + tv.tv_usec * 1e-6; }
@@ -965,9 +995,12 @@ static int classify_main(int argc, char **argv)
 	                                              {"kraken-report", required_argument, NULL, 8}, {"names", required_argument, NULL, 9},
 	                                              {"lca-min-frac", required_argument, NULL, 10}, {"abundance-reads", required_argument, NULL, 11},
 	                                              {"coverage-windows", required_argument, NULL, 12}, {"coverage-window-size", required_argument, NULL, 13},
+	                                              {"identity", required_argument, NULL, 14}, {"identity-refs", required_argument, NULL, 15},
+	                                              {"identity-band", required_argument, NULL, 16}, {"identity-max-frac", required_argument, NULL, 17},
 	                                              {NULL, 0, NULL, 0}};
 	const char *tax_path = NULL, *rep_path[2] = {NULL, NULL}, *cov_path = NULL, *ab_path = NULL, *kr_path = NULL, *krep_path = NULL, *names_path = NULL, *abr_path = NULL, *covw_path = NULL;
 	uint32_t ab_permille = 950, lca_permille = 950, cov_window = 1000; int lca_frac_set = 0, cov_window_set = 0;
+	const char *id_path = NULL, *idr_path = NULL; uint32_t id_band = DSB_IDENT_BAND_DEFAULT, id_permille = DSB_IDENT_PERMILLE_DEFAULT; int id_opt_set = 0;
 	while ((c = getopt_long(argc, argv, "ht:l:r:f:o:s:g:", long_opts, NULL)) >= 0) {
 		if (c == 'h') { usage(); return 0; }
 		else if (c == 1) tax_path = optarg;
@@ -993,6 +1026,18 @@ static int classify_main(int argc, char **argv)
 			char *e; const long long v = strtoll(optarg, &e, 10);
 			if (e == optarg || *e || v < 1 || v >= (1ll << 31)) die("[classify] --coverage-window-size takes a number of bases W with 1 <= W < 2^31");
 			cov_window = (uint32_t)v; cov_window_set = 1;
+		}
+		else if (c == 14) id_path = optarg;
+		else if (c == 15) idr_path = optarg;
+		else if (c == 16) {
+			char *e; const long long v = strtoll(optarg, &e, 10);
+			if (e == optarg || *e || v < 0 || v > DSB_IDENT_MAX_BAND) die("[classify] --identity-band takes a number of diagonals N with 0 <= N <= 1024");
+			id_band = (uint32_t)v; id_opt_set = 1;
+		}
+		else if (c == 17) {
+			char *e; const double f = strtod(optarg, &e);
+			if (e == optarg || *e || !(f > 0 && f <= 1) || f * 1000 + 0.5 < 1) die("[classify] --identity-max-frac takes a number F with 0 < F <= 1 (steps of 0.001)");
+			id_permille = (uint32_t)(f * 1000 + 0.5); id_opt_set = 1;
 		}
 		else if (c == '?' && optopt == 11) die("[classify] --abundance-reads takes a file name");   /* (last on the line: getopt_long found no argument) */
 		else if (c == 't') { /* thread count: accepted for compatibility, unused */ }
@@ -1030,7 +1075,9 @@ static int classify_main(int argc, char **argv)
 	if ((rep_path[0] || rep_path[1]) && !tax_path) die("[classify] --report and --report-base need --taxonomy nodes.dmp");
 	if ((kr_path || krep_path || names_path || lca_frac_set) && !tax_path) die("[classify] --kraken-out, --kraken-report, --names and --lca-min-frac need --taxonomy nodes.dmp");
 	if (cov_window_set && !covw_path) die("[classify] --coverage-window-size needs --coverage-windows FILE");
+	if (id_opt_set && !id_path && !idr_path) die("[classify] --identity-band and --identity-max-frac need --identity FILE or --identity-refs FILE");
 	a.lca_on = kr_path || krep_path;
+	a.ident_on = id_path || idr_path;
 	dsb_taxnames *names = NULL;
 	if (tax_path) {
 		int rt = dsb_taxonomy_load(tax_path, &a.tx);
@@ -1044,6 +1091,9 @@ static int classify_main(int argc, char **argv)
 	if (names_path && (rc_names(names_path, &names))) exit(1);
 	if (kr_path && !(a.kr_out = fopen(kr_path, "w"))) { fprintf(stderr, "[xopen] fail to open file '%s'\n", kr_path); exit(1); }
 	if (krep_path && !(krep_out = fopen(krep_path, "w"))) { fprintf(stderr, "[xopen] fail to open file '%s'\n", krep_path); exit(1); }
+	FILE *idr_out = NULL;
+	if (id_path && !(a.id_out = fopen(id_path, "w"))) { fprintf(stderr, "[xopen] fail to open file '%s'\n", id_path); exit(1); }
+	if (idr_path && !(idr_out = fopen(idr_path, "w"))) { fprintf(stderr, "[xopen] fail to open file '%s'\n", idr_path); exit(1); }
 	FILE *cov_out = NULL;
 	if (cov_path && !(cov_out = fopen(cov_path, "w"))) { fprintf(stderr, "[xopen] fail to open file '%s'\n", cov_path); exit(1); }
 	FILE *covw_out = NULL;
@@ -1072,6 +1122,7 @@ static int classify_main(int argc, char **argv)
 	if (covw_out && (rc = dsb_multi_enable_coverage_windows(a.multi, cov_window))) { fprintf(stderr, "\n[dsb_ctx_enable_coverage_windows] %s\n", dsb_strerror(rc)); exit(1); }
 	if ((ab_out || abr_out) && (rc = dsb_multi_enable_abundance(a.multi, 1, ab_permille))) { fprintf(stderr, "\n[dsb_ctx_enable_abundance] %s\n", dsb_strerror(rc)); exit(1); }
 	if (a.lca_on && (rc = dsb_multi_enable_lca(a.multi, 1, lca_permille))) { fprintf(stderr, "\n[dsb_ctx_enable_lca] %s\n", dsb_strerror(rc)); exit(1); }
+	if (a.ident_on && (rc = dsb_multi_enable_identity(a.multi, 1, id_band, id_permille))) { fprintf(stderr, "\n[dsb_ctx_enable_identity] %s\n", dsb_strerror(rc)); exit(1); }
 	double t0 = now(), cpu0 = cputime(); a.t0 = t0;
 	a.thr0 = a.trace ? throttled_usec() : -1;
 	fprintf(stderr, "Start classify\n");
@@ -1168,6 +1219,17 @@ static int classify_main(int argc, char **argv)
 		free(ab);
 	}
 	if (a.kr_out && fclose(a.kr_out)) die("[classify] cannot write the per-read classifications");
+	if (a.id_out && fclose(a.id_out)) die("[classify] cannot write the per-record identities");
+	if (idr_out) {
+		/* --identity-refs: the run's per-reference identity table, the contexts' tables added */
+		const size_t n_ref = (size_t)dsb_index_n_ref(a.idx);
+		dsb_ref_identity *tab = xrealloc(NULL, (n_ref ? n_ref : 1) * sizeof *tab);
+		if ((rc = dsb_multi_ref_identity(a.multi, tab))) { fprintf(stderr, "[dsb_multi_ref_identity] %s\n", dsb_strerror(rc)); exit(1); }
+		size_t cap = 1 << 16; char *buf = NULL; long w;
+		do { cap *= 4; buf = xrealloc(buf, cap); w = dsb_identity_format(a.idx, tab, buf, cap); } while (w < 0);
+		if (fwrite(buf, 1, (size_t)w, idr_out) != (size_t)w || fclose(idr_out)) die("[classify] cannot write the identity table");
+		free(buf); free(tab);
+	}
 	if (krep_out) {
 		/* --kraken-report: the run's reads per taxon, the contexts' counts added and rolled up on the device */
 		size_t n_rows = 0; dsb_lca_summary sum;

@@ -75,7 +75,7 @@ struct dsb_ctx {
 	uint32_t *dbg_host = nullptr, *dbg_dev = nullptr;
 	std::vector<UpStage> up; size_t up_chunk = 0;     // pinned staging of dsb_batch_upload (upload_gather)
 	dsb_opts opts;
-	DsbTaxa taxa; DsbCover cover; DsbEmStore em; DsbLca lca;   // the run reductions (dsb_reductions.h)
+	DsbTaxa taxa; DsbCover cover; DsbEmStore em; DsbLca lca; DsbIdent ident;   // the run reductions (dsb_reductions.h, dsb_identity.h)
 	dsb_ctx() { memset(&dx, 0, sizeof dx); memset(&arena, 0, sizeof arena); memset(&arena_big, 0, sizeof arena_big); memset(&arena_anc, 0, sizeof arena_anc); memset(&timing, 0, sizeof timing); memset(&opts, 0, sizeof opts); }
 };
 
@@ -86,6 +86,7 @@ struct dsb_multi {
 	std::vector<dsb_read_result> reads; std::vector<dsb_hit> hits;
 	const dsb_taxonomy *tx = nullptr; std::vector<dsb_read_taxon> taxa; bool taxa_ok = false;   // dsb_multi_set_taxonomy / dsb_multi_taxa
 	std::vector<dsb_read_lca> lca; bool lca_on = false, lca_ok = false;                          // dsb_multi_enable_lca / dsb_multi_lca
+	std::vector<dsb_hit_identity> ident; bool ident_on = false, ident_ok = false;                // dsb_multi_enable_identity / dsb_multi_identity
 };
 
 // a device buffer grown to hold at least `need` elements (its contents are not kept)

@@ -1786,6 +1786,7 @@ static int batch_run_locked(dsb_ctx *c, std::unique_lock<std::mutex> *turn)
 	c->timing.upload_bytes = s.upload_bytes;
 	c->taxa.run = c->taxa.tx != nullptr && n == 0; c->taxa.done = false;
 	c->lca.run = c->lca.d_direct != nullptr && n == 0; c->lca.done = false;
+	c->ident.run = c->ident.d_tab != nullptr && n == 0; c->ident.done = false;
 	if (n == 0) return DSB_OK;
 	const BatchPlan p = batch_plan(c, s);
 	c->n_early = p.n_heavy; c->timing.n_heavy_mw = p.n_mw;
@@ -1808,7 +1809,7 @@ static int batch_run_locked(dsb_ctx *c, std::unique_lock<std::mutex> *turn)
 	HIPCHK(hipEventSynchronize(c->ev[3]));
 	if ((rc = stage_regrow(c, s, p))) return rc;
 	// the run reductions (dsb_reductions.hip), after every classify launch of the batch
-	const DsbBatchView hits = {c->stream, c->d_rout, c->d_hout, c->d_counters, c->cap_hout, s.d_rd, (uint32_t)n, ord_set, s.ord_first};
+	const DsbBatchView hits = {c->stream, c->d_rout, c->d_hout, c->d_counters, c->cap_hout, s.d_rd, (uint32_t)n, c->d_pk, ord_set, s.ord_first};
 	if ((rc = reductions_run(c, hits))) return rc;
 	stage_debug_report(c, s, p);
 	HIPCHK(hipGetLastError());
@@ -2010,6 +2011,8 @@ extern "C" int dsb_multi_classify_batch(dsb_multi *m, const dsb_read *reads, siz
 	m->reads.assign(n, dsb_read_result());
 	m->taxa_ok = false; if (m->tx) m->taxa.assign(n, dsb_read_taxon());
 	m->lca_ok = false; if (m->lca_on) m->lca.assign(n, dsb_read_lca());
+	m->ident_ok = false; m->ident.clear();
+	std::vector<std::vector<dsb_hit_identity>> chunk_ident(nc);
 	std::vector<std::vector<dsb_hit>> chunk_hits(nc);
 	std::vector<int> rcs(W, DSB_OK);
 	const uint32_t hist0 = m->hist;
@@ -2041,11 +2044,14 @@ extern "C" int dsb_multi_classify_batch(dsb_multi *m, const dsb_read *reads, siz
 				if ((rc = dsb_batch_lca(c, &t))) { rcs[w] = rc; return; }
 				std::copy(t, t + (ch.end - ch.start), m->lca.begin() + (ptrdiff_t)ch.start);
 			}
+			const dsb_hit_identity *idn = nullptr;
+			if (m->ident_on && (rc = dsb_batch_identity(c, &idn))) { rcs[w] = rc; return; }
 			std::vector<dsb_hit> &H = chunk_hits[k];
 			for (uint64_t i = ch.start; i < ch.end; i++) {
 				dsb_read_result rr = r.reads[i - ch.start];
 				const uint32_t first = (uint32_t)H.size();
 				H.insert(H.end(), r.hits + rr.first, r.hits + rr.first + rr.n);
+				if (idn) chunk_ident[k].insert(chunk_ident[k].end(), idn + rr.first, idn + rr.first + rr.n);
 				rr.first = first;                                    // chunk-local for now
 				m->reads[i] = rr;
 			}
@@ -2062,10 +2068,11 @@ extern "C" int dsb_multi_classify_batch(dsb_multi *m, const dsb_read *reads, siz
 		const uint32_t base = (uint32_t)m->hits.size();
 		for (uint64_t i = plan[k].start; i < plan[k].end; i++) m->reads[i].first += base;
 		m->hits.insert(m->hits.end(), chunk_hits[k].begin(), chunk_hits[k].end());
+		m->ident.insert(m->ident.end(), chunk_ident[k].begin(), chunk_ident[k].end());
 	}
 	for (size_t i = 0; i < n; i++) if (len[i] > m->hist) m->hist = len[i];
 	out->reads = m->reads.data(); out->hits = m->hits.data(); out->n_hits = m->hits.size();
-	m->taxa_ok = m->tx != nullptr; m->lca_ok = m->lca_on;
+	m->taxa_ok = m->tx != nullptr; m->lca_ok = m->lca_on; m->ident_ok = m->ident_on;
 	return worst;
 }
 #endif  // DSB_UNIT_HOST

@@ -1,0 +1,28 @@
+// Per-hit edit distance and per-reference identity (dsb_ctx_enable_identity): the state a context keeps for it and the
+// seam with the other run reductions (dsb_reductions.hip calls the three functions below from reductions_run, reductions_fetch and
+// reductions_release).  The kernels and the host side are in dsb_identity.hip.  Internal: the public surface is include/desamba_amd.h.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <vector>
+#include "../../include/desamba_amd.h"
+
+// On exactly when d_tab is set.  d_rec: one record per entry of the hit buffer (grown with it); d_list: the batch's work list, {hit,
+// read} per counted record; d_cnt: [0] listed records, [1] the work counter of k_hit_edits; d_arena: two generations of furthest-
+// reaching points per wavefront of k_hit_edits' grid (stride ints each); d_tab: the run's table, one dsb_ref_identity per reference.
+struct DsbIdent {
+	dsb_hit_identity *d_rec = nullptr; size_t cap_rec = 0;
+	uint2 *d_list = nullptr; size_t cap_list = 0;
+	unsigned int *d_cnt = nullptr;
+	int *d_arena = nullptr; uint32_t stride = 0, n_waves = 0;
+	dsb_ref_identity *d_tab = nullptr;
+	uint32_t band = 0, permille = 0;
+	std::vector<dsb_hit_identity> h_rec;
+	bool run = false, done = false;               // as DsbTaxa's
+};
+
+struct dsb_ctx;
+struct DsbBatchView;
+int identity_run(dsb_ctx *c, const DsbBatchView &b);         // the three launches of a batch, on b.st
+int identity_fetch_queue(dsb_ctx *c, size_t n_hits);         // queues the copy of the batch's records on c's stream (the caller waits)
+void identity_release(dsb_ctx *c);

@@ -1,0 +1,397 @@
+// Per-hit edit distance and per-reference identity (dsb_identity.h): the banded alignment of every counted record of a
+// batch, one wavefront per record, after the batch's last classify launch; the run's per-reference table; the bare-pair entry
+// dsb_ctx_edit_pairs, which runs the same device function on sequences of the caller's.
+//
+// The alignment is the diagonal-transition form of the banded unit-cost problem.  Diagonal k holds the cells (i, i + k), i bases of Q
+// against i + k bases of T; FR_e[k] is the largest i on diagonal k that e edits reach.  The band is a set of whole diagonals
+// [lo, hi] = [min(0, d) - B, max(0, d) + B] (d = m - n), so the recurrence over the diagonals of the band computes exactly the value
+// of the banded DP: FR_e[k] = max(FR_{e-1}[k] + 1 (mismatch), FR_{e-1}[k - 1] (a base of T alone), FR_{e-1}[k + 1] + 1 (a base of Q
+// alone)) over the candidates that lie in the rectangle, then the slide along the diagonal while Q[i] == T[i + k].  The distance is
+// the first e with FR_e[d] >= n.
+#include <algorithm>
+#include "dsb_ctx.h"
+#include "dsb_sam_fields.h"
+#include "dsb_wave.h"
+
+#define IDENT_NEG (-0x40000000)                        // a diagonal no path has reached
+#define IDENT_BAD (DSB_IDENT_EMPTY | DSB_IDENT_SKEW | DSB_IDENT_OVER)
+#define IDENT_MAX_LEN 0x40000000u                      // dsb_ctx_edit_pairs: longest sequence (the furthest-reaching points are ints)
+#define IDENT_MAX_OFF (1ull << 40)                     // dsb_ctx_edit_pairs: furthest start of a pair in its blob
+#define IDENT_T_PAD 16                                 // bytes behind a packed text that a 32-base fetch may read (refbin has 4 KiB)
+
+// Q: packed words, 32 bases each, the first in the top bits, base qbase of them the first of Q (a read strand of d_pk, or a blob of
+// dsb_ctx_edit_pairs; one pad word behind).  T: packed bytes, 4 bases each, the first in the top bits, base tbase the first of T.
+struct IdentSeq { const uint64_t *qw; uint64_t qbase; const uint8_t *tb; uint64_t tbase; uint32_t n, m; };
+
+// 32 bases from base a on, the first in the top bits: two words funnel-shifted to the phase / nine bytes, byte-swapped, likewise
+DV uint64_t ident_q32(const uint64_t *qw, uint64_t a)
+{
+	const uint64_t w = a >> 5; const uint32_t sh = (uint32_t)(a & 31u) * 2u;
+	const uint64_t x = DSB_G64(qw, w), y = DSB_G64(qw, w + 1);
+	return sh ? (x << sh) | (y >> (64u - sh)) : x;
+}
+DV uint64_t ident_t32(const uint8_t *tb, uint64_t a)
+{
+	const uint8_t *p = tb + (a >> 2); const uint32_t sh = (uint32_t)(a & 3u) * 2u;
+	const uint64_t x = __builtin_bswap64(dsb_g64u(p)); const uint32_t y = p[8];
+	return sh ? (x << sh) | (uint64_t)(y >> (8u - sh)) : x;
+}
+
+// from cell (i, i + k): the first i' >= i with Q[i'] != T[i' + k], or where the rectangle ends.  32 bases per step; what a fetch
+// reads beyond n or m (the next bases, the pads) never counts: every step is clipped to the room left.
+DV int ident_slide(const IdentSeq &s, int i, int k)
+{
+	int j = i + k;
+	while (i < (int)s.n && j < (int)s.m) {
+		const uint64_t d = ident_q32(s.qw, s.qbase + (uint64_t)i) ^ ident_t32(s.tb, s.tbase + (uint64_t)j);
+		int eq = d ? (__builtin_clzll(d) >> 1) : 32;
+		const int room = min((int)s.n - i, (int)s.m - j);
+		if (eq > room) eq = room;
+		i += eq; j += eq;
+		if (eq < 32) break;
+	}
+	return i;
+}
+
+// One wavefront, one pair (all 64 lanes, wave-uniform arguments).  fr: two generations of half ints each, entry k - lo + 1 for
+// diagonal k with an unreached entry on either side of the band; both start unreached, and generation e writes the diagonals
+// [max(lo, -e), min(hi, e)], a superset of what generation e - 2 wrote into the same half.  Lane l takes diagonals klo + l + 64 r.
+// The loops are bounded by E_cap (edits), the band width (rounds) and n, m (slides).
+DV dsb_hit_identity ident_wave(const IdentSeq &s, uint32_t band, uint32_t permille, int *fr, uint32_t half, int lane)
+{
+	dsb_hit_identity o; o.edits = 0; o.q_len = s.n; o.t_len = s.m; o.flags = 0;
+	const int n = (int)s.n, m = (int)s.m, delta = m - n;
+	if (!n || !m) { o.flags = DSB_IDENT_EMPTY; return o; }
+	if (delta > DSB_IDENT_MAX_SKEW || delta < -DSB_IDENT_MAX_SKEW) { o.flags = DSB_IDENT_SKEW; return o; }
+	const int lo = (delta < 0 ? delta : 0) - (int)band, hi = (delta > 0 ? delta : 0) + (int)band, W = hi - lo + 1;
+	const uint32_t ecap = (uint32_t)((uint64_t)(n > m ? n : m) * permille / 1000u);
+	int *prev = fr, *cur = fr + half;
+	for (int x = lane; x < W + 2; x += DSB_WAVE) { prev[x] = IDENT_NEG; cur[x] = IDENT_NEG; }
+	wave_sync();
+	int v0 = IDENT_NEG;
+	if (lane == 0) { v0 = ident_slide(s, 0, 0); prev[1 - lo] = v0; }
+	bool hit = dsb_ballot64(lane == 0 && delta == 0 && v0 >= n) != 0;
+	uint32_t e = 0;
+	while (!hit && e < ecap) {
+		e++;
+		wave_sync();
+		const int klo = lo > -(int)e ? lo : -(int)e, khi = hi < (int)e ? hi : (int)e;
+		bool mine = false;
+		for (int k0 = klo; k0 <= khi; k0 += DSB_WAVE) {
+			const int k = k0 + lane;
+			if (k <= khi) {
+				const int x = k - lo + 1;
+				const int p = prev[x], pl = prev[x - 1], pr = prev[x + 1];
+				int c = p;
+				if (p >= 0 && p + 1 <= n && p + 1 + k <= m) c = p + 1;
+				if (pl >= 0 && pl + k <= m && pl > c) c = pl;
+				if (pr >= 0 && pr + 1 <= n && pr + 1 > c) c = pr + 1;
+				if (c >= 0) c = ident_slide(s, c, k);
+				cur[x] = c;
+				if (k == delta && c >= n) mine = true;
+			}
+		}
+		hit = dsb_ballot64(mine) != 0;
+		int *t = prev; prev = cur; cur = t;
+	}
+	if (hit) { o.edits = e; if (e <= band) o.flags = DSB_IDENT_EXACT; }
+	else { o.edits = ecap + 1; o.flags = DSB_IDENT_OVER; }
+	return o;
+}
+
+// The next entry of a work list for this wavefront: one atomic by lane 0, that lane's value read by all (dsb_shfl, in wave-uniform
+// control flow; dsb_wave.h keeps DSB_RFL for values every lane holds).  The loops that call this keep their control flow wave-uniform
+// from end to start as well: the record is stored by every lane (the same 16 bytes), not under a second lane test.
+DV uint32_t ident_take(unsigned int *work, int lane)
+{
+	uint32_t w = 0;
+	if (lane == 0) w = atomicAdd(work, 1u);
+	return dsb_shfl(w, 0);
+}
+
+// One lane per read, after the batch's last classify work: the records dsb_ref_coverage counts (dsb_sam_counted, among the hits
+// dsb_batch_fetch hands out) go into the work list as {hit, read}, in any order -- each record's result depends on itself alone.
+__global__ void __launch_bounds__(256) k_ident_list(const DsbReadOut *__restrict__ rout, const DsbHitOut *__restrict__ hout, const DsbCounters *__restrict__ counters,
+                                                    uint32_t cap_hout, uint32_t n, uint2 *__restrict__ list, unsigned int *cnt)
+{
+	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= n) return;
+	const uint32_t nh = dsb_hits_out(counters->hits, cap_hout);
+	const DsbReadOut r = rout[i];
+	const uint32_t nrec = dsb_hits_cut(r.first, r.n, nh) ? 0u : r.n;
+	const dsb_hit *h = reinterpret_cast<const dsb_hit *>(hout + r.first);
+	for (uint32_t k = 0; k < nrec; k++)
+		if (dsb_sam_counted(h + k, k)) { uint2 w; w.x = r.first + k; w.y = i; list[atomicAdd(cnt, 1u)] = w; }
+}
+
+// One wavefront per listed record, taken from the list by a work counter (cnt[1]) until it is empty.  The grid is as many wavefronts
+// as the arena has places for: wavefront w owns arena[w * stride .. + stride).
+__global__ void __launch_bounds__(256) k_hit_edits(const DsbHitOut *__restrict__ hout, const DsbReadDesc *__restrict__ rd, const uint64_t *__restrict__ pk,
+                                                   const uint8_t *__restrict__ refbin, const DsbRefInfo *__restrict__ refinfo, uint32_t n_ref,
+                                                   const uint2 *__restrict__ list, unsigned int *cnt, uint32_t band, uint32_t permille, int *arena, uint32_t stride,
+                                                   dsb_hit_identity *__restrict__ rec)
+{
+	const int lane = (int)(threadIdx.x & 63u);
+	int *fr = arena + (size_t)(blockIdx.x * 4u + (threadIdx.x >> 6)) * stride;
+	const uint32_t total = cnt[0];
+	for (;;) {
+		const uint32_t w = ident_take(cnt + 1, lane);
+		if (w >= total) break;
+		const uint2 it = list[w];
+		const DsbHitOut h = hout[it.x];
+		const DsbReadDesc d = rd[it.y];
+		uint64_t ln = 0, off = 0;
+		if (h.ref_ID < n_ref) { const DsbRefInfo ri = refinfo[h.ref_ID]; ln = ri.seq_l; off = ri.seq_offset; }
+		const uint32_t qs = h.q_st < d.len ? h.q_st : d.len, qe = h.q_ed < d.len ? h.q_ed : d.len;
+		const uint64_t ts = h.t_st < ln ? h.t_st : ln, te = h.t_ed < ln ? h.t_ed : ln;
+		IdentSeq s;
+		s.qw = pk + d.pk_off + (h.direction ? 0u : (d.len + 31u) / 32u + 1u); s.qbase = qs; s.n = qe > qs ? qe - qs : 0u;
+		s.tb = refbin; s.tbase = off + ts; s.m = te > ts ? (uint32_t)(te - ts) : 0u;
+		const dsb_hit_identity o = ident_wave(s, band, permille, fr, stride / 2u, lane);
+		rec[it.x] = o;                                          // (all lanes, the same value: ident_take)
+	}
+}
+
+// The batch's records into the run's table, behind k_hit_edits on the same stream: one lane per listed record, equal ref_IDs grouped
+// inside the wavefront first (as k_lca_count groups taxids), the first lane of a group adding the group's sums.  Integer adds only.
+__global__ void __launch_bounds__(256) k_ident_ref(const DsbHitOut *__restrict__ hout, const uint2 *__restrict__ list, const unsigned int *__restrict__ cnt,
+                                                   const dsb_hit_identity *__restrict__ rec, uint32_t n_ref, dsb_ref_identity *tab)
+{
+	const uint32_t lane = threadIdx.x & 63u, total = cnt[0];
+	for (uint32_t base = (blockIdx.x * 4u + (threadIdx.x >> 6)) * 64u; base < total; base += gridDim.x * 256u) {
+		const uint32_t i = base + lane;
+		bool live = i < total;
+		uint32_t ref = 0xffffffffu, v[6] = {0, 0, 0, 0, 0, 0};
+		if (live) {
+			const uint32_t hit = list[i].x;
+			ref = hout[hit].ref_ID;
+			const dsb_hit_identity r = rec[hit];
+			const bool bad = (r.flags & IDENT_BAD) != 0;
+			v[0] = bad ? 0u : 1u; v[1] = bad ? 0u : r.q_len; v[2] = bad ? 0u : r.t_len; v[3] = bad ? 0u : r.edits;
+			v[4] = (!bad && (r.flags & DSB_IDENT_EXACT)) ? 1u : 0u; v[5] = bad ? 1u : 0u;
+			live = ref < n_ref;
+		}
+		uint64_t left = dsb_ballot64(live);
+		while (left) {
+			const int src = __builtin_ctzll(left);
+			const uint32_t t = dsb_shfl(ref, src);
+			const uint64_t grp = dsb_ballot64(live && ref == t);
+			unsigned long long sum[6] = {0, 0, 0, 0, 0, 0};
+			for (uint64_t g = grp; g; g &= g - 1) {
+				const int l = __builtin_ctzll(g);
+				for (int f = 0; f < 6; f++) sum[f] += dsb_shfl(v[f], l);
+			}
+			if ((int)lane == src) {
+				unsigned long long *o = reinterpret_cast<unsigned long long *>(tab + t);
+				for (int f = 0; f < 6; f++) if (sum[f]) atomicAdd(o + f, sum[f]);
+			}
+			left &= ~grp;
+		}
+	}
+}
+
+// ---- dsb_ctx_edit_pairs: the caller's codes packed as reads and reference text are, then ident_wave per pair ----
+__global__ void __launch_bounds__(256) k_ident_pack_q(const uint8_t *__restrict__ codes, uint64_t n_bases, uint64_t *__restrict__ words, uint64_t n_words)
+{
+	const uint64_t w = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	if (w >= n_words) return;
+	uint64_t v = 0;
+	for (uint32_t b = 0; b < 32; b++) { const uint64_t p = w * 32 + b; v = (v << 2) | (p < n_bases ? codes[p] & 3u : 0u); }
+	words[w] = v;
+}
+__global__ void __launch_bounds__(256) k_ident_pack_t(const uint8_t *__restrict__ codes, uint64_t n_bases, uint8_t *__restrict__ bytes, uint64_t n_bytes)
+{
+	const uint64_t w = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	if (w >= n_bytes) return;
+	uint32_t v = 0;
+	for (uint32_t b = 0; b < 4; b++) { const uint64_t p = w * 4 + b; v = (v << 2) | (p < n_bases ? codes[p] & 3u : 0u); }
+	bytes[w] = (uint8_t)v;
+}
+__global__ void __launch_bounds__(256) k_pair_edits(const uint64_t *__restrict__ qw, const uint8_t *__restrict__ tb, const uint64_t *__restrict__ q_off,
+                                                    const uint32_t *__restrict__ q_len, const uint64_t *__restrict__ t_off, const uint32_t *__restrict__ t_len,
+                                                    uint32_t n_pairs, unsigned int *work, uint32_t band, uint32_t permille, int *arena, uint32_t stride,
+                                                    dsb_hit_identity *__restrict__ out)
+{
+	const int lane = (int)(threadIdx.x & 63u);
+	int *fr = arena + (size_t)(blockIdx.x * 4u + (threadIdx.x >> 6)) * stride;
+	for (;;) {
+		const uint32_t w = ident_take(work, lane);
+		if (w >= n_pairs) break;
+		IdentSeq s;
+		s.qw = qw; s.qbase = q_off[w]; s.n = q_len[w]; s.tb = tb; s.tbase = t_off[w]; s.m = t_len[w];
+		const dsb_hit_identity o = ident_wave(s, band, permille, fr, stride / 2u, lane);
+		out[w] = o;                                             // (all lanes, the same value: ident_take)
+	}
+}
+
+// ================================== host side ====================================================
+// ints of a wavefront's arena place: two generations of the widest band (|d| <= DSB_IDENT_MAX_SKEW) with its two unreached ends
+static uint32_t ident_stride(uint32_t band) { return 2u * (DSB_IDENT_MAX_SKEW + 2u * band + 3u); }
+// wavefronts of the grid: eight per compute unit (the kernel waits on dependent loads; 8 x 36 KiB of arena per CU stay in L2)
+static int ident_waves(int device, uint32_t *n_waves)
+{
+	int cus = 0;
+	HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+	*n_waves = (uint32_t)(cus > 0 ? cus : 1) * 8u;
+	return DSB_OK;
+}
+
+void identity_release(dsb_ctx *c)
+{
+	hipFree(c->ident.d_rec); hipFree(c->ident.d_list); hipFree(c->ident.d_cnt); hipFree(c->ident.d_arena); hipFree(c->ident.d_tab);
+	c->ident = DsbIdent();
+}
+
+extern "C" int dsb_ctx_reset_identity(dsb_ctx *c)
+{
+	if (!c || !c->ident.d_tab) return DSB_EINVAL;
+	HIPCHK(hipSetDevice(c->device));
+	HIPCHK(hipMemsetAsync(c->ident.d_tab, 0, (size_t)dsb_index_n_ref(c->idx) * sizeof(dsb_ref_identity) + 8, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	return DSB_OK;
+}
+
+extern "C" int dsb_ctx_enable_identity(dsb_ctx *c, int on, uint32_t band, uint32_t max_permille)
+{
+	if (!c) return DSB_EINVAL;
+	if (on && band == 0 && max_permille == 0) { band = DSB_IDENT_BAND_DEFAULT; max_permille = DSB_IDENT_PERMILLE_DEFAULT; }
+	if (on && (band > DSB_IDENT_MAX_BAND || max_permille < 1 || max_permille > 1000)) return DSB_EINVAL;
+	HIPCHK(hipSetDevice(c->device));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	if (on && c->ident.d_tab && c->ident.band == band) { c->ident.permille = max_permille; return dsb_ctx_reset_identity(c); }
+	identity_release(c);
+	if (!on) return DSB_OK;
+	DsbIdent &d = c->ident;
+	if (int rc = ident_waves(c->device, &d.n_waves)) return rc;
+	d.stride = ident_stride(band);
+	const size_t n_ref = (size_t)dsb_index_n_ref(c->idx);
+	if (hipMalloc((void **)&d.d_tab, n_ref * sizeof(dsb_ref_identity) + 8) != hipSuccess || hipMalloc((void **)&d.d_cnt, 2 * sizeof(unsigned int)) != hipSuccess ||
+	    hipMalloc((void **)&d.d_arena, (size_t)d.n_waves * d.stride * sizeof(int)) != hipSuccess ||
+	    grow(&d.d_rec, &d.cap_rec, c->cap_hout) || grow(&d.d_list, &d.cap_list, c->cap_hout)) {
+		identity_release(c); (void)hipGetLastError(); return DSB_ENOMEM;
+	}
+	d.band = band; d.permille = max_permille;
+	return dsb_ctx_reset_identity(c);
+}
+
+int identity_run(dsb_ctx *c, const DsbBatchView &b)
+{
+	DsbIdent &d = c->ident;
+	// one record and one list entry per place of the hit buffer (it may have been regrown by this batch)
+	if (grow(&d.d_rec, &d.cap_rec, b.cap_hout) || grow(&d.d_list, &d.cap_list, b.cap_hout)) return DSB_ENOMEM;
+	HIPCHK(hipMemsetAsync(d.d_rec, 0, b.cap_hout * sizeof(dsb_hit_identity), b.st));
+	HIPCHK(hipMemsetAsync(d.d_cnt, 0, 2 * sizeof(unsigned int), b.st));
+	hipLaunchKernelGGL(k_ident_list, dim3((b.n + 255) / 256), dim3(256), 0, b.st, b.rout, b.hout, b.counters, (uint32_t)b.cap_hout, b.n, d.d_list, d.d_cnt);
+	hipLaunchKernelGGL(k_hit_edits, dim3(d.n_waves / 4), dim3(256), 0, b.st, b.hout, b.rd, b.pk, c->dx.refbin, c->dx.refinfo, (uint32_t)dsb_index_n_ref(c->idx),
+	                   (const uint2 *)d.d_list, d.d_cnt, d.band, d.permille, d.d_arena, d.stride, d.d_rec);
+	const size_t ref_blocks = std::min<size_t>((b.cap_hout + 255) / 256, 1024);
+	hipLaunchKernelGGL(k_ident_ref, dim3((unsigned)(ref_blocks ? ref_blocks : 1)), dim3(256), 0, b.st, b.hout, (const uint2 *)d.d_list, (const unsigned int *)d.d_cnt,
+	                   (const dsb_hit_identity *)d.d_rec, (uint32_t)dsb_index_n_ref(c->idx), d.d_tab);
+	d.run = true;
+	return DSB_OK;
+}
+
+int identity_fetch_queue(dsb_ctx *c, size_t n_hits)
+{
+	c->ident.h_rec.resize(n_hits);
+	if (n_hits) HIPCHK(hipMemcpyAsync(c->ident.h_rec.data(), c->ident.d_rec, n_hits * sizeof(dsb_hit_identity), hipMemcpyDeviceToHost, c->stream));
+	return DSB_OK;
+}
+
+extern "C" int dsb_batch_identity(dsb_ctx *c, const dsb_hit_identity **out)
+{
+	if (!c || !out || !c->ident.d_tab || !c->ident.run) return DSB_EINVAL;
+	if (!c->ident.done) { dsb_result r; int rc = dsb_batch_fetch(c, &r); if (rc && rc != DSB_ECAP) return rc; }
+	*out = c->ident.h_rec.data();
+	return DSB_OK;
+}
+
+extern "C" int dsb_ctx_identity(dsb_ctx *c, dsb_ref_identity *out)
+{
+	if (!c || !out || !c->ident.d_tab) return DSB_EINVAL;
+	HIPCHK(hipSetDevice(c->device));
+	const size_t n_ref = (size_t)dsb_index_n_ref(c->idx);
+	if (n_ref) HIPCHK(hipMemcpyAsync(out, c->ident.d_tab, n_ref * sizeof(dsb_ref_identity), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	return DSB_OK;
+}
+
+extern "C" int dsb_multi_enable_identity(dsb_multi *m, int on, uint32_t band, uint32_t max_permille)
+{
+	if (!m) return DSB_EINVAL;
+	m->ident_on = m->ident_ok = false;
+	for (dsb_ctx *c : m->ctx) {
+		int rc = dsb_ctx_enable_identity(c, on, band, max_permille);
+		if (rc) { for (dsb_ctx *d : m->ctx) dsb_ctx_enable_identity(d, 0, 0, 0); return rc; }
+	}
+	m->ident_on = on != 0;
+	return DSB_OK;
+}
+
+extern "C" int dsb_multi_identity(dsb_multi *m, const dsb_hit_identity **out)
+{
+	if (!m || !out || !m->ident_on || !m->ident_ok) return DSB_EINVAL;
+	*out = m->ident.data();
+	return DSB_OK;
+}
+
+// the contexts' tables added on the host (48 bytes per reference and context)
+extern "C" int dsb_multi_ref_identity(dsb_multi *m, dsb_ref_identity *out)
+{
+	if (!m || !out || m->ctx.empty()) return DSB_EINVAL;
+	const size_t n_ref = (size_t)dsb_index_n_ref(m->idx);
+	std::vector<dsb_ref_identity> t(n_ref);
+	memset(out, 0, n_ref * sizeof *out);
+	for (dsb_ctx *c : m->ctx) {
+		if (int rc = dsb_ctx_identity(c, t.data())) return rc;
+		for (size_t r = 0; r < n_ref; r++) {
+			out[r].records += t[r].records; out[r].q_bases += t[r].q_bases; out[r].t_bases += t[r].t_bases;
+			out[r].edits += t[r].edits; out[r].exact += t[r].exact; out[r].unaligned += t[r].unaligned;
+		}
+	}
+	return DSB_OK;
+}
+
+extern "C" int dsb_ctx_edit_pairs(dsb_ctx *c, const uint8_t *q_codes, const uint64_t *q_off, const uint32_t *q_len, const uint8_t *t_codes, const uint64_t *t_off,
+                                  const uint32_t *t_len, size_t n_pairs, uint32_t band, uint32_t max_permille, dsb_hit_identity *out)
+{
+	if (!c || band > DSB_IDENT_MAX_BAND || max_permille < 1 || max_permille > 1000 || n_pairs > 0xffffffffu) return DSB_EINVAL;
+	if (!n_pairs) return DSB_OK;
+	if (!q_codes || !q_off || !q_len || !t_codes || !t_off || !t_len || !out) return DSB_EINVAL;
+	uint64_t nq = 0, nt = 0;
+	for (size_t p = 0; p < n_pairs; p++) {
+		if (q_len[p] > IDENT_MAX_LEN || t_len[p] > IDENT_MAX_LEN || q_off[p] > IDENT_MAX_OFF || t_off[p] > IDENT_MAX_OFF) return DSB_EINVAL;   // (the sums below cannot wrap)
+		nq = std::max(nq, q_off[p] + q_len[p]); nt = std::max(nt, t_off[p] + t_len[p]);
+	}
+	HIPCHK(hipSetDevice(c->device));
+	uint32_t n_waves = 0;
+	if (int rc = ident_waves(c->device, &n_waves)) return rc;
+	n_waves = (uint32_t)std::min<size_t>(n_waves, (n_pairs + 3) / 4 * 4);
+	const uint32_t stride = ident_stride(band);
+	const uint64_t n_words = (nq + 31) / 32 + 1, n_bytes = (nt + 3) / 4 + IDENT_T_PAD;
+	struct Bufs { std::vector<void *> p; ~Bufs() { for (void *q : p) hipFree(q); }
+	              void *get(size_t bytes) { void *q = nullptr; if (hipMalloc(&q, bytes ? bytes : 1) != hipSuccess) { (void)hipGetLastError(); return nullptr; } p.push_back(q); return q; } } T;
+	uint8_t *d_qc = (uint8_t *)T.get(nq), *d_tc = (uint8_t *)T.get(nt), *d_tb = (uint8_t *)T.get(n_bytes);
+	uint64_t *d_qw = (uint64_t *)T.get(n_words * 8), *d_qo = (uint64_t *)T.get(n_pairs * 8), *d_to = (uint64_t *)T.get(n_pairs * 8);
+	uint32_t *d_ql = (uint32_t *)T.get(n_pairs * 4), *d_tl = (uint32_t *)T.get(n_pairs * 4);
+	unsigned int *d_work = (unsigned int *)T.get(sizeof(unsigned int));
+	int *d_arena = (int *)T.get((size_t)n_waves * stride * sizeof(int));
+	dsb_hit_identity *d_out = (dsb_hit_identity *)T.get(n_pairs * sizeof(dsb_hit_identity));
+	if (!d_qc || !d_tc || !d_tb || !d_qw || !d_qo || !d_to || !d_ql || !d_tl || !d_work || !d_arena || !d_out) return DSB_ENOMEM;
+	hipStream_t st = c->stream;
+	if (nq) HIPCHK(hipMemcpyAsync(d_qc, q_codes, nq, hipMemcpyHostToDevice, st));
+	if (nt) HIPCHK(hipMemcpyAsync(d_tc, t_codes, nt, hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemcpyAsync(d_qo, q_off, n_pairs * 8, hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemcpyAsync(d_to, t_off, n_pairs * 8, hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemcpyAsync(d_ql, q_len, n_pairs * 4, hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemcpyAsync(d_tl, t_len, n_pairs * 4, hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemsetAsync(d_work, 0, sizeof(unsigned int), st));
+	hipLaunchKernelGGL(k_ident_pack_q, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, st, (const uint8_t *)d_qc, nq, d_qw, n_words);
+	hipLaunchKernelGGL(k_ident_pack_t, dim3((unsigned)((n_bytes + 255) / 256)), dim3(256), 0, st, (const uint8_t *)d_tc, nt, d_tb, n_bytes);
+	hipLaunchKernelGGL(k_pair_edits, dim3(n_waves / 4), dim3(256), 0, st, (const uint64_t *)d_qw, (const uint8_t *)d_tb, (const uint64_t *)d_qo, (const uint32_t *)d_ql,
+	                   (const uint64_t *)d_to, (const uint32_t *)d_tl, (uint32_t)n_pairs, d_work, band, max_permille, d_arena, stride, d_out);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(out, d_out, n_pairs * sizeof(dsb_hit_identity), hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	return DSB_OK;
+}

@@ -352,3 +352,52 @@ extern "C" long dsb_coverage_format(const dsb_index *x, const dsb_ref_coverage *
 #undef EMIT
 	return (long)o;
 }
+
+// ---- per-hit edit distance and per-reference identity: the host mirror of the reference text and the two tables ----
+extern "C" int dsb_index_ref_bases(const dsb_index *x, uint32_t id, uint64_t start, uint32_t len, uint8_t *codes)
+{
+	if (!x || id >= x->h.n_ref || (!codes && len)) return DSB_EINVAL;
+	const DsbHostRefInfoDisk &r = x->h.refdisk[id];
+	if (start > r.seq_l || len > r.seq_l - start) return DSB_EINVAL;
+	for (uint32_t i = 0; i < len; i++) { const uint64_t p = r.seq_offset + start + i; codes[i] = (uint8_t)((x->h.refbin[p >> 2] >> (6 - 2 * (p & 3))) & 3); }
+	return DSB_OK;
+}
+
+#define DSB_IDENT_BAD (DSB_IDENT_EMPTY | DSB_IDENT_SKEW | DSB_IDENT_OVER)
+extern "C" long dsb_format_identity(const dsb_index *x, const dsb_read *rd_, const dsb_read_result *rr, const dsb_hit *h, const dsb_hit_identity *id, char *buf, size_t cap)
+{
+	if (!x || !rd_ || !rr || (rr->n && (!h || !id)) || (!buf && cap)) return -1;
+	size_t o = 0; int w;
+#define EMIT(...) do { w = snprintf(buf + o, cap > o ? cap - o : 0, __VA_ARGS__); if (w < 0 || (size_t)w >= (cap > o ? cap - o : 0)) return -1; o += (size_t)w; } while (0)
+	if (rr->n == 0) { EMIT("%s\t*\t*\t0\t0\t0\t0\t0\t0\t0.0000\t0\n", rd_->name); return (long)o; }
+	for (uint32_t i = 0; i < rr->n; i++) {
+		const dsb_hit *c = h + i;
+		if (!dsb_sam_counted(c, i)) continue;
+		const uint64_t L = rd_->len, LN = dsb_index_ref_len(x, c->ref_ID);
+		const uint64_t qs = c->q_st < L ? c->q_st : L, qe = c->q_ed < L ? c->q_ed : L, ts = c->t_st < LN ? c->t_st : LN, te = c->t_ed < LN ? c->t_ed : LN;
+		const uint32_t big = id[i].q_len > id[i].t_len ? id[i].q_len : id[i].t_len;
+		const double ident = ((id[i].flags & DSB_IDENT_BAD) || !big) ? 0.0 : 1.0 - (double)id[i].edits / (double)big;
+		EMIT("%s\t%s\t%c\t%llu\t%llu\t%llu\t%llu\t%u\t%u\t%.4f\t%u\n", rd_->name, dsb_index_ref_name(x, c->ref_ID), c->direction ? '+' : '-', (unsigned long long)qs,
+		     (unsigned long long)qe, (unsigned long long)ts, (unsigned long long)te, c->sum_score, id[i].edits, ident, id[i].flags);
+	}
+#undef EMIT
+	return (long)o;
+}
+
+extern "C" long dsb_identity_format(const dsb_index *x, const dsb_ref_identity *tab, char *buf, size_t cap)
+{
+	if (!x || !tab || (!buf && cap)) return -1;
+	size_t o = 0; int w;
+#define EMIT(...) do { w = snprintf(buf + o, cap > o ? cap - o : 0, __VA_ARGS__); if (w < 0 || (size_t)w >= (cap > o ? cap - o : 0)) return -1; o += (size_t)w; } while (0)
+	EMIT("#rname\trecords\tq_bases\tt_bases\tedits\tidentity\texact\tunaligned\n");
+	const uint64_t n_ref = dsb_index_n_ref(x);
+	for (uint64_t r = 0; r < n_ref; r++) {
+		const dsb_ref_identity &t = tab[r];
+		if (!(t.records + t.unaligned)) continue;
+		const uint64_t big = t.q_bases > t.t_bases ? t.q_bases : t.t_bases;
+		EMIT("%s\t%llu\t%llu\t%llu\t%llu\t%.4f\t%llu\t%llu\n", dsb_index_ref_name(x, (uint32_t)r), (unsigned long long)t.records, (unsigned long long)t.q_bases,
+		     (unsigned long long)t.t_bases, (unsigned long long)t.edits, big ? 1.0 - (double)t.edits / (double)big : 0.0, (unsigned long long)t.exact, (unsigned long long)t.unaligned);
+	}
+#undef EMIT
+	return (long)o;
+}

@@ -1,6 +1,7 @@
 // The run reductions of classify: per-read taxa (dsb_ctx_set_taxonomy), per-reference and per-window coverage (dsb_ctx_enable_coverage,
 // dsb_ctx_enable_coverage_windows), per-reference abundance by EM (dsb_ctx_enable_abundance) and per-read LCA classification
-// (dsb_ctx_enable_lca).  Each reads a batch's hit buffer
+// (dsb_ctx_enable_lca); per-hit edit distance and per-reference identity (dsb_ctx_enable_identity) keeps its state
+// and kernels in dsb_identity.h / dsb_identity.hip and is driven through the same seam.  Each reads a batch's hit buffer
 // after its last classify launch, keeps state for the whole run and is merged across the contexts of a dsb_multi
 // (dsb_reductions.hip).  Internal: the public surface is include/desamba_amd.h.
 #pragma once
@@ -9,6 +10,7 @@
 #include <vector>
 #include "../../include/desamba_amd.h"
 #include "dsb_device.h"
+#include "dsb_identity.h"
 
 struct DsbEmSet;
 
@@ -55,6 +57,7 @@ struct DsbBatchView {
 	hipStream_t st;
 	const DsbReadOut *rout; const DsbHitOut *hout; const DsbCounters *counters; size_t cap_hout;
 	const DsbReadDesc *rd; uint32_t n;
+	const uint64_t *pk;                           // both packed strands of every read (k_encode_pack), at rd[i].pk_off
 	bool ord_set; uint64_t ord_first;             // dsb_ctx_set_batch_ordinal was called for this batch / with this ordinal
 };
 

@@ -1273,6 +1273,7 @@ int reductions_run(dsb_ctx *c, const DsbBatchView &b)
 		hipLaunchKernelGGL(k_lca_count, dim3((b.n + 255) / 256), dim3(256), 0, b.st, (const dsb_read_lca *)c->lca.d_rec, b.n, tx->max_tid, c->lca.d_direct, c->lca.d_sum);
 		c->lca.run = true;
 	}
+	if (c->ident.d_tab) return identity_run(c, b);             // per-hit edit distance and the per-reference identity table (dsb_identity.hip)
 	return DSB_OK;
 }
 
@@ -1282,8 +1283,10 @@ int reductions_fetch(dsb_ctx *c, size_t n, bool queued)
 	if (c->taxa.run) { c->taxa.h_taxa.resize(n); if (n) HIPCHK(hipMemcpyAsync(c->taxa.h_taxa.data(), c->taxa.d_taxa, n * sizeof(dsb_read_taxon), hipMemcpyDeviceToHost, c->stream)); }
 	c->lca.done = false;
 	if (c->lca.run) { c->lca.h_rec.resize(n); if (n) HIPCHK(hipMemcpyAsync(c->lca.h_rec.data(), c->lca.d_rec, n * sizeof(dsb_read_lca), hipMemcpyDeviceToHost, c->stream)); }
+	c->ident.done = false;
+	if (c->ident.run) { if (int rc = identity_fetch_queue(c, c->h_hout.size())) return rc; }    // (queued is set whenever the batch has hits)
 	if (queued || ((c->taxa.run || c->lca.run) && n)) HIPCHK(hipStreamSynchronize(c->stream));
-	c->lca.done = c->lca.run;
+	c->lca.done = c->lca.run; c->ident.done = c->ident.run;
 	if (!c->taxa.run) return DSB_OK;
 	// the reads the device left to the host get their taxon here (rare: see k_read_taxon)
 	const dsb_hit *H = reinterpret_cast<const dsb_hit *>(c->h_hout.data());
@@ -1297,7 +1300,7 @@ int reductions_fetch(dsb_ctx *c, size_t n, bool queued)
 
 void reductions_release(dsb_ctx *c)
 {
-	hipFree(c->taxa.d_parent); hipFree(c->taxa.d_ref_tid); hipFree(c->taxa.d_taxa); cover_free(c); em_free(c); lca_free(c);
+	hipFree(c->taxa.d_parent); hipFree(c->taxa.d_ref_tid); hipFree(c->taxa.d_taxa); cover_free(c); em_free(c); lca_free(c); identity_release(c);
 }
 
 // ---- several contexts (dsb_multi) ----

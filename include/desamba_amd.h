@@ -448,6 +448,69 @@ long dsb_format_kraken(const dsb_read *read, const dsb_read_lca *lca, char *buf,
 long dsb_lca_report_format(const dsb_taxonomy *tx, const dsb_taxnames *names, const dsb_taxon_count *rows, size_t n,
                            const dsb_lca_summary *summary, char *buf, size_t cap);
 
+/* ---- per-hit edit distance and per-reference identity, by banded alignment on the GPU.
+ * Counted are the records of dsb_ref_coverage: record i of a read with i == 0 or pri_index == 0, among the hits dsb_batch_fetch hands
+ * out; every other hit gets an all-zero record.  With L the read length and LN = dsb_index_ref_len(ref_ID) (0 for ref_ID >= n_ref):
+ * qs = min(q_st, L), qe = min(q_ed, L), ts = min(t_st, LN), te = min(t_ed, LN), n = qe - qs, m = te - ts (0 when the end is not above
+ * the start).  Q = bases [qs, qe) of the strand the chain was built on (direction 1: the read as given; 0: its reverse complement;
+ * q_st and q_ed count on that strand), T = bases [ts, te) of the reference.  n == 0 or m == 0: DSB_IDENT_EMPTY.  d = m - n,
+ * |d| > DSB_IDENT_MAX_SKEW: DSB_IDENT_SKEW.  Else edits = the unit-cost global edit distance (mismatches and indels) of Q and T over
+ * the cells (i, j) with min(0, d) - band <= j - i <= max(0, d) + band: never below the unbanded distance, and equal to it when
+ * edits <= band (DSB_IDENT_EXACT).  E_cap = floor(max(n, m) * max_permille / 1000): a distance above it is reported as E_cap + 1
+ * with DSB_IDENT_OVER, and the search stops there.  EMPTY and SKEW records have edits 0.  The identity of a record is
+ * 1 - edits / max(n, m), and 0 for an EMPTY, SKEW or OVER record.
+ * The intervals are taken as the hit gives them, and the hit's two starts are not always a matched pair: where an end of the chain
+ * is still its first or last anchor's (map_seed: index_in_read = read_offset + 1 - left extension with the reference's read_offset =
+ * k_idx + l_ek - 1 - match_len; chain_insert_meta copies it), q lies one base below the base that t_st matched, and only an end the
+ * left or right extension moved (sdp_left / sdp_right set q_st, t_st from a match node) is a matched pair.  A hit does not say which
+ * kind its ends are.  Seen on reads that match over their whole length: q_st 0 with t_st one above the read's 0-based start, 2 edits
+ * (one base alone at either end) where there are none.  So edits may be high by up to 2, identity low by up to 2 / max(n, m). */
+typedef struct { uint32_t edits, q_len /* n */, t_len /* m */, flags; } dsb_hit_identity;
+#define DSB_IDENT_EXACT 1      /* edits <= band: the band did not matter */
+#define DSB_IDENT_OVER  2      /* more than E_cap edits: edits = E_cap + 1 */
+#define DSB_IDENT_SKEW  4      /* |m - n| > DSB_IDENT_MAX_SKEW: not aligned */
+#define DSB_IDENT_EMPTY 8      /* n == 0, m == 0 or ref_ID >= n_ref: not aligned */
+#define DSB_IDENT_MAX_SKEW 4096
+#define DSB_IDENT_MAX_BAND 1024
+#define DSB_IDENT_BAND_DEFAULT 256
+#define DSB_IDENT_PERMILLE_DEFAULT 300
+/* per reference, everything since enable / reset: integer sums that do not depend on batch split, input slot, context or run.
+ * records, q_bases, t_bases, edits and exact count the records without EMPTY, SKEW and OVER; unaligned those with one of the three
+ * (a record with ref_ID >= n_ref belongs to no reference and is counted nowhere). */
+typedef struct { uint64_t records, q_bases, t_bases, edits, exact, unaligned; } dsb_ref_identity;
+/* on: every batch from now on ends with k_ident_list, k_hit_edits and k_ident_ref (16 bytes per hit of the hit buffer, 48 bytes per
+ * reference, and the wavefronts' diagonal arena: 8 bytes x (DSB_IDENT_MAX_SKEW + 2 band + 3) each).  band 0 .. DSB_IDENT_MAX_BAND and
+ * max_permille 1 .. 1000, else DSB_EINVAL; band == 0 && max_permille == 0: the defaults (a band of 0 is asked for with its cap
+ * spelled out, e.g. 0, 300).  On again: new options, table zeroed.  off: freed; nothing is allocated or launched while off. */
+int  dsb_ctx_enable_identity(dsb_ctx *ctx, int on, uint32_t band, uint32_t max_permille);
+int  dsb_ctx_reset_identity(dsb_ctx *ctx);                               /* zero the table, keep the allocation */
+/* the records of the last batch, one per hit of dsb_batch_fetch's hits (n_hits entries), valid until the next batch */
+int  dsb_batch_identity(dsb_ctx *ctx, const dsb_hit_identity **out);
+int  dsb_ctx_identity(dsb_ctx *ctx, dsb_ref_identity *out);              /* dsb_index_n_ref entries since enable / reset */
+int  dsb_multi_enable_identity(dsb_multi *m, int on, uint32_t band, uint32_t max_permille);
+int  dsb_multi_identity(dsb_multi *m, const dsb_hit_identity **out);     /* the last dsb_multi_classify_batch: one per hit of its result */
+int  dsb_multi_ref_identity(dsb_multi *m, dsb_ref_identity *out);        /* the contexts' tables added */
+/* one line per counted record of a read, in record order (hits and ident: the read's own, rr->n of each):
+ * QNAME \t rname \t +|- \t qs \t qe \t ts \t te \t AS \t edits \t identity (%.4f) \t flags (decimal) \n; a read without hits:
+ * QNAME \t * \t * \t 0 \t 0 \t 0 \t 0 \t 0 \t 0 \t 0.0000 \t 0 \n.  Return as dsb_format_sam. */
+long dsb_format_identity(const dsb_index *idx, const dsb_read *read, const dsb_read_result *rr, const dsb_hit *hits, const dsb_hit_identity *ident,
+                         char *buf, size_t cap);
+/* "#rname records q_bases t_bases edits identity exact unaligned" (tabs), then one row per reference with records + unaligned > 0 in
+ * ref_ID order; identity = 1 - edits / max(q_bases, t_bases) as %.4f (0.0000 without bases).  Return as dsb_format_sam. */
+long dsb_identity_format(const dsb_index *idx, const dsb_ref_identity *tab, char *buf, size_t cap);
+/* host mirror of the 2-bit reference text: codes[i] = base start + i of reference ref_ID (0 A, 1 C, 2 G, 3 T; the index holds
+ * every other letter of the FASTA as A, where a read's other letters count as C), len codes;
+ * DSB_EINVAL for a reference the index does not have or a window that reaches beyond its length */
+int  dsb_index_ref_bases(const dsb_index *idx, uint32_t ref_ID, uint64_t start, uint32_t len, uint8_t *codes);
+/* n_pairs bare alignments by the device function of k_hit_edits: Q of pair p = q_codes[q_off[p] .. + q_len[p]), T likewise, one code
+ * (0 .. 3) per byte.  The two blobs are packed on the device as reads and reference text are laid out (32 bases per 64-bit word and 4
+ * per byte, first base in the top bits), base b of a blob at base b of its packed form: a pair starts at word phase q_off & 31 and
+ * byte phase t_off & 3.  band 0 .. DSB_IDENT_MAX_BAND, max_permille 1 .. 1000, a length up to 2^30 and an offset up to 2^40, else DSB_EINVAL
+ * (no defaults here).  out: n_pairs records. */
+int  dsb_ctx_edit_pairs(dsb_ctx *ctx, const uint8_t *q_codes, const uint64_t *q_off, const uint32_t *q_len,
+                        const uint8_t *t_codes, const uint64_t *t_off, const uint32_t *t_len, size_t n_pairs,
+                        uint32_t band, uint32_t max_permille, dsb_hit_identity *out);
+
 const char *dsb_strerror(int code);
 const char *dsb_version(void);
 
