@@ -376,6 +376,7 @@ class Ctx:
         if rc != 0:
             raise DsbError(rc, "dsb_ctx_use_synthetic_filter")
         self.synthetic = (table_bytes, fill)
+        self.synthetic_k = {27: 16, 28: 17, 29: 17, 30: 18, 31: 18, 32: 19, 33: 19, 34: 20}[int(table_bytes).bit_length() - 1]
 
     def select_slot(self, slot):
         rc = lib().dsb_ctx_select_slot(self.h, slot)
@@ -430,8 +431,19 @@ class Ctx:
         lib().dsb_batch_timing(self.h, C.byref(t))
         return t
 
+    def read_len(self, read):
+        """length of a read of the staged batch, whichever way it was uploaded (the library knows: windows + k - 1; 0 for a read
+        shorter than 40 bases, which has no windows)"""
+        reads = self.staged.get(self.slot, (self.reads, 0))[0] or self.reads
+        if reads is not None:
+            return reads[read].len
+        n = C.c_uint32()
+        lib().dsb_batch_exist_bits(self.h, read, 1, None, 0, C.byref(n))      # (too small a buffer: only the number of windows comes back)
+        k = self.synthetic_k if getattr(self, "synthetic", None) else self.index.ek_len
+        return n.value + k - 1 if n.value else 0
+
     def seeds(self, read, strand):
-        cap = (self.reads[read].len >> 1) + 64
+        cap = (self.read_len(read) >> 1) + 64
         buf = (DsbSeed * cap)(); n = C.c_uint32(); ts = C.c_uint32()
         rc = lib().dsb_batch_seeds(self.h, read, strand, buf, cap, C.byref(n), C.byref(ts))
         if rc != 0:
@@ -439,8 +451,10 @@ class Ctx:
         return [(buf[i].offset, buf[i].len, buf[i].top) for i in range(n.value)], ts.value
 
     def exist_bits(self, read, strand):
-        cap = self.reads[read].len + 1
-        buf = (C.c_uint8 * cap)(); n = C.c_uint32()
+        n = C.c_uint32()
+        lib().dsb_batch_exist_bits(self.h, read, strand, None, 0, C.byref(n))        # the number of windows first
+        cap = n.value + 1
+        buf = (C.c_uint8 * cap)()
         rc = lib().dsb_batch_exist_bits(self.h, read, strand, buf, cap, C.byref(n))
         if rc != 0:
             raise DsbError(rc, "dsb_batch_exist_bits")

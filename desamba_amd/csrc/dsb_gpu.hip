@@ -921,7 +921,7 @@ static void knobs_read(DsbKnobs &k)
 	k.scan_look_set = false;
 	if (const char *e = getenv("DSB_SCAN_LOOK")) {
 		int a = 0, b = 0, f = 0, st = 0;
-		if (sscanf(e, "%d,%d,%d,%d", &a, &b, &f, &st) == 4 && a >= 1 && a <= DSB_SCAN_W && b >= 1 && b <= DSB_SCAN_W - 2 && f >= 1 && f <= DSB_SCAN_W && st >= 1 && st <= DSB_SCAN_W) {
+		if (sscanf(e, "%d,%d,%d,%d", &a, &b, &f, &st) == 4 && a >= 1 && a <= DSB_SCAN_W && b >= 0 && b <= DSB_SCAN_W - 2 && f >= 1 && f <= DSB_SCAN_W && st >= 1 && st <= DSB_SCAN_W) {
 			k.scan_look.after_seed = (uint8_t)a; k.scan_look.back_fwd = (uint8_t)b; k.scan_look.fwd_n = (uint8_t)f; k.scan_look.stride_n = (uint8_t)st; k.scan_look_set = true;
 		}
 	}

@@ -200,10 +200,10 @@ static uint32_t search_exist(const ora_idx_t *x, const uint64_t *kv, uint32_t n,
 }
 
 /* get_seed_vector_M2, src/cly.c:1162-1234 */
-static void seed_vector(ora_ctx_t *c, const ora_idx_t *x, uint8_t *bin, uint64_t *kb, uint32_t n, ora_seed_t *sv, uint32_t direction, sdir_t *out)
+/* the scan of the k-mers of one strand and the marking of the top seed of every 100-window bin: get_seed_vector_M2 behind its store_kmers */
+static uint32_t scan_and_mark(const ora_idx_t *x, const uint64_t *kb, uint32_t n, ora_seed_t *sv, uint32_t direction, uint64_t *cnt, uint32_t *total_out)
 {
-	store_kmers(bin, n, x->ek_len, x->single_base_max, kb);
-	uint32_t ns = search_exist(x, kb, n, sv, direction, c->cnt);
+	uint32_t ns = search_exist(x, kb, n, sv, direction, cnt);
 	uint32_t total = 0; int max_index = 0; uint32_t max_length = 0, index_end = 100;
 	for (uint32_t m = 0; m < ns; m++) {
 		sv[m].top = 0;
@@ -218,7 +218,32 @@ static void seed_vector(ora_ctx_t *c, const ora_idx_t *x, uint8_t *bin, uint64_t
 	}
 	sv[max_index].top = 1;
 	total += max_length;
+	*total_out = total;
+	return ns;
+}
+static void seed_vector(ora_ctx_t *c, const ora_idx_t *x, uint8_t *bin, uint64_t *kb, uint32_t n, ora_seed_t *sv, uint32_t direction, sdir_t *out)
+{
+	store_kmers(bin, n, x->ek_len, x->single_base_max, kb);
+	uint32_t total = 0, ns = scan_and_mark(x, kb, n, sv, direction, c->cnt, &total);
 	out->seed_v = sv; out->l_seed_v = ns; out->bin_read = bin; out->kmer = kb; out->direction = direction; out->total_score = total;
+}
+/* a-3 behind the table probes, on a caller's hit bytes (tests/test_stage_seed.py): one byte per window of a strand (non-zero: both table bits
+ * are set), direction 1 = forward, 0 = reverse -> the seed list with its top marks and total_score, as ora_last_seeds gives them.  The scan is
+ * search_exist and the marking loop of seed_vector themselves, on a filter whose two tables are the one byte 0x80 under the mask 0: every k-mer
+ * but 0 hashes to bit 0, which is set, and the k-mer 0 misses as it always does.  sv needs room for n / 3 + 2 seeds. */
+int ora_seed_stage(const uint8_t *hit, uint32_t n, int direction, ora_seed_t *sv, uint32_t max_sv, uint32_t *total_score)
+{
+	static uint8_t one_bit = 0x80;
+	if (max_sv < n / 3 + 2) return -1;
+	ora_idx_t x; memset(&x, 0, sizeof x);
+	x.ek_mask = 0; x.ek0 = &one_bit; x.ek1 = &one_bit;
+	uint64_t *kv = malloc(8 * ((size_t)n + 1));
+	for (uint32_t i = 0; i < n; i++) kv[i] = hit[i] ? 1 : 0;
+	sv[0].offset = 0; sv[0].len = 0; sv[0].top = 0;                  /* (a strand without seeds: the marking loop still writes sv[0].top) */
+	uint32_t total = 0, ns = scan_and_mark(&x, kv, n, sv, direction ? FORWARD : REVERSE, NULL, &total);
+	free(kv);
+	if (total_score) *total_score = total;
+	return (int)ns;
 }
 
 /* a-1 getIsland, src/cly.c:1236-1268 */

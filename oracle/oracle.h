@@ -85,6 +85,9 @@ void ora_ctx_set_history(ora_ctx_t *c, int max_read_l);
 int  ora_last_seeds(const ora_ctx_t *c, int strand /*1=F,0=R*/, const ora_seed_t **seeds, uint32_t *total_score);
 /* exist-kmer hit bit of every window of a strand (1 byte per window), for the probe kernel's parity */
 void ora_exist_bits(const ora_idx_t *idx, const char *seq, uint32_t len, int strand, uint8_t *out);
+/* a-3 behind the table probes (tests/test_stage_seed.py): search_exist_kmer_M2 and the top marking of get_seed_vector_M2 as ora_classify runs
+ * them, on one hit byte per window of a strand (1 = forward, 0 = reverse); returns the number of seeds (sv: room for n / 3 + 2), or -1 */
+int  ora_seed_stage(const uint8_t *hit, uint32_t n, int direction, ora_seed_t *sv, uint32_t max_sv, uint32_t *total_score);
 /* work counters of the last call: P0,P1,OCC,SA,RW,MEMS */
 int  ora_last_anchors(const ora_ctx_t *c, ora_anchor_t *out, int max);
 void ora_last_counters(const ora_ctx_t *c, uint64_t out[8]);

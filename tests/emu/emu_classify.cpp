@@ -214,48 +214,204 @@ extern "C" uint32_t emu_sms_peak(void *p)
 	while (n && a[n - 1] == 0xCDCDCDCDu) n--;
 	return (uint32_t)((n + 3) / 4);
 }
-// k_seed_scan's per-lane code (dsb_seed_scan.h) on the strands of the last read: the seed list of one strand and the number of
-// windows it asked for ([0] with a k-mer that passes the low-complexity filter, [1] all); same layout as emu_seeds
-extern "C" int emu_scan_seeds(void *p, int strand, DsbSeed *out, int max_out, uint32_t *total, uint32_t *probes)
+// ---- one round of a lane of k_seed_scan, stage by stage: a RESTATEMENT of the per-lane part of the kernel's loop (dsb_gpu.hip), line for line
+// but for the names of the word cache.  (As functions of dsb_seed_scan.h that the kernel calls too, the kernel's resource line stayed the
+// parent's but its ISA did not, and the benchmark's seed lookup on the strain index came out 0.7 % slower than the parent's own spread allows:
+// DESIGN.md.  The device leg of tests/test_stage_seed.py is what covers the kernel's own text.)
+// packed words wbase .. wbase + 2 of the forward strand (reverse-strand lanes keep them reverse-complemented); none yet: no index is near wbase
+struct DsbScanWords { uint64_t K0, K1, K2; uint32_t wbase; };
+DSB_SCAN_FN void dsb_scan_words_init(DsbScanWords &c) { c.K0 = c.K1 = c.K2 = 0; c.wbase = 0xfffffff0u; }
+DSB_SCAN_FN uint32_t dsb_scan_lowest(const uint32_t (&want)[DSB_SCAN_W])
 {
-	EmuCtx *e = (EmuCtx *)p; const DsbDevIndex &dx = e->dx; const WCtx &w = e->w;
-	const uint32_t L = w.L, n = L >= 40 ? L - dx.ek_len + 1 : 0; const bool rc = strand == 0;
-	const int k = dx.ek_len; const uint64_t kmask = k >= 32 ? ~0ULL : ((1ULL << (2 * k)) - 1ULL);
-	std::vector<DsbSeed> sv;
+	uint32_t lo = DSB_SCAN_NONE;
+#pragma unroll
+	for (int t = 0; t < DSB_SCAN_W; t++) lo = want[t] < lo ? want[t] : lo;
+	return lo;
+}
+// the three packed words that hold the wanted k-mers (lo: the smallest wanted window, not DSB_SCAN_NONE): a sliding window in registers, a
+// word is loaded only when the scan has moved past the ones at hand (the texture addresser, not the memory behind it, is what the kernel
+// saturates: every lane's load is a request of its own)
+DSB_SCAN_FN void dsb_scan_words_fetch(DsbScanWords &c, const uint64_t *P, uint32_t lo, bool rc)
+{
+	const uint32_t wi = lo >> 5;
+	uint64_t n0, n1, n2;
+#define DSB_SCAN_WORD(dst, idx) \
+	if ((idx) == c.wbase) dst = c.K0; else if ((idx) == c.wbase + 1) dst = c.K1; else if ((idx) == c.wbase + 2) dst = c.K2; \
+	else { dst = P[idx]; if (rc) dst = dsb_revcomp_kmer(dst, 32); }
+	DSB_SCAN_WORD(n0, wi) DSB_SCAN_WORD(n1, wi + 1) DSB_SCAN_WORD(n2, wi + 2)
+#undef DSB_SCAN_WORD
+	c.K0 = n0; c.K1 = n1; c.K2 = n2; c.wbase = wi;
+}
+// k-mer, low-complexity filter and first hash of every wanted window (base: the first window of the word of the smallest).  Forward
+// lanes: bases of the block in order K0 K1 K2, window at rel; reverse lanes: the block reverse-complemented is rc(K2) rc(K1) rc(K0), and
+// the reverse complement of the k-mer at rel is the k-mer at 96 - rel - k of that block.  p0 counts the windows that pass the filter.
+DSB_SCAN_FN void dsb_scan_kmers(const DsbScanWords &c, const uint32_t (&want)[DSB_SCAN_W], uint32_t base, bool rc, int k, uint64_t kmask, int sbm, uint64_t ek_mask,
+                                uint64_t (&km)[DSB_SCAN_W], uint64_t (&h1)[DSB_SCAN_W], bool (&ok)[DSB_SCAN_W], uint32_t &p0)
+{
+	const uint64_t B0 = rc ? c.K2 : c.K0, B1 = c.K1, B2 = rc ? c.K0 : c.K2;
+#pragma unroll
+	for (int t = 0; t < DSB_SCAN_W; t++) {
+		ok[t] = want[t] != DSB_SCAN_NONE; km[t] = 0; h1[t] = 0;
+		if (ok[t]) {
+			uint32_t rel = want[t] - base;                                // < 64: the window starts in the first or second word
+			if (rc) rel = 96u - rel - (uint32_t)k;                        // 12 .. 80
+			const uint64_t a = rel < 32 ? B0 : rel < 64 ? B1 : B2, b = rel < 32 ? B1 : B2; const uint32_t sh = (rel & 31u) * 2;
+			const uint64_t hi = sh ? ((a << sh) | (b >> (64 - sh))) : a;
+			const uint64_t v = (hi >> (64 - 2 * k)) & kmask;
+			ok[t] = dsb_kmer_ok(v, k, sbm); km[t] = v;
+			if (ok[t]) { p0++; h1[t] = dsb_ph1(v) & ek_mask; }
+		}
+	}
+}
+// table 0 (get_exist_kmer, src/cly.c:956-972); returns whether any window of the lane goes on to table 1
+DSB_SCAN_FN bool dsb_scan_table0(const uint8_t *ek0, const uint64_t (&h1)[DSB_SCAN_W], bool (&ok)[DSB_SCAN_W])
+{
+	uint8_t t0[DSB_SCAN_W];
+#pragma unroll
+	for (int t = 0; t < DSB_SCAN_W; t++) { t0[t] = 0; if (ok[t]) t0[t] = ek0[h1[t] >> 3]; }
+	bool any1 = false;
+#pragma unroll
+	for (int t = 0; t < DSB_SCAN_W; t++) { ok[t] = ok[t] && ((t0[t] >> (7 - (h1[t] & 7))) & 1); any1 |= ok[t]; }
+	return any1;
+}
+// table 1 in two steps, its loads first: p1 counts the probes made
+DSB_SCAN_FN void dsb_scan_table1_load(const uint8_t *ek1, uint64_t ek_mask, const uint64_t (&km)[DSB_SCAN_W], const bool (&ok)[DSB_SCAN_W],
+                                      uint8_t (&t1)[DSB_SCAN_W], uint64_t (&h2)[DSB_SCAN_W], uint32_t &p1)
+{
+#pragma unroll
+	for (int t = 0; t < DSB_SCAN_W; t++) { t1[t] = 0; h2[t] = 0; if (ok[t]) { h2[t] = dsb_ph2(km[t]) & ek_mask; t1[t] = ek1[h2[t] >> 3]; p1++; } }
+}
+// bit t of the result = window want[t] hit
+DSB_SCAN_FN uint32_t dsb_scan_table1_bits(const bool (&ok)[DSB_SCAN_W], const uint8_t (&t1)[DSB_SCAN_W], const uint64_t (&h2)[DSB_SCAN_W])
+{
+	uint32_t bits = 0;
+#pragma unroll
+	for (int t = 0; t < DSB_SCAN_W; t++) if (ok[t] && ((t1[t] >> (7 - (h2[t] & 7))) & 1)) bits |= 1u << t;
+	return bits;
+}
+
+// ---- the seed lookup on its own (tests/test_stage_seed.py).  One lane of k_seed_scan: the state machine of dsb_seed_scan.h and the round
+// functions above in the kernel's order, without the wavefront votes (a lane whose neighbours go on to table 1 runs the table-1 step with
+// nothing to ask, which changes nothing).  P: the packed words of the forward strand, followed by the reverse strand's as on the device.
+// cnt: [0] windows that passed the low-complexity filter (the kernel's first counter), [1] windows asked for, [2] table-1 probes (the
+// second counter), [3] rounds, [4] packed words loaded from memory
+struct ScanLane { std::vector<DsbSeed> sv; uint32_t ns = 0, total = 0, cnt[5] = {0, 0, 0, 0, 0}; };
+static void scan_lane(const uint64_t *P, uint32_t n, int k, int sbm, const uint8_t *ek0, const uint8_t *ek1, uint64_t ek_mask, const uint8_t *summ, int summ_shift,
+                      bool rc, DsbScanLook look, ScanLane &o)
+{
+	const uint64_t kmask = k >= 32 ? ~0ULL : ((1ULL << (2 * k)) - 1ULL);
+	std::vector<DsbSeed> &sv = o.sv;
 	auto store = [&](uint32_t idx, uint32_t off, uint32_t len) { if (sv.size() <= idx) sv.resize(idx + 1); sv[idx].offset = off; sv[idx].len = (uint16_t)len; sv[idx].top = 0; };
 	auto mark = [&](uint32_t idx) { sv[idx].top = 1; };
-	DsbScan s; dsb_scan_init(s, n, dsb_scan_look_for((dx.ek_mask + 1) / 8));
-	uint32_t np = 0, nall = 0;
+	DsbScan s; dsb_scan_init(s, n, look);
+	uint32_t p0 = 0, p1 = 0;
+	DsbScanWords kw; dsb_scan_words_init(kw);
 	while (s.mode != DSB_SCAN_DONE) {
-		uint32_t want[DSB_SCAN_W]; dsb_scan_want(s, want); uint32_t bits = 0;
-		uint32_t lo = DSB_SCAN_NONE; for (int t = 0; t < DSB_SCAN_W; t++) if (want[t] < lo) lo = want[t];
-		for (int t = 0; t < DSB_SCAN_W; t++) {
-			if (want[t] == DSB_SCAN_NONE) continue;
-			nall++;
-			// the kernel's three-word window: every wanted window starts within the two packed words at lo >> 5
-			const uint32_t base = lo & ~31u, rel = want[t] - base;
-			if (rel >= 64) abort();
-			const size_t wi = lo >> 5; const uint64_t W0 = e->pk[wi], W1 = e->pk[wi + 1], W2 = wi + 2 < (L + 31) / 32 + 1 ? e->pk[wi + 2] : 0;
-			const uint64_t a = rel < 32 ? W0 : W1, b = rel < 32 ? W1 : W2; const uint32_t sh = (rel & 31u) * 2;
-			const uint64_t hi = sh ? ((a << sh) | (b >> (64 - sh))) : a;
-			uint64_t v = (hi >> (64 - 2 * k)) & kmask;
-			if (rc) v = dsb_revcomp_kmer(v, k);
-			if (!dsb_kmer_ok(v, k, dx.single_base_max)) continue;
-			np++;
-			const uint64_t h1 = dsb_ph1(v) & dx.ek_mask;
-			if (((dx.ek0[h1 >> 3] >> (7 - (h1 & 7))) & 1) == 0) continue;
-			const uint64_t h2 = dsb_ph2(v) & dx.ek_mask;
-			if ((dx.ek1[h2 >> 3] >> (7 - (h2 & 7))) & 1) bits |= 1u << t;
+		uint32_t want[DSB_SCAN_W]; dsb_scan_want(s, want);
+		const uint32_t lo = dsb_scan_lowest(want);
+		if (lo != DSB_SCAN_NONE) {
+			const uint32_t wi = lo >> 5;
+			for (uint32_t q = wi; q < wi + 3; q++) if (q - kw.wbase > 2u) o.cnt[4]++;
+			dsb_scan_words_fetch(kw, P, lo, rc);
 		}
+		for (int t = 0; t < DSB_SCAN_W; t++) if (want[t] != DSB_SCAN_NONE) o.cnt[1]++;
+		uint64_t km[DSB_SCAN_W], h1[DSB_SCAN_W]; bool ok[DSB_SCAN_W];
+		dsb_scan_kmers(kw, want, lo & ~31u, rc, k, kmask, sbm, ek_mask, km, h1, ok, p0);
+		if (summ) {          // (the kernel's own four lines)
+			uint8_t sb[DSB_SCAN_W];
+			for (int t = 0; t < DSB_SCAN_W; t++) { sb[t] = 0xff; if (ok[t]) sb[t] = summ[(h1[t] >> summ_shift) >> 3]; }
+			for (int t = 0; t < DSB_SCAN_W; t++) ok[t] = ok[t] && ((sb[t] >> ((h1[t] >> summ_shift) & 7)) & 1);
+		}
+		const bool any1 = dsb_scan_table0(ek0, h1, ok);
+		uint32_t bits = 0;
+		if (any1) { uint8_t t1[DSB_SCAN_W]; uint64_t h2[DSB_SCAN_W]; dsb_scan_table1_load(ek1, ek_mask, km, ok, t1, h2, p1); bits = dsb_scan_table1_bits(ok, t1, h2); }
 		dsb_scan_consume(s, bits, rc, store, mark);
+		o.cnt[3]++;
 	}
 	dsb_scan_finish(s, mark);
-	int m = (int)s.ns < max_out ? (int)s.ns : max_out;
-	for (int i = 0; i < m; i++) out[i] = sv[i];
-	if (total) *total = s.total;
-	if (probes) { probes[0] = np; probes[1] = nall; }
-	return (int)s.ns;
+	o.ns = s.ns; o.total = s.total; o.cnt[0] = p0; o.cnt[2] = p1;
 }
+static DsbScanLook look_of(const uint8_t *look, uint64_t table_bytes)
+{
+	DsbScanLook k = dsb_scan_look_for(table_bytes);
+	if (look) { k.after_seed = look[0]; k.back_fwd = look[1]; k.fwd_n = look[2]; k.stride_n = look[3]; }
+	return k;
+}
+static int scan_lane_out(const ScanLane &o, DsbSeed *out, int max_out, uint32_t *total, uint32_t *cnt)
+{
+	const int m = (int)o.ns < max_out ? (int)o.ns : max_out;
+	for (int i = 0; i < m; i++) out[i] = o.sv[i];
+	if (total) *total = o.total;
+	if (cnt) memcpy(cnt, o.cnt, sizeof o.cnt);
+	return (int)o.ns;
+}
+// the strands of the last read on the index of the context: the seed list of one strand (same layout as emu_seeds) and the counters of
+// scan_lane; look: after_seed, back_fwd, fwd_n, stride_n (null: what dsb_scan_look_for gives the index), summ: a summary of table 0 (or null)
+extern "C" int emu_scan_seeds(void *p, int strand, DsbSeed *out, int max_out, uint32_t *total, uint32_t *cnt, const uint8_t *look, const uint8_t *summ, int summ_shift)
+{
+	EmuCtx *e = (EmuCtx *)p; const DsbDevIndex &dx = e->dx; const WCtx &w = e->w;
+	const uint32_t L = w.L, n = L >= 40 ? L - dx.ek_len + 1 : 0;
+	ScanLane o;
+	scan_lane(e->pk.data(), n, dx.ek_len, dx.single_base_max, dx.ek0, dx.ek1, dx.ek_mask, summ, summ_shift, strand == 0, look_of(look, (dx.ek_mask + 1) / 8), o);
+	return scan_lane_out(o, out, max_out, total, cnt);
+}
+// the same on a caller's packed read (pk: 2 x ((L + 31) / 32 + 1) words, forward strand first) and a caller's filter tables
+extern "C" int emu_stage_scan_read(const uint64_t *pk, uint32_t L, int k, int sbm, const uint8_t *ek0, const uint8_t *ek1, uint64_t ek_mask, const uint8_t *summ, int summ_shift,
+                                   int strand, const uint8_t *look, DsbSeed *out, int max_out, uint32_t *total, uint32_t *cnt)
+{
+	if (L < 40 || k < 1 || k > 20 || !look) return -1;
+	ScanLane o;
+	scan_lane(pk, L - (uint32_t)k + 1, k, sbm, ek0, ek1, ek_mask, summ, summ_shift, strand == 0, look_of(look, 0), o);
+	return scan_lane_out(o, out, max_out, total, cnt);
+}
+// the state machine alone on one hit byte per window of a strand (strand 1 forward, 0 reverse; the reverse strand is scanned through the
+// mirrored index, as the kernel does)
+extern "C" int emu_stage_scan_bytes(const uint8_t *hit, uint32_t n, int strand, const uint8_t *look, DsbSeed *out, int max_out, uint32_t *total, uint32_t *cnt)
+{
+	if (!look) return -1;
+	const bool rc = strand == 0;
+	ScanLane o; std::vector<DsbSeed> &sv = o.sv;
+	auto store = [&](uint32_t idx, uint32_t off, uint32_t len) { if (sv.size() <= idx) sv.resize(idx + 1); sv[idx].offset = off; sv[idx].len = (uint16_t)len; sv[idx].top = 0; };
+	auto mark = [&](uint32_t idx) { sv[idx].top = 1; };
+	DsbScan s; dsb_scan_init(s, n, look_of(look, 0));
+	while (s.mode != DSB_SCAN_DONE) {
+		uint32_t want[DSB_SCAN_W]; dsb_scan_want(s, want); uint32_t bits = 0;
+		for (int t = 0; t < DSB_SCAN_W; t++) {
+			if (want[t] == DSB_SCAN_NONE) continue;
+			if (want[t] >= n) return -2;
+			o.cnt[1]++;
+			if (hit[rc ? n - 1 - want[t] : want[t]]) bits |= 1u << t;
+		}
+		dsb_scan_consume(s, bits, rc, store, mark);
+		o.cnt[3]++;
+	}
+	dsb_scan_finish(s, mark);
+	o.ns = s.ns; o.total = s.total;
+	return scan_lane_out(o, out, max_out, total, cnt);
+}
+// every window of one packed strand through dsb_probe_window, as k_seed_probe asks (P: (L + 31) / 32 + 1 words); went_t1: table-1 probes made
+extern "C" void emu_stage_probe(const uint64_t *P, uint32_t n, int k, int sbm, const uint8_t *ek0, const uint8_t *ek1, uint64_t ek_mask, const uint8_t *summ, int summ_shift,
+                                uint8_t *out, uint32_t *went_t1)
+{
+	const uint64_t kmask = k >= 32 ? ~0ULL : ((1ULL << (2 * k)) - 1ULL);
+	uint32_t t1n = 0;
+	for (uint32_t q = 0; q < n; q++) { int t1 = 0; out[q] = (uint8_t)dsb_probe_window(P, q, k, kmask, sbm, ek0, ek1, ek_mask, &t1, summ, summ_shift); t1n += (uint32_t)t1; }
+	if (went_t1) *went_t1 = t1n;
+}
+#if DSB_EMU_LANES != 64
+// seed_vector_scan on a caller's hit words (bit w & 63 of word w >> 6; the bits behind n are 0, as k_seed_probe leaves them, and one
+// zero word follows, as seed_vector stages them); direction 1 forward, 0 reverse.  One lane runs it on the device as well.
+extern "C" int emu_stage_vector_scan(const uint64_t *words, uint32_t n, int direction, DsbSeed *out, int max_out, uint32_t *total)
+{
+	std::vector<DsbSeed> sv((size_t)(n >> 1) + 64); uint32_t ns = 0, tot = 0;
+	memset(sv.data(), 0, sv.size() * sizeof(DsbSeed));
+	seed_vector_scan<const uint64_t *>(words, n, sv.data(), direction ? D_FORWARD : D_REVERSE, &ns, &tot);
+	const int m = (int)ns < max_out ? (int)ns : max_out;
+	for (int i = 0; i < m; i++) out[i] = sv[i];
+	if (total) *total = tot;
+	return (int)ns;
+}
+#endif
 // loop budget of the following reads (DSB_STEP_LIMIT by default); steps the last read charged
 // a-9 on its own: the device's register-packed lv_extd on two strings that arrive with 8 bytes in front of them (as its callers' local
 // arrays hold them); the end marks go where the callers put them

@@ -30,7 +30,7 @@ class Emu:
         L.emu_counters.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         if hasattr(L, "dsb_emu_findings"):
             L.dsb_emu_findings.argtypes = [C.c_char_p, C.c_size_t]; L.dsb_emu_findings.restype = C.c_int
-        L.emu_scan_seeds.argtypes = [C.c_void_p, C.c_int, C.POINTER(EmuSeed), C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.emu_scan_seeds.argtypes = [C.c_void_p, C.c_int, C.POINTER(EmuSeed), C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_char_p, C.c_void_p, C.c_int]
         self.L = L
         self.idx = C.c_void_p()
         rc = L.dsb_index_open(os.fsencode(index_dir), C.byref(self.idx))
@@ -71,9 +71,12 @@ class Emu:
         n = self.L.emu_seeds(self.e, strand, buf, 65536, C.byref(ts))
         return [(buf[i].offset, buf[i].len, buf[i].top) for i in range(n)], ts.value
 
-    def scan_seeds(self, strand):
-        """the seed list of one strand of the last read as k_seed_scan's per-lane state machine makes it (probing only what
-        the scan consumes) -> (seeds, total_score, (probes with a valid k-mer, windows asked for))"""
-        buf = (EmuSeed * 65536)(); ts = C.c_uint32(); pr = (C.c_uint32 * 2)()
-        n = self.L.emu_scan_seeds(self.e, strand, buf, 65536, C.byref(ts), pr)
-        return [(buf[i].offset, buf[i].len, buf[i].top) for i in range(n)], ts.value, (pr[0], pr[1])
+    def scan_seeds(self, strand, look=None, summ=None, summ_shift=0):
+        """the seed list of one strand of the last read as one lane of k_seed_scan makes it (the state machine of dsb_seed_scan.h and
+        the emulation's restatement of the kernel's round, probing only what the scan consumes) -> (seeds, total_score, (windows that passed the low-complexity filter,
+        windows asked for, table-1 probes)); look: (after_seed, back_fwd, fwd_n, stride_n), None: the index's own setting; summ: a
+        summary of table 0 as numpy u8 (None: no summary)"""
+        buf = (EmuSeed * 65536)(); ts = C.c_uint32(); pr = (C.c_uint32 * 5)()
+        n = self.L.emu_scan_seeds(self.e, strand, buf, 65536, C.byref(ts), pr, bytes(look) if look is not None else None,
+                                  summ.ctypes.data if summ is not None else None, summ_shift)
+        return [(buf[i].offset, buf[i].len, buf[i].top) for i in range(n)], ts.value, (pr[0], pr[1], pr[2])

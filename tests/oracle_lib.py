@@ -39,6 +39,7 @@ def lib():
         L.ora_ctx_reset_history.argtypes = [C.c_void_p]
         L.ora_last_seeds.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.POINTER(OraSeed)), C.POINTER(C.c_uint32)]
         L.ora_exist_bits.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint8)]
+        L.ora_seed_stage.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(OraSeed), C.c_uint32, C.POINTER(C.c_uint32)]
         L.ora_last_counters.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         L.ora_last_anchors.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.ora_occ.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint8)]; L.ora_occ.restype = C.c_uint64
@@ -46,6 +47,18 @@ def lib():
         L.ora_classify_file.restype = C.c_long
         _lib = L
     return _lib
+
+
+def seed_stage(hit, direction):
+    """the oracle's scan and top marking (a-3) on one hit byte per window (numpy u8 / bytes); direction 1 = forward strand, 0 = reverse
+    -> ([(offset, len, top)], total_score)"""
+    hit = bytes(hit); n = len(hit)
+    cap = n // 3 + 2
+    buf = (OraSeed * cap)(); ts = C.c_uint32()
+    ns = lib().ora_seed_stage(hit, n, direction, buf, cap, C.byref(ts))
+    if ns < 0:
+        raise RuntimeError("ora_seed_stage = %d" % ns)
+    return [(buf[i].offset, buf[i].len, buf[i].top) for i in range(ns)], ts.value
 
 
 class Oracle:
