@@ -36,7 +36,7 @@
 #define SPENT(w) (++(w).steps > (w).step_limit)        /* group-uniform code only */
 #define LSPENT(l) (++(l).lsteps > (l).step_limit)      /* per-lane code (fast_island): l is an LCtx */
 // stage timers (100 MHz ticks), accumulated per slot when DSB_DEBUG is set
-#define TICK(w, k) do { if ((w).dbg) { uint64_t _t = DSB_CLOCK(); (w).tacc[k] += _t - (w).tlast; (w).tlast = _t; } } while (0)
+#define TICK(w, k) do { if (DSB_UNI64((w).dbg)) { uint64_t _t = DSB_CLOCK(); (w).tacc[k] += _t - (w).tlast; (w).tlast = _t; } } while (0)
 // the fine timers sit inside the per-node loops of the extensions: compiled in only with -DDSB_TIMERS (DSB_HIPCC_FLAGS=-DDSB_TIMERS
 // python -c "import __graft_entry__ as g; g.build()"): even a test of w.dbg per hook costs an LDS round trip there
 #ifdef DSB_TIMERS
@@ -52,7 +52,7 @@
 #define TX1(w, k, v) do { } while (0)
 #define TXC(w, k) do { } while (0)
 #endif
-#define MARK(w, code) do { if ((w).dbg && DSB_LANE == 0) { (w).dbg[0] = (code); (w).dbg[1] = (w).steps; } } while (0)
+#define MARK(w, code) do { if (DSB_UNI64((w).dbg) && DSB_LANE == 0) { (w).dbg[0] = (code); (w).dbg[1] = (w).steps; } } while (0)
 #ifdef DSB_LDS_DIET              /* experiment: 9.8 KB of LDS per wavefront = 16 wavefronts per CU (with -DDSB_WAVES_PER_EU=4) */
 #define DSB_WTAB_SLOTS 2176u
 #else
@@ -71,11 +71,11 @@
 #ifndef DSB_LANE_STEPS
 #define DSB_LANE_STEPS 256u        /* search steps a lane may spend on its read in fast_classify_lane */
 #endif
-#define DSB_BOOST_IF_HEAVY(w) do { if (!(w).boosted && (w).dp_preds > DSB_BOOST_PREDS) { dsb_setprio3(); (w).boosted = 1; } } while (0)
+#define DSB_BOOST_IF_HEAVY(w) do { if (!DSB_UNI((w).boosted) && DSB_UNI((w).dp_preds) > DSB_BOOST_PREDS) { dsb_setprio3(); (w).boosted = 1; } } while (0)
 #endif
 // ... and beyond heavy_limit predecessors a single-wavefront launch gives the read up (DSB_ST_HEAVY): spending the loop budget
 // makes the extension loops stop at their next SPENT test, so the hand-over costs nothing per node
-#define DSB_HEAVY_CHECK(w) do { if ((w).heavy_limit && (w).dp_preds > (w).heavy_limit) { (w).status |= DSB_ST_HEAVY; (w).steps = (w).step_limit; } } while (0)
+#define DSB_HEAVY_CHECK(w) do { const uint32_t hl_ = DSB_UNI((w).heavy_limit); if (hl_ && DSB_UNI((w).dp_preds) > hl_) { (w).status |= DSB_ST_HEAVY; (w).steps = (w).step_limit; } } while (0)
 
 namespace DSB_NS {
 
@@ -84,6 +84,20 @@ namespace DSB_NS {
 #include "dsb_emu_shim.h"
 #else
 #include "dsb_wave.h"
+#endif
+// DSB_UNI(v) / DSB_UNI64(v): "all lanes that are here hold this value" -- v through v_readfirstlane, so that it lives in a scalar
+// register, what is computed from it stays on the scalar unit, and a test of it is an s_cmp and a scalar branch.  Every value of the
+// read's control flow is wave-uniform (the head of this file), but the compiler cannot know it of what comes out of LDS (every
+// w.field), out of the arena or the index by a vector load, or out of a function that is not inlined: it keeps 64 copies and lowers each
+// `if` and `while` on them as divergent (v_cmp, save / and exec, s_cbranch_execz, restore exec).  The rule: a value is DSB_UNI where
+// it ENTERS wave-uniform code from memory or from such a call and a loop bound, a branch condition or an address is made of it --
+// once, into a local, and again after every call that can redefine it; never a value of per-lane code (anything that takes an LCtx,
+// a lane's own node / gap / position), and what lane 0 computed in a DSB_SERIAL section only after it went through LDS.  The type
+// of v is kept (DSB_UNI64: 64-bit integers and pointers to global memory).  The identity in the host emulations (DSB_RFL of
+// tests/emu/dsb_emu_shim.h); a checking build supplies definitions of its own that compare v across the lanes that are there.
+#ifndef DSB_UNI
+#define DSB_UNI(v) ((decltype(+(v)))DSB_RFL(v))
+#define DSB_UNI64(v) ((decltype(+(v)))DSB_RFL64((uint64_t)(v)))
 #endif
 
 // Work counters of a launch (the terms of the algorithmic bytes): [0] occ() evaluations, [1] MEM searches
@@ -1700,9 +1714,10 @@ DV int MEM_search(P8 q, P8 t, bool forward, int max)
 }
 DV DsbSms *push_sms(WCtxL &w)
 {
-	const uint32_t cap = w.x->sms_cap;
-	if (w.n_sms >= cap) { w.status |= DSB_ST_SMS_OVF; return w.sms + cap - 1; }
-	return w.sms + w.n_sms++;
+	const uint32_t cap = DSB_UNI(w.x->sms_cap), n = DSB_UNI(w.n_sms); DsbSms *const sms = DSB_UNI64(w.sms);
+	if (n >= cap) { w.status |= DSB_ST_SMS_OVF; return sms + cap - 1; }
+	w.n_sms = n + 1;
+	return sms + n;
 }
 DV uint64_t bin2kmer9(const uint8_t *s) { uint64_t v = 0;
 #pragma unroll
@@ -1897,8 +1912,8 @@ DN uint32_t sdp_match_t(WCtxL &w, const SdpArgsT<P8> a, uint32_t n_sms)
 	if (t_kmer_num > 0x7fffffffu || t_kmer_num <= 4) return n_sms; // the reference's loop does not run either (t_len >= 13 at every call site)
 	uint32_t n_pos = (t_kmer_num - 4 + 3) / 4;                      // i = 4, 8, ... < t_kmer_num
 	// the context lives in memory (it is shared by reference with non-inlined callers): work on copies
-	const int lane = DSB_LANE; uint32_t *const red = w.red; DsbSms *const sms = w.sms; const uint32_t sms_cap = w.x->sms_cap;
-	uint32_t lsteps = w.lsteps, mirror_bad = 0; int st = 0; const uint32_t step_limit = w.step_limit;
+	const int lane = DSB_LANE; uint32_t *const red = w.red; DsbSms *const sms = DSB_UNI64(w.sms); const uint32_t sms_cap = DSB_UNI(w.x->sms_cap);
+	uint32_t lsteps = w.lsteps, mirror_bad = 0; int st = 0; const uint32_t step_limit = DSB_UNI(w.step_limit);
 	sdp_match_groups<FWD, P8>(a, 0, n_pos, n_pos, lane, red, sms, sms_cap, lsteps, step_limit, st, n_sms, mirror_bad);
 	// (the budget and the status bits of the lanes become the wavefront's: the largest count, the union of the bits)
 	const uint32_t ls = (uint32_t)grp_max_i((int)(lsteps >> 1));
@@ -1997,7 +2012,7 @@ DN uint32_t sdp_match_inv(WCtxL &w, const SdpArgsT<P8> a, uint32_t n_sms, const 
 		}
 	}
 	wave_sync();
-	const uint32_t n_pairs = cntp[0];
+	const uint32_t n_pairs = DSB_UNI(cntp[0]);
 	TX1(w, 0, t_b);
 	if (n_pairs == 0) return n_sms;
 	if (n_pairs > DSB_INV_PAIRS) return DSB_INV_NONE;
@@ -2012,7 +2027,7 @@ DN uint32_t sdp_match_inv(WCtxL &w, const SdpArgsT<P8> a, uint32_t n_sms, const 
 	}
 	wave_sync();
 	// (E) one pair per lane: the two exact-match extensions, the node if it qualifies
-	uint32_t *const red = w.red; DsbSms *const sms = w.sms; const uint32_t sms_cap = w.x->sms_cap; bool ovf = false;
+	uint32_t *const red = w.red; DsbSms *const sms = DSB_UNI64(w.sms); const uint32_t sms_cap = DSB_UNI(w.x->sms_cap); bool ovf = false;
 	for (uint32_t b0 = 0; b0 < n_pairs; b0 += DSB_WAVE) {
 		DsbSms o; o.t_pos = o.q_pos = o.len = o.score = 0; bool ok = false;
 		if (b0 + (uint32_t)lane < n_pairs) {
@@ -2051,19 +2066,23 @@ template <class P8>
 DV uint32_t sdp_match_p(WCtxL &w, uint32_t n_sms, uint32_t q_bg, uint32_t q_ed, P8 q_base, int32_t q_lo, P8 t_str, uint32_t t_len, uint32_t t_st, bool isForward, uint4 *lnodes,
                         const uint64_t *qpk = nullptr)
 {
+	// (the window's bounds are the wavefront's: n_pos, n_pairs and the node count made of them stay in scalar registers)
+	n_sms = DSB_UNI(n_sms); q_bg = DSB_UNI(q_bg); q_ed = DSB_UNI(q_ed); q_lo = DSB_UNI(q_lo); t_len = DSB_UNI(t_len); t_st = DSB_UNI(t_st);
+	const uint32_t L = DSB_UNI(w.L);
 	SdpArgsT<P8> a; a.lnodes = lnodes; a.q_bg = q_bg; a.q_ed = q_ed; a.q_base = q_base; a.q_lo = q_lo; a.t_str = t_str; a.t_len = t_len; a.t_st = t_st;
-	a.tab = (const lds_u32 *)w.wtab; a.bm = reinterpret_cast<uint32_t *>(w.sortkey) + DSB_LANE;
-	a.n_q = sdp_nq(w.L, q_bg, q_ed);
+	a.tab = (const lds_u32 *)w.wtab; a.bm = reinterpret_cast<uint32_t *>(DSB_UNI64(w.sortkey)) + DSB_LANE;
+	a.n_q = sdp_nq(L, q_bg, q_ed);
 	if (a.n_q > DSB_WTAB_MAXQ) { w.status |= DSB_ST_SMS_OVF; return n_sms; }     // cannot happen: windows are <= 2001 wide
 	uint32_t t_kmer_num = t_len - 9 + 1;
 	if (a.n_q == 0 || t_kmer_num > 0x7fffffffu || t_kmer_num <= 4) return n_sms;
 	// wide window, few probed positions (every step of the right / left extensions, the bigger gaps): the reference side is hashed
 	if (qpk && a.n_q >= DSB_INV_MINQ && t_kmer_num <= 4 * DSB_INV_MAXPOS) {
-		const uint32_t rv = isForward ? sdp_match_inv<true, P8>(w, a, n_sms, qpk, (w.L + 31) / 32 + 1) : sdp_match_inv<false, P8>(w, a, n_sms, qpk, (w.L + 31) / 32 + 1);
+		const uint32_t rv_ = isForward ? sdp_match_inv<true, P8>(w, a, n_sms, qpk, (L + 31) / 32 + 1) : sdp_match_inv<false, P8>(w, a, n_sms, qpk, (L + 31) / 32 + 1);
+		const uint32_t rv = DSB_UNI(rv_);
 		if (rv != DSB_INV_NONE) return rv;
 	}
 	TX0(w, t_b);
-	if (qpk) wtab_build_pk((lds_u32 *)w.wtab, DSB_LANE, qpk, (w.L + 31) / 32 + 1, q_bg, a.n_q);
+	if (qpk) wtab_build_pk((lds_u32 *)w.wtab, DSB_LANE, qpk, (L + 31) / 32 + 1, q_bg, a.n_q);
 	else wtab_build<P8>((lds_u32 *)w.wtab, DSB_LANE, q_base + ((int32_t)q_bg - q_lo), 0u, a.n_q);
 	TX1(w, 0, t_b);
 	TX0(w, t_p);
@@ -2075,7 +2094,7 @@ DV uint32_t sdp_match_p(WCtxL &w, uint32_t n_sms, uint32_t q_bg, uint32_t q_ed, 
 DN uint32_t sdp_match_n(WCtxL &w, uint32_t n_sms, uint32_t q_bg, uint32_t q_ed, const uint8_t *q_str, const uint8_t *t_str, uint32_t t_len,
                         uint32_t t_st, bool isForward, uint4 *lnodes, const uint64_t *qpk)
 {
-	return sdp_match_p<gp8>(w, n_sms, q_bg, q_ed, q_str, 0, t_str, t_len, t_st, isForward, lnodes, qpk);
+	return sdp_match_p<gp8>(w, n_sms, q_bg, q_ed, DSB_UNI64(q_str), 0, DSB_UNI64(t_str), t_len, t_st, isForward, DSB_UNI64(lnodes), DSB_UNI64(qpk));
 }
 // ... or staged in LDS by sdp_middle_M2 behind the tables: lq holds the read from position q_lo on, lt the reference window
 DN uint32_t sdp_match_lds(WCtxL &w, uint32_t n_sms, uint32_t q_bg, uint32_t q_ed, const uint8_t *lq, int32_t q_lo, const uint8_t *lt, uint32_t t_len,
@@ -2087,7 +2106,7 @@ DV void sdp_match(WCtxL &w, uint32_t q_bg, uint32_t q_ed, const uint8_t *q_str, 
                   int tbl, uint32_t t_st, bool isForward)
 {
 	(void)key_len;
-	w.n_sms = sdp_match_n(w, w.n_sms, q_bg, q_ed, q_str, t_str, t_len, t_st, isForward, nullptr, w.pk[tbl]) & 0x7fffffffu;
+	w.n_sms = sdp_match_n(w, DSB_UNI(w.n_sms), q_bg, q_ed, q_str, t_str, t_len, t_st, isForward, nullptr, w.pk[tbl]) & 0x7fffffffu;
 }
 
 // (the ring lives in LDS: ring_ld / ring_st are typed accesses, ds_read_b128 / ds_write_b128)
@@ -3013,27 +3032,31 @@ DN int sdp_middle_M2(WCtxL &w, int32_t c_a, const uint8_t *q_str, int tbl, int k
 DN int sdp_right_M2_mw(WCtxL &w, const uint8_t *q_str, int tbl, int key_len, DsbChain *c_st, int chain_ID, uint32_t l_read, DsbScHash *sc_hash, int score_ori)
 {
 	DsbXP x = w.x;
-	score_ori += 10000;
+	// (scalar values only in the loop's state, as in the block-wise sdp_right_M2 below)
+	q_str = DSB_UNI64(q_str); tbl = DSB_UNI(tbl); c_st = DSB_UNI64(c_st); chain_ID = DSB_UNI(chain_ID); l_read = DSB_UNI(l_read); sc_hash = DSB_UNI64(sc_hash);
+	score_ori = DSB_UNI(score_ori) + 10000;
 	int total_max_score = score_ori, max_sms_id = 0;
 	DsbChain *c_h = c_st + chain_ID, *combined;
 	w.n_sms = 0;
-	uint8_t *ref = w.win_right;
+	uint8_t *ref = DSB_UNI64(w.win_right);
 	fill_window(w, ref, 1000 + 128);
 	wave_sync();
 	DsbSms *p = push_sms(w);
-	p->score = score_ori; p->q_pos = c_h->q_ed; p->t_pos = c_h->t_ed; p->len = 1 - 9;
-	ring_put(w, 0, p->t_pos, p->q_pos, p->len, p->score);
-	uint32_t best_t = c_h->t_ed, best_q = c_h->q_ed, best_len = (uint32_t)(1 - 9);     // fields of node max_sms_id
+	uint32_t best_t = DSB_UNI(c_h->t_ed), best_q = DSB_UNI(c_h->q_ed), best_len = (uint32_t)(1 - 9);     // fields of node max_sms_id
+	p->score = score_ori; p->q_pos = best_q; p->t_pos = best_t; p->len = 1 - 9;
+	ring_put(w, 0, best_t, best_q, (uint32_t)(1 - 9), (uint32_t)score_ori);
 	NodeBlock nb; nb.base = 0; nb.valid = 0;
 	DpBatchL &db = *w.dpb; db.n0 = 0; db.K = 0;
 	uint32_t bn0 = 0, bK = 0;                                 // the bounds of the batch in db
 	uint32_t current_sms = 1;
-	uint64_t t_offset_global = x->refinfo[c_h->ref_ID].seq_offset, t_length = x->refinfo[c_h->ref_ID].seq_l;
-	uint32_t c_t_offset = c_h->t_ed - 3;
+	const uint32_t ref_ID = DSB_UNI(c_h->ref_ID);
+	uint64_t t_offset_global = DSB_UNI64(x->refinfo[ref_ID].seq_offset), t_length = DSB_UNI64(x->refinfo[ref_ID].seq_l);
+	const uint8_t *const refbin = DSB_UNI64(x->refbin); const uint64_t ref_bases = DSB_UNI64(x->ref_bases);
+	uint32_t c_t_offset = best_t - 3;
 	int last_search = false;
-	uint32_t ch_q_st = c_h->q_st, ch_q_ed = c_h->q_ed;       // (they change when a chain is combined in: read again there)
+	uint32_t ch_q_st = DSB_UNI(c_h->q_st), ch_q_ed = best_q;       // (they change when a chain is combined in: read again there)
 	// loop state in registers (the context is in LDS: a round trip per access, and this loop runs per match node)
-	uint32_t steps = w.steps, n_sms = 1; const uint32_t step_limit = w.step_limit; DsbSms *const sms = w.sms; uint4 *const ring = w.ring;
+	uint32_t steps = DSB_UNI(w.steps), n_sms = 1; const uint32_t step_limit = DSB_UNI(w.step_limit); DsbSms *const sms = DSB_UNI64(w.sms); uint4 *const ring = w.ring;
 	while (1) {
 		if (++steps > step_limit) { w.status |= DSB_ST_TIMEOUT; break; }
 		if (n_sms == current_sms) {
@@ -3046,7 +3069,7 @@ DN int sdp_right_M2_mw(WCtxL &w, const uint8_t *q_str, int tbl, int key_len, Dsb
 				max_search_ref = l_read - ch_q_ed + 60;
 			} else max_search_ref = t_length - c_t_offset;
 			max_search_ref = MINV(600u, max_search_ref);
-			get_ref_wave(x->refbin, x->ref_bases, DSB_LANE, ref, c_t_offset + t_offset_global, max_search_ref + 50); cnt_add(Cnt{w.k.c, 1u}, 3, max_search_ref + 50);
+			get_ref_wave(refbin, ref_bases, DSB_LANE, ref, c_t_offset + t_offset_global, max_search_ref + 50); cnt_add(Cnt{w.k.c, 1u}, 3, max_search_ref + 50);
 			wave_sync();
 			int search_q_ed = (int)best_q + 1000;
 			search_q_ed = MINV((uint32_t)search_q_ed, l_read);
@@ -3055,7 +3078,7 @@ DN int sdp_right_M2_mw(WCtxL &w, const uint8_t *q_str, int tbl, int key_len, Dsb
 			sdp_match(w, search_q_st, search_q_ed, q_str, ref, max_search_ref, key_len, tbl, c_t_offset, true);
 			SUB1(w, 10);
 			c_t_offset += max_search_ref - 9 - 3;
-			n_sms = w.n_sms;
+			n_sms = DSB_UNI(w.n_sms);
 			if (n_sms == current_sms) break;
 			nb.valid = 0;
 			if (node_get(w, nb, current_sms).t_pos > best_t + 1000) break;
@@ -3069,22 +3092,22 @@ DN int sdp_right_M2_mw(WCtxL &w, const uint8_t *q_str, int tbl, int key_len, Dsb
 		c_sms->score = max_score;
 		{ uint4 r_; r_.x = cs.t_pos; r_.y = cs.q_pos; r_.z = cs.len; r_.w = (uint32_t)max_score; ring_st(ring, (current_sms - 1) & (DSB_RING - 1), r_); }
 		SUB0(w);
-		bool comb = (int)cs.len >= 8 && combine_chain(c_st, chain_ID, sc_hash, cs.t_pos - cs.q_pos, false, cs.q_pos, &combined) == true;
+		bool comb = (int)cs.len >= 8 && DSB_UNI(combine_chain(c_st, chain_ID, sc_hash, cs.t_pos - cs.q_pos, false, cs.q_pos, &combined)) == true;
 		SUB1(w, 12);
 		if (comb) {
 			int c_len = cs.len;
 			w.steps = steps;
-			total_max_score = MAXV(score_ori, max_score) - c_len + sdp_middle_M2(w, combined->cur, q_str, tbl, key_len);
-			steps = w.steps;
-			ch_q_st = c_h->q_st; ch_q_ed = c_h->q_ed;
+			total_max_score = MAXV(score_ori, max_score) - c_len + DSB_UNI(sdp_middle_M2(w, DSB_UNI(DSB_UNI64(combined)->cur), q_str, tbl, key_len));
+			steps = DSB_UNI(w.steps);
+			ch_q_st = DSB_UNI(c_h->q_st); ch_q_ed = DSB_UNI(c_h->q_ed);
 			score_ori = total_max_score; max_sms_id = 0;
 			w.n_sms = 0;
 			p = push_sms(w); n_sms = 1;
-			p->score = total_max_score; p->q_pos = c_h->q_ed; p->t_pos = c_h->t_ed; p->len = -9;
-			ring_put(w, 0, p->t_pos, p->q_pos, p->len, p->score);
-			best_t = c_h->t_ed; best_q = c_h->q_ed; best_len = (uint32_t)(-9); nb.valid = 0; db.K = 0; bK = 0;
+			best_t = DSB_UNI(c_h->t_ed); best_q = ch_q_ed; best_len = (uint32_t)(-9); nb.valid = 0; db.K = 0; bK = 0;
+			p->score = total_max_score; p->q_pos = best_q; p->t_pos = best_t; p->len = -9;
+			ring_put(w, 0, best_t, best_q, (uint32_t)(-9), (uint32_t)total_max_score);
 			current_sms = 1;
-			c_t_offset = c_h->t_ed;
+			c_t_offset = best_t;
 			continue;
 		}
 		if (total_max_score < max_score) { total_max_score = max_score; max_sms_id = current_sms - 1; best_t = cs.t_pos; best_q = cs.q_pos; best_len = cs.len; }
@@ -3100,26 +3123,28 @@ DN int sdp_right_M2_mw(WCtxL &w, const uint8_t *q_str, int tbl, int key_len, Dsb
 DN int sdp_left_M2_mw(WCtxL &w, const uint8_t *q_str, int tbl, int key_len, DsbChain *c_st, int chain_ID, uint32_t l_read, DsbScHash *sc_hash, int score_ori)
 {
 	DsbXP x = w.x;
-	score_ori += 10000;
+	q_str = DSB_UNI64(q_str); tbl = DSB_UNI(tbl); c_st = DSB_UNI64(c_st); chain_ID = DSB_UNI(chain_ID); sc_hash = DSB_UNI64(sc_hash);
+	score_ori = DSB_UNI(score_ori) + 10000;
 	int total_max_score = score_ori, max_sms_id = 0;
 	DsbChain *c_h = c_st + chain_ID, *combined;
 	w.n_sms = 0;
-	uint8_t *ref = w.win_left;
+	uint8_t *ref = DSB_UNI64(w.win_left);
 	fill_window(w, ref, 1000 + 128);
 	wave_sync();
 	DsbSms *p = push_sms(w);
-	p->score = score_ori; p->q_pos = c_h->q_st; p->t_pos = c_h->t_st;
-	ring_put(w, 0, p->t_pos, p->q_pos, 0, p->score);                       // a[0].len is never read by the left DP
-	uint32_t best_t = c_h->t_st, best_q = c_h->q_st;                       // fields of node max_sms_id
+	uint32_t best_t = DSB_UNI(c_h->t_st), best_q = DSB_UNI(c_h->q_st);     // fields of node max_sms_id
+	p->score = score_ori; p->q_pos = best_q; p->t_pos = best_t;
+	ring_put(w, 0, best_t, best_q, 0, (uint32_t)score_ori);                // a[0].len is never read by the left DP
 	NodeBlock nb; nb.base = 0; nb.valid = 0;
 	DpBatchL &db = *w.dpb; db.n0 = 0; db.K = 0;
 	uint32_t bn0 = 0, bK = 0;
 	uint32_t current_sms = 1;
-	uint64_t t_offset_global = x->refinfo[c_h->ref_ID].seq_offset;
-	uint32_t c_t_offset = c_h->t_st + 3;
+	uint64_t t_offset_global = DSB_UNI64(x->refinfo[DSB_UNI(c_h->ref_ID)].seq_offset);
+	const uint8_t *const refbin = DSB_UNI64(x->refbin); const uint64_t ref_bases = DSB_UNI64(x->ref_bases);
+	uint32_t c_t_offset = best_t + 3;
 	int last_search = false;
-	uint32_t ch_q_st = c_h->q_st;                             // (changes when a chain is combined in: read again there)
-	uint32_t steps = w.steps, n_sms = 1; const uint32_t step_limit = w.step_limit; DsbSms *const sms = w.sms; uint4 *const ring = w.ring;   // (as in sdp_right_M2)
+	uint32_t ch_q_st = best_q;                                // (changes when a chain is combined in: read again there)
+	uint32_t steps = DSB_UNI(w.steps), n_sms = 1; const uint32_t step_limit = DSB_UNI(w.step_limit); DsbSms *const sms = DSB_UNI64(w.sms); uint4 *const ring = w.ring;   // (as in sdp_right_M2)
 	while (1) {
 		if (++steps > step_limit) { w.status |= DSB_ST_TIMEOUT; break; }
 		if (n_sms == current_sms) {
@@ -3133,9 +3158,9 @@ DN int sdp_left_M2_mw(WCtxL &w, const uint8_t *q_str, int tbl, int key_len, DsbC
 			} else max_search_ref = c_t_offset;
 			max_search_ref = MINV(600u, max_search_ref);
 			if (t_offset_global == 0 && c_t_offset < 50 + max_search_ref)
-				{ get_ref_wave(x->refbin, x->ref_bases, DSB_LANE, ref, (int64_t)(c_t_offset + t_offset_global - max_search_ref), max_search_ref); cnt_add(Cnt{w.k.c, 1u}, 3, max_search_ref); }
+				{ get_ref_wave(refbin, ref_bases, DSB_LANE, ref, (int64_t)(c_t_offset + t_offset_global - max_search_ref), max_search_ref); cnt_add(Cnt{w.k.c, 1u}, 3, max_search_ref); }
 			else
-				{ get_ref_wave(x->refbin, x->ref_bases, DSB_LANE, ref, (int64_t)(c_t_offset + t_offset_global - max_search_ref - 50), max_search_ref + 50); cnt_add(Cnt{w.k.c, 1u}, 3, max_search_ref + 50); }
+				{ get_ref_wave(refbin, ref_bases, DSB_LANE, ref, (int64_t)(c_t_offset + t_offset_global - max_search_ref - 50), max_search_ref + 50); cnt_add(Cnt{w.k.c, 1u}, 3, max_search_ref + 50); }
 			wave_sync();
 			int search_q_st = (int)best_q - 1000;
 			search_q_st = MAXV(search_q_st, 0);
@@ -3144,7 +3169,7 @@ DN int sdp_left_M2_mw(WCtxL &w, const uint8_t *q_str, int tbl, int key_len, DsbC
 			sdp_match(w, search_q_st, search_q_ed, q_str, ref + 50, max_search_ref, key_len, tbl, c_t_offset - max_search_ref, false);
 			TX1(w, 3, t_lm);
 			c_t_offset = c_t_offset - max_search_ref + 9 + 3;
-			n_sms = w.n_sms;
+			n_sms = DSB_UNI(w.n_sms);
 			if (n_sms == current_sms) break;
 			nb.valid = 0;
 			if (node_get(w, nb, current_sms).t_pos + 1000 < best_t) break;
@@ -3156,20 +3181,20 @@ DN int sdp_left_M2_mw(WCtxL &w, const uint8_t *q_str, int tbl, int key_len, DsbC
 		TX1(w, 4, t_ld);
 		c_sms->score = max_score;
 		{ uint4 r_; r_.x = cs.t_pos; r_.y = cs.q_pos; r_.z = cs.len; r_.w = (uint32_t)max_score; ring_st(ring, (current_sms - 1) & (DSB_RING - 1), r_); }
-		if ((int)cs.len >= 8 && combine_chain(c_st, chain_ID, sc_hash, cs.t_pos - cs.q_pos, true, cs.q_pos + cs.len, &combined) == true) {
+		if ((int)cs.len >= 8 && DSB_UNI(combine_chain(c_st, chain_ID, sc_hash, cs.t_pos - cs.q_pos, true, cs.q_pos + cs.len, &combined)) == true) {
 			int c_len = cs.len;
 			w.steps = steps;
-			total_max_score = MAXV(score_ori, max_score) - c_len + sdp_middle_M2(w, combined->cur, q_str, tbl, key_len);
-			steps = w.steps;
-			ch_q_st = c_h->q_st;
+			total_max_score = MAXV(score_ori, max_score) - c_len + DSB_UNI(sdp_middle_M2(w, DSB_UNI(DSB_UNI64(combined)->cur), q_str, tbl, key_len));
+			steps = DSB_UNI(w.steps);
+			ch_q_st = DSB_UNI(c_h->q_st);
 			score_ori = total_max_score; max_sms_id = 0;
 			w.n_sms = 0;
 			p = push_sms(w); n_sms = 1;
-			p->score = total_max_score; p->q_pos = c_h->q_st; p->t_pos = c_h->t_st;
-			ring_put(w, 0, p->t_pos, p->q_pos, 0, p->score);
-			best_t = c_h->t_st; best_q = c_h->q_st; nb.valid = 0; db.K = 0; bK = 0;
+			best_t = DSB_UNI(c_h->t_st); best_q = ch_q_st; nb.valid = 0; db.K = 0; bK = 0;
+			p->score = total_max_score; p->q_pos = best_q; p->t_pos = best_t;
+			ring_put(w, 0, best_t, best_q, 0, (uint32_t)total_max_score);
 			current_sms = 1;
-			c_t_offset = c_h->t_st;
+			c_t_offset = best_t;
 			continue;
 		}
 		if (total_max_score < max_score) { total_max_score = max_score; max_sms_id = current_sms - 1; best_t = cs.t_pos; best_q = cs.q_pos; }
@@ -3195,7 +3220,7 @@ struct ExtState { int total_max_score; uint32_t best_t, best_q, best_len; uint32
 template <int MODE>
 DV int ext_block(WCtxL &w, ExtState &e, const uint32_t n0, const uint32_t m, DsbChain *c_st, int chain_ID, DsbScHash *sc_hash, const uint32_t step_limit)
 {
-	const int lane = DSB_LANE; DsbSms *const sms = w.sms;
+	const int lane = DSB_LANE; DsbSms *const sms = DSB_UNI64(w.sms);
 	const bool mine = (uint32_t)lane < m;
 	DsbSms cs; cs.t_pos = cs.q_pos = cs.len = cs.score = 0;
 	if (mine) cs = sms[n0 + lane];
@@ -3204,14 +3229,14 @@ DV int ext_block(WCtxL &w, ExtState &e, const uint32_t n0, const uint32_t m, Dsb
 	const bool cand = mine && (int)cs.len >= 8 && combine_test(c_st, chain_ID, sc_hash, (int)(cs.t_pos - cs.q_pos), MODE == 2, (int)(MODE == 2 ? cs.q_pos + cs.len : cs.q_pos));
 	const uint64_t cmask = dsb_ballot64(cand);
 	wave_sync();                                                // (the scores: the next block's old predecessors)
-	if (w.status & DSB_ST_HEAVY) { e.steps = step_limit; }        // the read is being handed over (DSB_HEAVY_CHECK)
+	if (DSB_UNI(w.status) & DSB_ST_HEAVY) { e.steps = step_limit; }        // the read is being handed over (DSB_HEAVY_CHECK)
 	DSB_BOOST_IF_HEAVY(w);
 	for (uint32_t j = 0; j < m; j++) {
 		if (++e.steps > step_limit) { w.status |= DSB_ST_TIMEOUT; return DSB_EXT_STOP; }
 		const int s_j = dsb_shfl(sc, (int)j); const uint32_t t_j = dsb_shfl(cs.t_pos, (int)j);
 		if ((cmask >> j) & 1ULL) {
 			const uint32_t q_j = dsb_shfl(cs.q_pos, (int)j), l_j = dsb_shfl(cs.len, (int)j);
-			if (combine_chain(c_st, chain_ID, sc_hash, (int)(t_j - q_j), MODE == 2, (int)(MODE == 2 ? q_j + l_j : q_j), &e.combined)) { e.merge_score = s_j; e.merge_len = l_j; return DSB_EXT_MERGED; }
+			if (DSB_UNI(combine_chain(c_st, chain_ID, sc_hash, (int)(t_j - q_j), MODE == 2, (int)(MODE == 2 ? q_j + l_j : q_j), &e.combined))) { e.combined = DSB_UNI64(e.combined); e.merge_score = s_j; e.merge_len = l_j; return DSB_EXT_MERGED; }
 		}
 		if (e.total_max_score < s_j) { e.total_max_score = s_j; e.best_t = t_j; e.best_q = dsb_shfl(cs.q_pos, (int)j); e.best_len = dsb_shfl(cs.len, (int)j); }
 		if (MODE == 1 ? (t_j > e.best_t + 1000) : (t_j + 1000 < e.best_t)) return DSB_EXT_STOP;
@@ -3223,22 +3248,29 @@ DV int ext_block(WCtxL &w, ExtState &e, const uint32_t n0, const uint32_t m, Dsb
 DN int sdp_right_M2(WCtxL &w, const uint8_t *q_str, int tbl, int key_len, DsbChain *c_st, int chain_ID, uint32_t l_read, DsbScHash *sc_hash, int score_ori)
 {
 	DsbXP x = w.x;
-	score_ori += 10000;
+	// (everything the loop below branches on is the wavefront's: arguments, context and chain fields go through DSB_UNI once, the loop's
+	// own state -- e.*, n_sms, current_sms, c_t_offset, ch_q_st / ch_q_ed, score_ori, last_search -- is then made of scalar values only,
+	// and what a call hands back from memory is DSB_UNI again)
+	q_str = DSB_UNI64(q_str); tbl = DSB_UNI(tbl); c_st = DSB_UNI64(c_st); chain_ID = DSB_UNI(chain_ID); l_read = DSB_UNI(l_read); sc_hash = DSB_UNI64(sc_hash);
+	score_ori = DSB_UNI(score_ori) + 10000;
 	DsbChain *c_h = c_st + chain_ID;
 	w.n_sms = 0;
-	uint8_t *ref = w.win_right;
+	uint8_t *ref = DSB_UNI64(w.win_right);
 	fill_window(w, ref, 1000 + 128);
 	wave_sync();
 	DsbSms *p = push_sms(w);
-	p->score = score_ori; p->q_pos = c_h->q_ed; p->t_pos = c_h->t_ed; p->len = 1 - 9;
-	ExtState e; e.total_max_score = score_ori; e.best_t = c_h->t_ed; e.best_q = c_h->q_ed; e.best_len = (uint32_t)(1 - 9);     // fields of the best node so far (node 0)
-	e.steps = w.steps; e.combined = nullptr; e.merge_score = 0; e.merge_len = 0;
+	const uint32_t ch_t_ed0 = DSB_UNI(c_h->t_ed), ch_q_ed0 = DSB_UNI(c_h->q_ed);
+	p->score = score_ori; p->q_pos = ch_q_ed0; p->t_pos = ch_t_ed0; p->len = 1 - 9;
+	ExtState e; e.total_max_score = score_ori; e.best_t = ch_t_ed0; e.best_q = ch_q_ed0; e.best_len = (uint32_t)(1 - 9);     // fields of the best node so far (node 0)
+	e.steps = DSB_UNI(w.steps); e.combined = nullptr; e.merge_score = 0; e.merge_len = 0;
 	uint32_t current_sms = 1, n_sms = 1;
-	uint64_t t_offset_global = x->refinfo[c_h->ref_ID].seq_offset, t_length = x->refinfo[c_h->ref_ID].seq_l;
-	uint32_t c_t_offset = c_h->t_ed - 3;
+	const uint32_t ref_ID = DSB_UNI(c_h->ref_ID);
+	uint64_t t_offset_global = DSB_UNI64(x->refinfo[ref_ID].seq_offset), t_length = DSB_UNI64(x->refinfo[ref_ID].seq_l);
+	const uint8_t *const refbin = DSB_UNI64(x->refbin); const uint64_t ref_bases = DSB_UNI64(x->ref_bases);
+	uint32_t c_t_offset = ch_t_ed0 - 3;
 	int last_search = false;
-	uint32_t ch_q_st = c_h->q_st, ch_q_ed = c_h->q_ed;       // (they change when a chain is combined in: read again there)
-	const uint32_t step_limit = w.step_limit; DsbSms *const sms = w.sms;
+	uint32_t ch_q_st = DSB_UNI(c_h->q_st), ch_q_ed = ch_q_ed0;       // (they change when a chain is combined in: read again there)
+	const uint32_t step_limit = DSB_UNI(w.step_limit); DsbSms *const sms = DSB_UNI64(w.sms);
 	wave_sync();
 	while (1) {
 		if (++e.steps > step_limit) { w.status |= DSB_ST_TIMEOUT; break; }
@@ -3252,7 +3284,7 @@ DN int sdp_right_M2(WCtxL &w, const uint8_t *q_str, int tbl, int key_len, DsbCha
 				max_search_ref = l_read - ch_q_ed + 60;
 			} else max_search_ref = t_length - c_t_offset;
 			max_search_ref = MINV(600u, max_search_ref);
-			get_ref_wave(x->refbin, x->ref_bases, DSB_LANE, ref, c_t_offset + t_offset_global, max_search_ref + 50); cnt_add(Cnt{w.k.c, 1u}, 3, max_search_ref + 50);
+			get_ref_wave(refbin, ref_bases, DSB_LANE, ref, c_t_offset + t_offset_global, max_search_ref + 50); cnt_add(Cnt{w.k.c, 1u}, 3, max_search_ref + 50);
 			wave_sync();
 			int search_q_ed = (int)e.best_q + 1000;
 			search_q_ed = MINV((uint32_t)search_q_ed, l_read);
@@ -3261,27 +3293,28 @@ DN int sdp_right_M2(WCtxL &w, const uint8_t *q_str, int tbl, int key_len, DsbCha
 			sdp_match(w, search_q_st, search_q_ed, q_str, ref, max_search_ref, key_len, tbl, c_t_offset, true);
 			SUB1(w, 10);
 			c_t_offset += max_search_ref - 9 - 3;
-			n_sms = w.n_sms;
+			n_sms = DSB_UNI(w.n_sms);
 			if (n_sms == current_sms) break;
-			if (sms[current_sms].t_pos > e.best_t + 1000) break;
+			if (DSB_UNI(sms[current_sms].t_pos) > e.best_t + 1000) break;
 		}
 		const uint32_t m = MINV((uint32_t)DSB_WAVE, n_sms - current_sms);
 		SUB0(w);
-		const int how = ext_block<1>(w, e, current_sms, m, c_st, chain_ID, sc_hash, step_limit);
+		const int how = DSB_UNI(ext_block<1>(w, e, current_sms, m, c_st, chain_ID, sc_hash, step_limit));
 		SUB1(w, 11);
 		if (how == DSB_EXT_STOP) break;
 		if (how == DSB_EXT_MERGED) {
 			w.steps = e.steps;
-			e.total_max_score = MAXV(score_ori, e.merge_score) - (int)e.merge_len + sdp_middle_M2(w, e.combined->cur, q_str, tbl, key_len);
-			e.steps = w.steps;
-			ch_q_st = c_h->q_st; ch_q_ed = c_h->q_ed;
+			e.total_max_score = MAXV(score_ori, e.merge_score) - (int)e.merge_len + DSB_UNI(sdp_middle_M2(w, DSB_UNI(e.combined->cur), q_str, tbl, key_len));
+			e.steps = DSB_UNI(w.steps);
+			ch_q_st = DSB_UNI(c_h->q_st); ch_q_ed = DSB_UNI(c_h->q_ed);
 			score_ori = e.total_max_score;
 			w.n_sms = 0;
 			p = push_sms(w); n_sms = 1;
-			p->score = e.total_max_score; p->q_pos = c_h->q_ed; p->t_pos = c_h->t_ed; p->len = -9;
-			e.best_t = c_h->t_ed; e.best_q = c_h->q_ed; e.best_len = (uint32_t)(-9);
+			const uint32_t ch_t_ed = DSB_UNI(c_h->t_ed);
+			p->score = e.total_max_score; p->q_pos = ch_q_ed; p->t_pos = ch_t_ed; p->len = -9;
+			e.best_t = ch_t_ed; e.best_q = ch_q_ed; e.best_len = (uint32_t)(-9);
 			current_sms = 1;
-			c_t_offset = c_h->t_ed;
+			c_t_offset = ch_t_ed;
 			wave_sync();
 			continue;
 		}
@@ -3297,22 +3330,26 @@ DN int sdp_right_M2(WCtxL &w, const uint8_t *q_str, int tbl, int key_len, DsbCha
 DN int sdp_left_M2(WCtxL &w, const uint8_t *q_str, int tbl, int key_len, DsbChain *c_st, int chain_ID, uint32_t l_read, DsbScHash *sc_hash, int score_ori)
 {
 	DsbXP x = w.x;
-	score_ori += 10000;
+	// (scalar values only in the loop's state, as in sdp_right_M2)
+	q_str = DSB_UNI64(q_str); tbl = DSB_UNI(tbl); c_st = DSB_UNI64(c_st); chain_ID = DSB_UNI(chain_ID); sc_hash = DSB_UNI64(sc_hash);
+	score_ori = DSB_UNI(score_ori) + 10000;
 	DsbChain *c_h = c_st + chain_ID;
 	w.n_sms = 0;
-	uint8_t *ref = w.win_left;
+	uint8_t *ref = DSB_UNI64(w.win_left);
 	fill_window(w, ref, 1000 + 128);
 	wave_sync();
 	DsbSms *p = push_sms(w);
-	p->score = score_ori; p->q_pos = c_h->q_st; p->t_pos = c_h->t_st; p->len = 0;          // (a[0].len is never read by the left DP)
-	ExtState e; e.total_max_score = score_ori; e.best_t = c_h->t_st; e.best_q = c_h->q_st; e.best_len = 0;
-	e.steps = w.steps; e.combined = nullptr; e.merge_score = 0; e.merge_len = 0;
+	const uint32_t ch_t_st0 = DSB_UNI(c_h->t_st), ch_q_st0 = DSB_UNI(c_h->q_st);
+	p->score = score_ori; p->q_pos = ch_q_st0; p->t_pos = ch_t_st0; p->len = 0;          // (a[0].len is never read by the left DP)
+	ExtState e; e.total_max_score = score_ori; e.best_t = ch_t_st0; e.best_q = ch_q_st0; e.best_len = 0;
+	e.steps = DSB_UNI(w.steps); e.combined = nullptr; e.merge_score = 0; e.merge_len = 0;
 	uint32_t current_sms = 1, n_sms = 1;
-	uint64_t t_offset_global = x->refinfo[c_h->ref_ID].seq_offset;
-	uint32_t c_t_offset = c_h->t_st + 3;
+	uint64_t t_offset_global = DSB_UNI64(x->refinfo[DSB_UNI(c_h->ref_ID)].seq_offset);
+	const uint8_t *const refbin = DSB_UNI64(x->refbin); const uint64_t ref_bases = DSB_UNI64(x->ref_bases);
+	uint32_t c_t_offset = ch_t_st0 + 3;
 	int last_search = false;
-	uint32_t ch_q_st = c_h->q_st;                             // (changes when a chain is combined in: read again there)
-	const uint32_t step_limit = w.step_limit; DsbSms *const sms = w.sms;
+	uint32_t ch_q_st = ch_q_st0;                              // (changes when a chain is combined in: read again there)
+	const uint32_t step_limit = DSB_UNI(w.step_limit); DsbSms *const sms = DSB_UNI64(w.sms);
 	wave_sync();
 	while (1) {
 		if (++e.steps > step_limit) { w.status |= DSB_ST_TIMEOUT; break; }
@@ -3327,9 +3364,9 @@ DN int sdp_left_M2(WCtxL &w, const uint8_t *q_str, int tbl, int key_len, DsbChai
 			} else max_search_ref = c_t_offset;
 			max_search_ref = MINV(600u, max_search_ref);
 			if (t_offset_global == 0 && c_t_offset < 50 + max_search_ref)
-				{ get_ref_wave(x->refbin, x->ref_bases, DSB_LANE, ref, (int64_t)(c_t_offset + t_offset_global - max_search_ref), max_search_ref); cnt_add(Cnt{w.k.c, 1u}, 3, max_search_ref); }
+				{ get_ref_wave(refbin, ref_bases, DSB_LANE, ref, (int64_t)(c_t_offset + t_offset_global - max_search_ref), max_search_ref); cnt_add(Cnt{w.k.c, 1u}, 3, max_search_ref); }
 			else
-				{ get_ref_wave(x->refbin, x->ref_bases, DSB_LANE, ref, (int64_t)(c_t_offset + t_offset_global - max_search_ref - 50), max_search_ref + 50); cnt_add(Cnt{w.k.c, 1u}, 3, max_search_ref + 50); }
+				{ get_ref_wave(refbin, ref_bases, DSB_LANE, ref, (int64_t)(c_t_offset + t_offset_global - max_search_ref - 50), max_search_ref + 50); cnt_add(Cnt{w.k.c, 1u}, 3, max_search_ref + 50); }
 			wave_sync();
 			int search_q_st = (int)e.best_q - 1000;
 			search_q_st = MAXV(search_q_st, 0);
@@ -3338,27 +3375,28 @@ DN int sdp_left_M2(WCtxL &w, const uint8_t *q_str, int tbl, int key_len, DsbChai
 			sdp_match(w, search_q_st, search_q_ed, q_str, ref + 50, max_search_ref, key_len, tbl, c_t_offset - max_search_ref, false);
 			TX1(w, 3, t_lm);
 			c_t_offset = c_t_offset - max_search_ref + 9 + 3;
-			n_sms = w.n_sms;
+			n_sms = DSB_UNI(w.n_sms);
 			if (n_sms == current_sms) break;
-			if (sms[current_sms].t_pos + 1000 < e.best_t) break;
+			if (DSB_UNI(sms[current_sms].t_pos) + 1000 < e.best_t) break;
 		}
 		const uint32_t m = MINV((uint32_t)DSB_WAVE, n_sms - current_sms);
 		TX0(w, t_ld);
-		const int how = ext_block<2>(w, e, current_sms, m, c_st, chain_ID, sc_hash, step_limit);
+		const int how = DSB_UNI(ext_block<2>(w, e, current_sms, m, c_st, chain_ID, sc_hash, step_limit));
 		TX1(w, 4, t_ld);
 		if (how == DSB_EXT_STOP) break;
 		if (how == DSB_EXT_MERGED) {
 			w.steps = e.steps;
-			e.total_max_score = MAXV(score_ori, e.merge_score) - (int)e.merge_len + sdp_middle_M2(w, e.combined->cur, q_str, tbl, key_len);
-			e.steps = w.steps;
-			ch_q_st = c_h->q_st;
+			e.total_max_score = MAXV(score_ori, e.merge_score) - (int)e.merge_len + DSB_UNI(sdp_middle_M2(w, DSB_UNI(e.combined->cur), q_str, tbl, key_len));
+			e.steps = DSB_UNI(w.steps);
+			ch_q_st = DSB_UNI(c_h->q_st);
 			score_ori = e.total_max_score;
 			w.n_sms = 0;
 			p = push_sms(w); n_sms = 1;
-			p->score = e.total_max_score; p->q_pos = c_h->q_st; p->t_pos = c_h->t_st; p->len = 0;
-			e.best_t = c_h->t_st; e.best_q = c_h->q_st;
+			const uint32_t ch_t_st = DSB_UNI(c_h->t_st);
+			p->score = e.total_max_score; p->q_pos = ch_q_st; p->t_pos = ch_t_st; p->len = 0;
+			e.best_t = ch_t_st; e.best_q = ch_q_st;
 			current_sms = 1;
-			c_t_offset = c_h->t_st;
+			c_t_offset = ch_t_st;
 			wave_sync();
 			continue;
 		}
@@ -3384,13 +3422,16 @@ DN void get_score_M2(WCtxL &w, SDirL *sd, uint32_t l_read, DsbScHash *sc_hash)
 	int key_len = 0;
 	MARK(w, 51);
 	TICK(w, 4);
-	DsbChain *H = w.hit;
-	for (uint32_t i = 0; i < w.n_hit; i++) {
-		if (H[i].sum_score == 0) continue;
-		SDirL *csd = ((sd->direction == H[i].direction) ? 0 : 1) + sd;
-		int tbl = (H[i].direction == D_FORWARD) ? 0 : 1;
+	DsbChain *H = DSB_UNI64(w.hit);
+	l_read = DSB_UNI(l_read); sc_hash = DSB_UNI64(sc_hash);
+	const uint32_t n_hit = DSB_UNI(w.n_hit);                 // (a merged chain stays in the list with sum_score 0: the count does not change here)
+	for (uint32_t i = 0; i < n_hit; i++) {
+		if (DSB_UNI(H[i].sum_score) == 0) continue;
+		const uint32_t dir = DSB_UNI(H[i].direction);
+		SDirL *csd = ((DSB_UNI(sd->direction) == dir) ? 0 : 1) + sd;
+		int tbl = (dir == D_FORWARD) ? 0 : 1;
 		MARK(w, 52);
-		int score = sdp_middle_M2(w, H[i].cur, csd->bin_read, tbl, key_len);
+		int score = DSB_UNI(sdp_middle_M2(w, DSB_UNI(H[i].cur), csd->bin_read, tbl, key_len));
 		MARK(w, 53);
 		TICK(w, 5);
 		score = DSB_EXT_MW(MW) ? sdp_right_M2_mw(w, csd->bin_read, tbl, key_len, H, i, l_read, sc_hash, score) : sdp_right_M2(w, csd->bin_read, tbl, key_len, H, i, l_read, sc_hash, score);

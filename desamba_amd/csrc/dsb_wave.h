@@ -7,7 +7,10 @@
 // Contract of the cross-lane operations (the 64-lane emulation checks it): wave_sync, grp_first, grp_max_i, grp_excl_scan_u,
 // dsb_ballot64, dsb_shfl, dsb_shfl_var and dsb_shfl_up1 are called by ALL 64 lanes from wave-uniform control flow.  DSB_RFL
 // (v_readfirstlane) may stand in a section that only some lanes run: it returns the value of the first lane that is there,
-// and is only ever used on values that are the same in all of them.
+// and is only ever used on values that are the same in all of them.  DSB_UNI / DSB_UNI64 (dsb_classify_dev.h) are DSB_RFL / DSB_RFL64 with
+// the value's type kept, under the name of what they promise -- "all lanes that are here hold this value", so that it lives in a scalar
+// register and its tests are scalar branches; a checking build of the 64-lane emulation (tests/emu/dsb_uni_check.h) defines them itself and
+// compares the value across those lanes.
 
 // ---- function qualifiers, group width ----------------------------------------------------------------------------------
 #define DV __device__ __forceinline__
