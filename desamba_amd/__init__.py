@@ -125,6 +125,17 @@ REF_IDENTITY_FIELDS = ("records", "q_bases", "t_bases", "edits", "exact", "unali
 REF_IDENTITY_DTYPE = [(f, "<u8") for f in REF_IDENTITY_FIELDS]
 
 
+class DsbHitAlignment(C.Structure):
+    _fields_ = [("ops_off", C.c_uint64), ("n_ops", C.c_uint32), ("n_x", C.c_uint32), ("n_ins", C.c_uint32), ("n_del", C.c_uint32),
+                ("flags", C.c_uint32), ("pad", C.c_uint32)]
+
+
+DSB_ALN_OPS, DSB_ALN_NOTRACE, DSB_ALN_NOROOM, DSB_ALN_UNALIGNED = 1, 2, 4, 8
+DSB_ALN_OP_I, DSB_ALN_OP_D, DSB_ALN_OP_EQ, DSB_ALN_OP_X = 1, 2, 7, 8
+DSB_ALN_TRACE_KIB_DEFAULT, DSB_ALN_TRACE_KIB_MAX = 2048, 65536
+HIT_ALIGNMENT_DTYPE = [("ops_off", "<u8"), ("n_ops", "<u4"), ("n_x", "<u4"), ("n_ins", "<u4"), ("n_del", "<u4"), ("flags", "<u4"), ("pad", "<u4")]
+
+
 class DsbChunk(C.Structure):
     _fields_ = [("start", C.c_uint64), ("end", C.c_uint64), ("hist_max_before", C.c_uint32), ("rank", C.c_int32)]
 
@@ -146,7 +157,9 @@ EXPORTS = ["dsb_index_open", "dsb_index_close", "dsb_index_n_ref", "dsb_index_re
            "dsb_ctx_enable_lca", "dsb_ctx_reset_lca", "dsb_batch_lca", "dsb_ctx_lca_counts", "dsb_multi_enable_lca", "dsb_multi_lca",
            "dsb_multi_lca_counts", "dsb_taxnames_load", "dsb_taxnames_close", "dsb_format_kraken", "dsb_lca_report_format",
            "dsb_ctx_enable_identity", "dsb_ctx_reset_identity", "dsb_batch_identity", "dsb_ctx_identity", "dsb_multi_enable_identity",
-           "dsb_multi_identity", "dsb_multi_ref_identity", "dsb_format_identity", "dsb_identity_format", "dsb_index_ref_bases", "dsb_ctx_edit_pairs"]
+           "dsb_multi_identity", "dsb_multi_ref_identity", "dsb_format_identity", "dsb_identity_format", "dsb_index_ref_bases", "dsb_ctx_edit_pairs",
+           "dsb_ctx_enable_alignment", "dsb_batch_alignment", "dsb_multi_enable_alignment", "dsb_multi_alignment", "dsb_ctx_align_pairs",
+           "dsb_format_aligned_sam", "dsb_aligned_sam_header"]
 
 _lib = None
 
@@ -259,6 +272,14 @@ def lib():
     L.dsb_identity_format.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]; L.dsb_identity_format.restype = C.c_long
     L.dsb_index_ref_bases.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p]
     L.dsb_ctx_edit_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.dsb_ctx_enable_alignment.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint64]
+    L.dsb_batch_alignment.argtypes = [C.c_void_p, C.POINTER(C.POINTER(DsbHitAlignment)), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint64)]
+    L.dsb_multi_enable_alignment.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint64]
+    L.dsb_multi_alignment.argtypes = [C.c_void_p, C.POINTER(C.POINTER(DsbHitAlignment)), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint64)]
+    L.dsb_ctx_align_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.dsb_format_aligned_sam.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]; L.dsb_format_aligned_sam.restype = C.c_long
+    L.dsb_aligned_sam_header.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]; L.dsb_aligned_sam_header.restype = C.c_long
     L.dsb_strerror.argtypes = [C.c_int]; L.dsb_strerror.restype = C.c_char_p
     L.dsb_version.restype = C.c_char_p
     _lib = L
@@ -600,6 +621,41 @@ class Ctx:
             raise DsbError(rc, "dsb_ctx_edit_pairs")
         return out
 
+    def enable_alignment(self, on=True, trace_kib=0, ops_cap=0):
+        """base-level alignment of every counted record from now on (needs enable_identity; uses its band and cap), or off (freed).
+        trace_kib: KiB of trace per wavefront, 1 .. 65536 [2048]; ops_cap: operations the batch's array holds [0: sized per batch]"""
+        rc = lib().dsb_ctx_enable_alignment(self.h, 1 if on else 0, int(trace_kib) if on else 0, int(ops_cap) if on else 0)
+        if rc != 0:
+            raise DsbError(rc, "dsb_ctx_enable_alignment")
+
+    def alignment(self, n_hits):
+        """(records, ops) of the last batch: one record per hit (HIT_ALIGNMENT_DTYPE) and the uint32 operation array they index"""
+        return _alignment(lib().dsb_batch_alignment, self.h, int(n_hits), "dsb_batch_alignment")
+
+    def align_pairs(self, q_codes, q_off, q_len, t_codes, t_off, t_len, band=DSB_IDENT_BAND_DEFAULT, max_permille=DSB_IDENT_PERMILLE_DEFAULT,
+                    trace_kib=DSB_ALN_TRACE_KIB_DEFAULT, ops_cap=None):
+        """dsb_ctx_align_pairs: edit_pairs with the path kept; returns (identity records, alignment records, ops).  ops_cap: room of
+        the operation array [None: an operation per base of Q and T plus one per pair -- never short]"""
+        import numpy as np
+        qc = np.ascontiguousarray(q_codes, dtype=np.uint8); tc = np.ascontiguousarray(t_codes, dtype=np.uint8)
+        qo = np.ascontiguousarray(q_off, dtype=np.uint64); to = np.ascontiguousarray(t_off, dtype=np.uint64)
+        ql = np.ascontiguousarray(q_len, dtype=np.uint32); tl = np.ascontiguousarray(t_len, dtype=np.uint32)
+        n = len(qo)
+        if not (len(to) == len(ql) == len(tl) == n):
+            raise ValueError("align_pairs: the four offset and length arrays differ in length")
+        if n and (int((qo + ql).max()) > len(qc) or int((to + tl).max()) > len(tc)):
+            raise ValueError("align_pairs: a pair reaches beyond its codes")
+        if ops_cap is None:
+            ops_cap = 2 * (int(ql.astype(np.uint64).sum()) + int(tl.astype(np.uint64).sum())) + n    # (2 edits + 1 <= 2 max(n, m) + 1 per pair)
+        ident = np.zeros(n, dtype=HIT_IDENTITY_DTYPE); aln = np.zeros(n, dtype=HIT_ALIGNMENT_DTYPE); ops = np.zeros(max(int(ops_cap), 1), dtype=np.uint32)
+        used = C.c_uint64(0)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        rc = lib().dsb_ctx_align_pairs(self.h, p(qc), p(qo), p(ql), p(tc), p(to), p(tl), n, int(band), int(max_permille), int(trace_kib),
+                                       p(ident), p(aln), p(ops), int(ops_cap), C.byref(used))
+        if rc != 0:
+            raise DsbError(rc, "dsb_ctx_align_pairs")
+        return ident, aln, ops[:used.value]
+
     def in_last_batch(self):
         return self.ran[1]
 
@@ -742,6 +798,16 @@ class Multi:
     def ref_identity(self):
         """Ctx.ref_identity added over the contexts"""
         return _ref_identity(lib().dsb_multi_ref_identity, self.h, self.index.n_ref, "dsb_multi_ref_identity")
+
+    def enable_alignment(self, on=True, trace_kib=0, ops_cap=0):
+        """Ctx.enable_alignment on every context"""
+        rc = lib().dsb_multi_enable_alignment(self.h, 1 if on else 0, int(trace_kib) if on else 0, int(ops_cap) if on else 0)
+        if rc != 0:
+            raise DsbError(rc, "dsb_multi_enable_alignment")
+
+    def alignment(self, n_hits):
+        """Ctx.alignment for the last classify(): one record per hit of its result, ops_off rebased into the one array"""
+        return _alignment(lib().dsb_multi_alignment, self.h, int(n_hits), "dsb_multi_alignment")
 
     def taxa(self, records=False):
         """Ctx.taxa for the last classify(), in input order"""
@@ -936,6 +1002,59 @@ def _ref_identity(fn, h, n_ref, what):
     if rc != 0:
         raise DsbError(rc, what)
     return out
+
+
+def _alignment(fn, h, n_hits, what):
+    import numpy as np
+    pr = C.POINTER(DsbHitAlignment)(); po = C.POINTER(C.c_uint32)(); n = C.c_uint64(0)
+    rc = fn(h, C.byref(pr), C.byref(po), C.byref(n))
+    if rc != 0:
+        raise DsbError(rc, what)
+    recs = np.zeros(n_hits, dtype=HIT_ALIGNMENT_DTYPE); ops = np.zeros(n.value, dtype=np.uint32)
+    if n_hits:
+        C.memmove(recs.ctypes.data, pr, n_hits * C.sizeof(DsbHitAlignment))
+    if n.value:
+        C.memmove(ops.ctypes.data, po, n.value * 4)
+    return recs, ops
+
+
+def aligned_sam_header(index):
+    """dsb_aligned_sam_header: @HD, one @SQ per reference, @PG (bytes)"""
+    cap = 1 << 16
+    while True:
+        buf = C.create_string_buffer(cap)
+        n = lib().dsb_aligned_sam_header(index.h, buf, cap)
+        if n >= 0:
+            return buf.raw[:n]
+        cap *= 4
+
+
+def format_aligned_sam(index, reads, res, ident, aln, ops):
+    """dsb_format_aligned_sam over a batch: the SAM lines (bytes) of make_reads()'s array, its result, Ctx/Multi.identity()'s records
+    and Ctx/Multi.alignment()'s records and operations"""
+    import numpy as np
+    ident = np.ascontiguousarray(ident, dtype=HIT_IDENTITY_DTYPE); aln = np.ascontiguousarray(aln, dtype=HIT_ALIGNMENT_DTYPE)
+    ops = np.ascontiguousarray(ops, dtype=np.uint32)
+    if len(ident) != res.n_hits or len(aln) != res.n_hits:
+        raise ValueError("format_aligned_sam: %d and %d records for %d hits" % (len(ident), len(aln), res.n_hits))
+    if len(aln) and int((aln["ops_off"] + aln["n_ops"])[aln["n_ops"] > 0].max(initial=0)) > len(ops):
+        raise ValueError("format_aligned_sam: a record reaches beyond the operations")
+    out = []
+    for i in range(len(reads)):
+        rr = res.reads[i]
+        hits = C.byref(res.hits.contents, rr.first * C.sizeof(DsbHit)) if rr.n else None
+        idp = ident[rr.first:rr.first + rr.n].ctypes.data_as(C.c_void_p) if rr.n else None
+        alp = aln[rr.first:rr.first + rr.n].ctypes.data_as(C.c_void_p) if rr.n else None
+        cap = 1024 + (2 * reads[i].len + len(reads[i].name) + 256) * (rr.n + 1) + 12 * int(aln["n_ops"][rr.first:rr.first + rr.n].sum())
+        while True:
+            buf = C.create_string_buffer(cap)
+            n = lib().dsb_format_aligned_sam(index.h, C.byref(reads[i]), C.byref(rr), hits, idp, alp, ops.ctypes.data_as(C.c_void_p), buf, cap)
+            if n >= 0:
+                out.append(buf.raw[:n]); break
+            if cap > (1 << 28):
+                raise DsbError(DSB_EINVAL, "dsb_format_aligned_sam")
+            cap *= 4
+    return b"".join(out)
 
 
 def format_identity(index, reads, res, ident):

@@ -63,7 +63,9 @@ typedef struct {
 	dsb_read_result *rr; dsb_hit *hits; size_t cap_rr, cap_hits, n_hits;
 	dsb_read_taxon *taxa; size_t cap_taxa;            /* --report: the device's per-read taxa of the batch */
 	dsb_read_lca *lca; size_t cap_lca;                /* --kraken-out / --kraken-report: the device's per-read LCA records of the batch */
-	dsb_hit_identity *ident; size_t cap_ident;        /* --identity: the device's per-hit identity records of the batch (parallel to hits) */
+	dsb_hit_identity *ident; size_t cap_ident;        /* --identity, --cigar-sam: the device's per-hit identity records of the batch (parallel to hits) */
+	dsb_hit_alignment *aln; size_t cap_aln;           /* --cigar-sam: the device's per-hit alignment records (parallel to hits) and the operations they index */
+	uint32_t *aln_ops; size_t cap_aln_ops;
 } batch_t;
 
 typedef struct { batch_t *slot[N_BATCH + 2]; int head, n, closed; pthread_mutex_t mu; pthread_cond_t cv; } queue_t;
@@ -139,6 +141,8 @@ typedef struct {
 	int lca_on; FILE *kr_out;
 	/* --identity / --identity-refs: per-hit edit distance on; the per-record lines are written by the writer in input order */
 	int ident_on; FILE *id_out;
+	/* --cigar-sam: base-level alignment on; the SAM lines are written by the writer in input order */
+	FILE *cg_out;
 	/* --abundance-reads: each batch runs under the input index of its first read, and the writer keeps every read's
 	 * QNAME, NUL-terminated, in input order, for the lines written when the run ends */
 	int keep_names; char *qnames; size_t qnames_len, qnames_cap;
@@ -777,11 +781,19 @@ static void *gpu_main(void *arg)
 				if (b->n > b->cap_lca) { b->cap_lca = b->n * 2; b->lca = xrealloc(b->lca, b->cap_lca * sizeof *b->lca); }
 				memcpy(b->lca, t, b->n * sizeof *b->lca);
 			}
-			if (a->id_out) {
+			if (a->id_out || a->cg_out) {
 				const dsb_hit_identity *t; int rt = dsb_batch_identity(ctx, &t);
 				if (rt) { fprintf(stderr, "[dsb_batch_identity] %s\n", dsb_strerror(rt)); exit(1); }
 				if (res.n_hits > b->cap_ident) { b->cap_ident = res.n_hits * 2; b->ident = xrealloc(b->ident, b->cap_ident * sizeof *b->ident); }
 				if (res.n_hits) memcpy(b->ident, t, res.n_hits * sizeof *b->ident);
+			}
+			if (a->cg_out) {
+				const dsb_hit_alignment *t; const uint32_t *ops; uint64_t n_ops; int rt = dsb_batch_alignment(ctx, &t, &ops, &n_ops);
+				if (rt) { fprintf(stderr, "[dsb_batch_alignment] %s\n", dsb_strerror(rt)); exit(1); }
+				if (res.n_hits > b->cap_aln) { b->cap_aln = res.n_hits * 2; b->aln = xrealloc(b->aln, b->cap_aln * sizeof *b->aln); }
+				if (n_ops > b->cap_aln_ops) { b->cap_aln_ops = (size_t)n_ops * 2; b->aln_ops = xrealloc(b->aln_ops, b->cap_aln_ops * sizeof *b->aln_ops); }
+				if (res.n_hits) memcpy(b->aln, t, res.n_hits * sizeof *b->aln);
+				if (n_ops) memcpy(b->aln_ops, ops, (size_t)n_ops * sizeof *b->aln_ops);
 			}
 			t_idle = now();
 		}
@@ -870,6 +882,22 @@ static void *writer_main(void *arg)
 				if (fwrite(ib, 1, (size_t)w, a->id_out) != (size_t)w) die("[classify] cannot write the per-record identities");
 			}
 		}
+		if (a->cg_out) {
+			/* the aligned SAM lines of the batch's counted records, from the device's records, in input order */
+			static char *cb; static size_t ccap;
+			for (size_t i = 0; i < b->n; i++) {
+				const dsb_read_result *rr = &b->rr[i];
+				size_t need = 1024 + (2 * (size_t)b->reads[i].len + strlen(b->reads[i].name) + 384) * ((size_t)rr->n + 1);
+				for (uint32_t k = 0; k < rr->n; k++) need += 12 * (size_t)b->aln[rr->first + k].n_ops;
+				if (need > ccap) { ccap = need * 2; cb = xrealloc(cb, ccap); }
+				long w;   /* (reference names are not bounded by the estimate: a buffer too small grows) */
+				while ((w = dsb_format_aligned_sam(a->idx, &b->reads[i], rr, b->hits + rr->first, b->ident + rr->first, b->aln + rr->first, b->aln_ops, cb, ccap)) < 0) {
+					if (ccap > ((size_t)1 << 32)) die("[dsb_format_aligned_sam] cannot format a record");
+					ccap *= 4; cb = xrealloc(cb, ccap);
+				}
+				if (fwrite(cb, 1, (size_t)w, a->cg_out) != (size_t)w) die("[classify] cannot write the aligned SAM");
+			}
+		}
 		if (a->keep_names)
 			for (size_t i = 0; i < b->n; i++) {
 				const size_t l = strlen(b->reads[i].name) + 1;
@@ -923,7 +951,11 @@ static void usage(void)
 	fprintf(stderr, "                     (flags: 1 the band did not matter, 2 over the edit cap, 4 lengths too different, 8 empty interval)\n");
 	fprintf(stderr, "    --identity-refs FILE  write records, bases, edits and identity per reference of those alignments into FILE when the run ends\n");
 	fprintf(stderr, "    --identity-band N  diagonals on either side of the corridor between the record's corners, 0 <= N <= 1024 [256]\n");
-	fprintf(stderr, "    --identity-max-frac F  stop aligning a record after F x its length edits (it is reported as over the cap), 0 < F <= 1 [0.3]\n\n");
+	fprintf(stderr, "    --identity-max-frac F  stop aligning a record after F x its length edits (it is reported as over the cap), 0 < F <= 1 [0.3]\n");
+	fprintf(stderr, "    --cigar-sam FILE  keep the path of those alignments and write FILE as SAM with a header: one line per primary and supplementary\n");
+	fprintf(stderr, "                     record with a base-level CIGAR (= X I D), 1-based POS, SEQ on the aligned strand and NM:i (--identity-band and\n");
+	fprintf(stderr, "                     --identity-max-frac apply; a record without a path has CIGAR * and xa:i:<flags>)\n");
+	fprintf(stderr, "    --cigar-trace-kib N  KiB of trace per wavefront, 1 <= N <= 65536 [2048]; a record whose edits need more gets no path\n\n");
 }
 
 static double now(void) { struct timeval tv; gettimeofday(&tv, NULL); return tv.tv_sec + tv.tv_usec * 1e-6; }
@@ -997,10 +1029,12 @@ static int classify_main(int argc, char **argv)
 	                                              {"coverage-windows", required_argument, NULL, 12}, {"coverage-window-size", required_argument, NULL, 13},
 	                                              {"identity", required_argument, NULL, 14}, {"identity-refs", required_argument, NULL, 15},
 	                                              {"identity-band", required_argument, NULL, 16}, {"identity-max-frac", required_argument, NULL, 17},
+	                                              {"cigar-sam", required_argument, NULL, 18}, {"cigar-trace-kib", required_argument, NULL, 19},
 	                                              {NULL, 0, NULL, 0}};
 	const char *tax_path = NULL, *rep_path[2] = {NULL, NULL}, *cov_path = NULL, *ab_path = NULL, *kr_path = NULL, *krep_path = NULL, *names_path = NULL, *abr_path = NULL, *covw_path = NULL;
 	uint32_t ab_permille = 950, lca_permille = 950, cov_window = 1000; int lca_frac_set = 0, cov_window_set = 0;
 	const char *id_path = NULL, *idr_path = NULL; uint32_t id_band = DSB_IDENT_BAND_DEFAULT, id_permille = DSB_IDENT_PERMILLE_DEFAULT; int id_opt_set = 0;
+	const char *cig_path = NULL; uint32_t cig_trace_kib = DSB_ALN_TRACE_KIB_DEFAULT; int cig_opt_set = 0;
 	while ((c = getopt_long(argc, argv, "ht:l:r:f:o:s:g:", long_opts, NULL)) >= 0) {
 		if (c == 'h') { usage(); return 0; }
 		else if (c == 1) tax_path = optarg;
@@ -1039,6 +1073,12 @@ static int classify_main(int argc, char **argv)
 			if (e == optarg || *e || !(f > 0 && f <= 1) || f * 1000 + 0.5 < 1) die("[classify] --identity-max-frac takes a number F with 0 < F <= 1 (steps of 0.001)");
 			id_permille = (uint32_t)(f * 1000 + 0.5); id_opt_set = 1;
 		}
+		else if (c == 18) cig_path = optarg;
+		else if (c == 19) {
+			char *e; const long long v = strtoll(optarg, &e, 10);
+			if (e == optarg || *e || v < 1 || v > DSB_ALN_TRACE_KIB_MAX) die("[classify] --cigar-trace-kib takes a number of KiB N with 1 <= N <= 65536");
+			cig_trace_kib = (uint32_t)v; cig_opt_set = 1;
+		}
 		else if (c == '?' && optopt == 11) die("[classify] --abundance-reads takes a file name");   /* (last on the line: getopt_long found no argument) */
 		else if (c == 't') { /* thread count: accepted for compatibility, unused */ }
 		else if (c == 'l') a.o.L_min_matching = atoi(optarg);
@@ -1075,9 +1115,10 @@ static int classify_main(int argc, char **argv)
 	if ((rep_path[0] || rep_path[1]) && !tax_path) die("[classify] --report and --report-base need --taxonomy nodes.dmp");
 	if ((kr_path || krep_path || names_path || lca_frac_set) && !tax_path) die("[classify] --kraken-out, --kraken-report, --names and --lca-min-frac need --taxonomy nodes.dmp");
 	if (cov_window_set && !covw_path) die("[classify] --coverage-window-size needs --coverage-windows FILE");
-	if (id_opt_set && !id_path && !idr_path) die("[classify] --identity-band and --identity-max-frac need --identity FILE or --identity-refs FILE");
+	if (id_opt_set && !id_path && !idr_path && !cig_path) die("[classify] --identity-band and --identity-max-frac need --identity FILE, --identity-refs FILE or --cigar-sam FILE");
+	if (cig_opt_set && !cig_path) die("[classify] --cigar-trace-kib needs --cigar-sam FILE");
 	a.lca_on = kr_path || krep_path;
-	a.ident_on = id_path || idr_path;
+	a.ident_on = id_path || idr_path || cig_path;
 	dsb_taxnames *names = NULL;
 	if (tax_path) {
 		int rt = dsb_taxonomy_load(tax_path, &a.tx);
@@ -1094,6 +1135,7 @@ static int classify_main(int argc, char **argv)
 	FILE *idr_out = NULL;
 	if (id_path && !(a.id_out = fopen(id_path, "w"))) { fprintf(stderr, "[xopen] fail to open file '%s'\n", id_path); exit(1); }
 	if (idr_path && !(idr_out = fopen(idr_path, "w"))) { fprintf(stderr, "[xopen] fail to open file '%s'\n", idr_path); exit(1); }
+	if (cig_path && !(a.cg_out = fopen(cig_path, "w"))) { fprintf(stderr, "[xopen] fail to open file '%s'\n", cig_path); exit(1); }
 	FILE *cov_out = NULL;
 	if (cov_path && !(cov_out = fopen(cov_path, "w"))) { fprintf(stderr, "[xopen] fail to open file '%s'\n", cov_path); exit(1); }
 	FILE *covw_out = NULL;
@@ -1123,6 +1165,13 @@ static int classify_main(int argc, char **argv)
 	if ((ab_out || abr_out) && (rc = dsb_multi_enable_abundance(a.multi, 1, ab_permille))) { fprintf(stderr, "\n[dsb_ctx_enable_abundance] %s\n", dsb_strerror(rc)); exit(1); }
 	if (a.lca_on && (rc = dsb_multi_enable_lca(a.multi, 1, lca_permille))) { fprintf(stderr, "\n[dsb_ctx_enable_lca] %s\n", dsb_strerror(rc)); exit(1); }
 	if (a.ident_on && (rc = dsb_multi_enable_identity(a.multi, 1, id_band, id_permille))) { fprintf(stderr, "\n[dsb_ctx_enable_identity] %s\n", dsb_strerror(rc)); exit(1); }
+	if (a.cg_out) {
+		if ((rc = dsb_multi_enable_alignment(a.multi, 1, cig_trace_kib, 0))) { fprintf(stderr, "\n[dsb_ctx_enable_alignment] %s\n", dsb_strerror(rc)); exit(1); }
+		size_t cap = 1 << 14; char *buf = NULL; long w;
+		do { cap *= 4; buf = xrealloc(buf, cap); w = dsb_aligned_sam_header(a.idx, buf, cap); } while (w < 0);
+		if (fwrite(buf, 1, (size_t)w, a.cg_out) != (size_t)w) die("[classify] cannot write the aligned SAM");
+		free(buf);
+	}
 	double t0 = now(), cpu0 = cputime(); a.t0 = t0;
 	a.thr0 = a.trace ? throttled_usec() : -1;
 	fprintf(stderr, "Start classify\n");
@@ -1220,6 +1269,7 @@ static int classify_main(int argc, char **argv)
 	}
 	if (a.kr_out && fclose(a.kr_out)) die("[classify] cannot write the per-read classifications");
 	if (a.id_out && fclose(a.id_out)) die("[classify] cannot write the per-record identities");
+	if (a.cg_out && fclose(a.cg_out)) die("[classify] cannot write the aligned SAM");
 	if (idr_out) {
 		/* --identity-refs: the run's per-reference identity table, the contexts' tables added */
 		const size_t n_ref = (size_t)dsb_index_n_ref(a.idx);

@@ -87,6 +87,7 @@ struct dsb_multi {
 	const dsb_taxonomy *tx = nullptr; std::vector<dsb_read_taxon> taxa; bool taxa_ok = false;   // dsb_multi_set_taxonomy / dsb_multi_taxa
 	std::vector<dsb_read_lca> lca; bool lca_on = false, lca_ok = false;                          // dsb_multi_enable_lca / dsb_multi_lca
 	std::vector<dsb_hit_identity> ident; bool ident_on = false, ident_ok = false;                // dsb_multi_enable_identity / dsb_multi_identity
+	std::vector<dsb_hit_alignment> aln; std::vector<uint32_t> aln_ops; bool aln_on = false, aln_ok = false;   // dsb_multi_enable_alignment / dsb_multi_alignment
 };
 
 // a device buffer grown to hold at least `need` elements (its contents are not kept)

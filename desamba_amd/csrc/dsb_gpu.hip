@@ -1786,7 +1786,7 @@ static int batch_run_locked(dsb_ctx *c, std::unique_lock<std::mutex> *turn)
 	c->timing.upload_bytes = s.upload_bytes;
 	c->taxa.run = c->taxa.tx != nullptr && n == 0; c->taxa.done = false;
 	c->lca.run = c->lca.d_direct != nullptr && n == 0; c->lca.done = false;
-	c->ident.run = c->ident.d_tab != nullptr && n == 0; c->ident.done = false;
+	c->ident.run = c->ident.d_tab != nullptr && n == 0; c->ident.done = false; c->ident.aln_run = c->ident.d_trace != nullptr && n == 0;
 	if (n == 0) return DSB_OK;
 	const BatchPlan p = batch_plan(c, s);
 	c->n_early = p.n_heavy; c->timing.n_heavy_mw = p.n_mw;
@@ -2012,6 +2012,9 @@ extern "C" int dsb_multi_classify_batch(dsb_multi *m, const dsb_read *reads, siz
 	m->taxa_ok = false; if (m->tx) m->taxa.assign(n, dsb_read_taxon());
 	m->lca_ok = false; if (m->lca_on) m->lca.assign(n, dsb_read_lca());
 	m->ident_ok = false; m->ident.clear();
+	m->aln_ok = false; m->aln.clear(); m->aln_ops.clear();
+	std::vector<std::vector<dsb_hit_alignment>> chunk_aln(nc);      // (ops_off chunk-local for now, the operations packed behind each other)
+	std::vector<std::vector<uint32_t>> chunk_ops(nc);
 	std::vector<std::vector<dsb_hit_identity>> chunk_ident(nc);
 	std::vector<std::vector<dsb_hit>> chunk_hits(nc);
 	std::vector<int> rcs(W, DSB_OK);
@@ -2046,12 +2049,23 @@ extern "C" int dsb_multi_classify_batch(dsb_multi *m, const dsb_read *reads, siz
 			}
 			const dsb_hit_identity *idn = nullptr;
 			if (m->ident_on && (rc = dsb_batch_identity(c, &idn))) { rcs[w] = rc; return; }
+			const dsb_hit_alignment *aln = nullptr; const uint32_t *aops = nullptr; uint64_t n_aops = 0;
+			if (m->aln_on && (rc = dsb_batch_alignment(c, &aln, &aops, &n_aops))) { rcs[w] = rc; return; }
 			std::vector<dsb_hit> &H = chunk_hits[k];
 			for (uint64_t i = ch.start; i < ch.end; i++) {
 				dsb_read_result rr = r.reads[i - ch.start];
 				const uint32_t first = (uint32_t)H.size();
 				H.insert(H.end(), r.hits + rr.first, r.hits + rr.first + rr.n);
 				if (idn) chunk_ident[k].insert(chunk_ident[k].end(), idn + rr.first, idn + rr.first + rr.n);
+				for (uint32_t j = 0; aln && j < rr.n; j++) {
+					dsb_hit_alignment a = aln[rr.first + j];
+					if (a.n_ops && a.ops_off + a.n_ops <= n_aops) {
+						const uint64_t at = chunk_ops[k].size();
+						chunk_ops[k].insert(chunk_ops[k].end(), aops + a.ops_off, aops + a.ops_off + a.n_ops);
+						a.ops_off = at;
+					}
+					chunk_aln[k].push_back(a);
+				}
 				rr.first = first;                                    // chunk-local for now
 				m->reads[i] = rr;
 			}
@@ -2069,10 +2083,13 @@ extern "C" int dsb_multi_classify_batch(dsb_multi *m, const dsb_read *reads, siz
 		for (uint64_t i = plan[k].start; i < plan[k].end; i++) m->reads[i].first += base;
 		m->hits.insert(m->hits.end(), chunk_hits[k].begin(), chunk_hits[k].end());
 		m->ident.insert(m->ident.end(), chunk_ident[k].begin(), chunk_ident[k].end());
+		const uint64_t ops_base = m->aln_ops.size();
+		for (dsb_hit_alignment a : chunk_aln[k]) { if (a.n_ops) a.ops_off += ops_base; m->aln.push_back(a); }
+		m->aln_ops.insert(m->aln_ops.end(), chunk_ops[k].begin(), chunk_ops[k].end());
 	}
 	for (size_t i = 0; i < n; i++) if (len[i] > m->hist) m->hist = len[i];
 	out->reads = m->reads.data(); out->hits = m->hits.data(); out->n_hits = m->hits.size();
-	m->taxa_ok = m->tx != nullptr; m->lca_ok = m->lca_on; m->ident_ok = m->ident_on;
+	m->taxa_ok = m->tx != nullptr; m->lca_ok = m->lca_on; m->ident_ok = m->ident_on; m->aln_ok = m->aln_on;
 	return worst;
 }
 #endif  // DSB_UNIT_HOST

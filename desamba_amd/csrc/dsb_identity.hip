@@ -1,6 +1,7 @@
 // Per-hit edit distance and per-reference identity (dsb_identity.h): the banded alignment of every counted record of a
 // batch, one wavefront per record, after the batch's last classify launch; the run's per-reference table; the bare-pair entry
-// dsb_ctx_edit_pairs, which runs the same device function on sequences of the caller's.
+// dsb_ctx_edit_pairs, which runs the same device function on sequences of the caller's.  With dsb_ctx_enable_alignment the
+// same pass also keeps the path: k_hit_align in place of k_hit_edits, ident_path behind ident_wave<true>, dsb_ctx_align_pairs.
 //
 // The alignment is the diagonal-transition form of the banded unit-cost problem.  Diagonal k holds the cells (i, i + k), i bases of Q
 // against i + k bases of T; FR_e[k] is the largest i on diagonal k that e edits reach.  The band is a set of whole diagonals
@@ -17,7 +18,8 @@
 #define IDENT_BAD (DSB_IDENT_EMPTY | DSB_IDENT_SKEW | DSB_IDENT_OVER)
 #define IDENT_MAX_LEN 0x40000000u                      // dsb_ctx_edit_pairs: longest sequence (the furthest-reaching points are ints)
 #define IDENT_MAX_OFF (1ull << 40)                     // dsb_ctx_edit_pairs: furthest start of a pair in its blob
-#define IDENT_T_PAD 16                                 // bytes behind a packed text that a 32-base fetch may read (refbin has 4 KiB)
+#define IDENT_MAX_RUN 0x10000000u                      // an operation's length has 28 bits (BAM's): longer sequences get no path
+#define IDENT_T_PAD 16                                // bytes behind a packed text that a 32-base fetch may read (refbin has 4 KiB)
 
 // Q: packed words, 32 bases each, the first in the top bits, base qbase of them the first of Q (a read strand of d_pk, or a blob of
 // dsb_ctx_edit_pairs; one pad word behind).  T: packed bytes, 4 bases each, the first in the top bits, base tbase the first of T.
@@ -57,7 +59,12 @@ DV int ident_slide(const IdentSeq &s, int i, int k)
 // diagonal k with an unreached entry on either side of the band; both start unreached, and generation e writes the diagonals
 // [max(lo, -e), min(hi, e)], a superset of what generation e - 2 wrote into the same half.  Lane l takes diagonals klo + l + 64 r.
 // The loops are bounded by E_cap (edits), the band width (rounds) and n, m (slides).
-DV dsb_hit_identity ident_wave(const IdentSeq &s, uint32_t band, uint32_t permille, int *fr, uint32_t half, int lane)
+// TR (the tracing form, k_hit_align / k_pair_align): every lane also holds the 2-bit code of the candidate it chose (0
+// mismatch, 1 a base of T alone, 2 a base of Q alone, 3 none moved; lanes beyond khi: 3), and each round's two bit planes (two
+// ballots) go as 16 bytes to trace + (e - 1) * R + 16 * round, R = 16 * ceil(W / 64), by one lane -- while e * R <= room, so that
+// nothing is written beyond the place; after that the pass goes on as the plain form does.  The plain form compiles to what it was.
+template <bool TR>
+DV dsb_hit_identity ident_wave(const IdentSeq &s, uint32_t band, uint32_t permille, int *fr, uint32_t half, int lane, uint64_t *trace = nullptr, uint64_t room = 0)
 {
 	dsb_hit_identity o; o.edits = 0; o.q_len = s.n; o.t_len = s.m; o.flags = 0;
 	const int n = (int)s.n, m = (int)s.m, delta = m - n;
@@ -77,18 +84,29 @@ DV dsb_hit_identity ident_wave(const IdentSeq &s, uint32_t band, uint32_t permil
 		wave_sync();
 		const int klo = lo > -(int)e ? lo : -(int)e, khi = hi < (int)e ? hi : (int)e;
 		bool mine = false;
+		const uint32_t R = 2u * (uint32_t)((W + 63) / 64);            // (TR) a generation's trace, in 8-byte words
+		const bool tracing = TR && (uint64_t)e * R * 8u <= room;
+		uint64_t *gen = TR ? trace + (uint64_t)(e - 1) * R : nullptr;
 		for (int k0 = klo; k0 <= khi; k0 += DSB_WAVE) {
 			const int k = k0 + lane;
+			uint32_t mv = 3;
 			if (k <= khi) {
 				const int x = k - lo + 1;
 				const int p = prev[x], pl = prev[x - 1], pr = prev[x + 1];
 				int c = p;
-				if (p >= 0 && p + 1 <= n && p + 1 + k <= m) c = p + 1;
-				if (pl >= 0 && pl + k <= m && pl > c) c = pl;
-				if (pr >= 0 && pr + 1 <= n && pr + 1 > c) c = pr + 1;
+				if (p >= 0 && p + 1 <= n && p + 1 + k <= m) { c = p + 1; mv = 0; }
+				if (pl >= 0 && pl + k <= m && pl > c) { c = pl; mv = 1; }
+				if (pr >= 0 && pr + 1 <= n && pr + 1 > c) { c = pr + 1; mv = 2; }
 				if (c >= 0) c = ident_slide(s, c, k);
 				cur[x] = c;
 				if (k == delta && c >= n) mine = true;
+			}
+			if constexpr (TR) {
+				if (tracing) {                                         // (wave-uniform: all lanes give their bit to both planes)
+					const uint64_t b0 = dsb_ballot64((mv & 1u) != 0), b1 = dsb_ballot64((mv & 2u) != 0);
+					if (lane == 0) { ulonglong2 v; v.x = b0; v.y = b1; *reinterpret_cast<ulonglong2 *>(gen) = v; }
+					gen += 2;
+				}
 			}
 		}
 		hit = dsb_ballot64(mine) != 0;
@@ -107,6 +125,77 @@ DV uint32_t ident_take(unsigned int *work, int lane)
 	uint32_t w = 0;
 	if (lane == 0) w = atomicAdd(work, 1u);
 	return dsb_shfl(w, 0);
+}
+
+// ---- the path of a record: walk back through the traced moves, replay forward, emit run-length operations ----
+// Appends to a record's operations, merging equal neighbours.  Every lane holds the same state and stores the same word.
+struct IdentOps {
+	uint32_t *out; uint32_t cnt, op, len;
+	DV void put(uint32_t o, uint32_t l)
+	{
+		if (!l) return;
+		if (o == op) { len += l; return; }
+		flush(); op = o; len = l;
+	}
+	DV void flush() { if (len) out[cnt++] = len << 4 | op; len = 0; }
+};
+
+// After ident_wave<true> and a wave_sync, in wave-uniform control flow: all lanes run the same steps on the same values (what
+// comes from memory goes through DSB_RFL, so the walk and the replay are scalar branches), and the stores are the same bytes from
+// every lane.  The walk back reads generation e = edits .. 1 at diagonal k (from d to 0), two words per step, and leaves the move
+// in the first byte of that generation's own 16 bytes -- read already, and below every generation still to be read.  Index
+// arithmetic alone keeps every access inside the place: e <= edits with edits * R <= room, and the diagonal is clamped to
+// the generation's [klo, khi].  The replay applies a move only where the rectangle has the room for it and ends on (n, m); a trace
+// that does not (none was seen: the model of tests/align_lib.py asserts it cannot happen) gives a record without operations.
+// Loops: edits steps each, the slides bounded by n and m; at most 2 * edits + 1 operations, the room reserved with one atomic.
+DV dsb_hit_alignment ident_path(const IdentSeq &s, uint32_t band, const dsb_hit_identity &o, uint64_t *trace, uint64_t room,
+                                uint32_t *ops, uint64_t ops_cap, unsigned long long *ops_used, int lane)
+{
+	dsb_hit_alignment a; a.ops_off = 0; a.n_ops = a.n_x = a.n_ins = a.n_del = a.flags = a.pad = 0;
+	if (o.flags & IDENT_BAD) { a.flags = DSB_ALN_UNALIGNED; return a; }
+	const int n = (int)s.n, m = (int)s.m, delta = m - n;
+	const int lo = (delta < 0 ? delta : 0) - (int)band, hi = (delta > 0 ? delta : 0) + (int)band, W = hi - lo + 1;
+	const uint32_t R = 2u * (uint32_t)((W + 63) / 64), E = o.edits;
+	if ((uint64_t)E * R * 8u > room || s.n >= IDENT_MAX_RUN || s.m >= IDENT_MAX_RUN) { a.flags = DSB_ALN_NOTRACE; return a; }
+	uint8_t *moves = reinterpret_cast<uint8_t *>(trace);
+	int k = delta;
+	for (uint32_t e = E; e >= 1; e--) {
+		const int klo = lo > -(int)e ? lo : -(int)e, khi = hi < (int)e ? hi : (int)e;
+		int x = k - klo;
+		if (x > khi - klo) x = khi - klo;
+		if (x < 0) x = 0;
+		const uint64_t *g = trace + (uint64_t)(e - 1) * R + 2u * ((uint32_t)x >> 6);
+		const uint64_t b0 = g[0], b1 = g[1];
+		const uint32_t mv = DSB_RFL((uint32_t)((b0 >> (x & 63)) & 1u) | (uint32_t)((b1 >> (x & 63)) & 1u) << 1);
+		moves[(uint64_t)(e - 1) * R * 8u] = (uint8_t)mv;
+		k = klo + x + (mv == 2u ? 1 : 0) - (mv == 1u ? 1 : 0);
+	}
+	wave_sync();
+	const uint64_t need = 2ull * E + 1u;
+	uint32_t off_lo = 0, off_hi = 0;
+	if (lane == 0) { const unsigned long long at = atomicAdd(ops_used, (unsigned long long)need); off_lo = (uint32_t)at; off_hi = (uint32_t)(at >> 32); }
+	const uint64_t off = (uint64_t)dsb_shfl(off_hi, 0) << 32 | dsb_shfl(off_lo, 0);
+	if (off > ops_cap || need > ops_cap - off) { a.flags = DSB_ALN_NOROOM; return a; }
+	IdentOps w; w.out = ops + off; w.cnt = 0; w.op = 0; w.len = 0;
+	int i = 0; k = 0;
+	bool good = true;
+	for (uint32_t e = 1; e <= E && good; e++) {
+		const int i2 = (int)DSB_RFL(ident_slide(s, i, k));
+		w.put(DSB_ALN_OP_EQ, (uint32_t)(i2 - i)); i = i2;
+		const uint32_t mv = DSB_RFL(moves[(uint64_t)(e - 1) * R * 8u]);
+		if (mv == 1u && i + k < m) { w.put(DSB_ALN_OP_D, 1); k++; a.n_del++; }
+		else if (mv == 2u && i < n) { w.put(DSB_ALN_OP_I, 1); i++; k--; a.n_ins++; }
+		else if (mv == 0u && i < n && i + k < m) { w.put(DSB_ALN_OP_X, 1); i++; a.n_x++; }
+		else good = false;
+	}
+	if (good) {
+		const int i2 = (int)DSB_RFL(ident_slide(s, i, k));
+		w.put(DSB_ALN_OP_EQ, (uint32_t)(i2 - i)); i = i2;
+		w.flush();
+	}
+	if (!good || i != n || i + k != m) { a.n_x = a.n_ins = a.n_del = 0; a.flags = DSB_ALN_NOTRACE; return a; }
+	a.ops_off = off; a.n_ops = w.cnt; a.flags = DSB_ALN_OPS;
+	return a;
 }
 
 // One lane per read, after the batch's last classify work: the records dsb_ref_coverage counts (dsb_sam_counted, among the hits
@@ -147,8 +236,43 @@ __global__ void __launch_bounds__(256) k_hit_edits(const DsbHitOut *__restrict__
 		IdentSeq s;
 		s.qw = pk + d.pk_off + (h.direction ? 0u : (d.len + 31u) / 32u + 1u); s.qbase = qs; s.n = qe > qs ? qe - qs : 0u;
 		s.tb = refbin; s.tbase = off + ts; s.m = te > ts ? (uint32_t)(te - ts) : 0u;
-		const dsb_hit_identity o = ident_wave(s, band, permille, fr, stride / 2u, lane);
+		const dsb_hit_identity o = ident_wave<false>(s, band, permille, fr, stride / 2u, lane);
 		rec[it.x] = o;                                          // (all lanes, the same value: ident_take)
+	}
+}
+
+// Where a trace arena lies and where operations go (k_hit_align, k_pair_align): wavefront w owns trace[w * room / 8 .. + room / 8)
+struct IdentAlnOut { uint64_t *trace; uint64_t room; dsb_hit_alignment *aln; uint32_t *ops; uint64_t ops_cap; unsigned long long *ops_used; };
+
+// k_hit_edits with the path kept (dsb_ctx_enable_alignment): the same list, work counter and loop; one forward pass in the tracing
+// form, then the same wavefront walks back and replays (ident_path).  The identity record is the one k_hit_edits gives.
+__global__ void __launch_bounds__(256) k_hit_align(const DsbHitOut *__restrict__ hout, const DsbReadDesc *__restrict__ rd, const uint64_t *__restrict__ pk,
+                                                   const uint8_t *__restrict__ refbin, const DsbRefInfo *__restrict__ refinfo, uint32_t n_ref,
+                                                   const uint2 *__restrict__ list, unsigned int *cnt, uint32_t band, uint32_t permille, int *arena, uint32_t stride,
+                                                   dsb_hit_identity *__restrict__ rec, IdentAlnOut A)
+{
+	const int lane = (int)(threadIdx.x & 63u);
+	const size_t wave = blockIdx.x * 4u + (threadIdx.x >> 6);
+	int *fr = arena + wave * stride;
+	uint64_t *trace = A.trace + wave * (A.room / 8u);
+	const uint32_t total = cnt[0];
+	for (;;) {
+		const uint32_t w = ident_take(cnt + 1, lane);
+		if (w >= total) break;
+		const uint2 it = list[w];
+		const DsbHitOut h = hout[it.x];
+		const DsbReadDesc d = rd[it.y];
+		uint64_t ln = 0, off = 0;
+		if (h.ref_ID < n_ref) { const DsbRefInfo ri = refinfo[h.ref_ID]; ln = ri.seq_l; off = ri.seq_offset; }
+		const uint32_t qs = h.q_st < d.len ? h.q_st : d.len, qe = h.q_ed < d.len ? h.q_ed : d.len;
+		const uint64_t ts = h.t_st < ln ? h.t_st : ln, te = h.t_ed < ln ? h.t_ed : ln;
+		IdentSeq s;
+		s.qw = pk + d.pk_off + (h.direction ? 0u : (d.len + 31u) / 32u + 1u); s.qbase = qs; s.n = qe > qs ? qe - qs : 0u;
+		s.tb = refbin; s.tbase = off + ts; s.m = te > ts ? (uint32_t)(te - ts) : 0u;
+		const dsb_hit_identity o = ident_wave<true>(s, band, permille, fr, stride / 2u, lane, trace, A.room);
+		wave_sync();
+		const dsb_hit_alignment a = ident_path(s, band, o, trace, A.room, A.ops, A.ops_cap, A.ops_used, lane);
+		rec[it.x] = o; A.aln[it.x] = a;                         // (all lanes, the same values)
 	}
 }
 
@@ -219,8 +343,29 @@ __global__ void __launch_bounds__(256) k_pair_edits(const uint64_t *__restrict__
 		if (w >= n_pairs) break;
 		IdentSeq s;
 		s.qw = qw; s.qbase = q_off[w]; s.n = q_len[w]; s.tb = tb; s.tbase = t_off[w]; s.m = t_len[w];
-		const dsb_hit_identity o = ident_wave(s, band, permille, fr, stride / 2u, lane);
+		const dsb_hit_identity o = ident_wave<false>(s, band, permille, fr, stride / 2u, lane);
 		out[w] = o;                                             // (all lanes, the same value: ident_take)
+	}
+}
+// its tracing twin (dsb_ctx_align_pairs): what k_hit_align does to a record, on pair w
+__global__ void __launch_bounds__(256) k_pair_align(const uint64_t *__restrict__ qw, const uint8_t *__restrict__ tb, const uint64_t *__restrict__ q_off,
+                                                    const uint32_t *__restrict__ q_len, const uint64_t *__restrict__ t_off, const uint32_t *__restrict__ t_len,
+                                                    uint32_t n_pairs, unsigned int *work, uint32_t band, uint32_t permille, int *arena, uint32_t stride,
+                                                    dsb_hit_identity *__restrict__ out, IdentAlnOut A)
+{
+	const int lane = (int)(threadIdx.x & 63u);
+	const size_t wave = blockIdx.x * 4u + (threadIdx.x >> 6);
+	int *fr = arena + wave * stride;
+	uint64_t *trace = A.trace + wave * (A.room / 8u);
+	for (;;) {
+		const uint32_t w = ident_take(work, lane);
+		if (w >= n_pairs) break;
+		IdentSeq s;
+		s.qw = qw; s.qbase = q_off[w]; s.n = q_len[w]; s.tb = tb; s.tbase = t_off[w]; s.m = t_len[w];
+		const dsb_hit_identity o = ident_wave<true>(s, band, permille, fr, stride / 2u, lane, trace, A.room);
+		wave_sync();
+		const dsb_hit_alignment a = ident_path(s, band, o, trace, A.room, A.ops, A.ops_cap, A.ops_used, lane);
+		out[w] = o; A.aln[w] = a;                               // (all lanes, the same values)
 	}
 }
 
@@ -236,8 +381,19 @@ static int ident_waves(int device, uint32_t *n_waves)
 	return DSB_OK;
 }
 
+// alignment off: the trace arena, the records and the operation array freed (identity stays as it is)
+static void alignment_release(dsb_ctx *c)
+{
+	DsbIdent &d = c->ident;
+	hipFree(d.d_trace); hipFree(d.d_aln); hipFree(d.d_ops); hipFree(d.d_ops_used);
+	d.d_trace = nullptr; d.d_aln = nullptr; d.d_ops = nullptr; d.d_ops_used = nullptr;
+	d.cap_aln = d.cap_ops = 0; d.trace_kib = 0; d.ops_fixed = d.ops_room = 0; d.aln_run = false;
+	std::vector<dsb_hit_alignment>().swap(d.h_aln); std::vector<uint32_t>().swap(d.h_ops);
+}
+
 void identity_release(dsb_ctx *c)
 {
+	alignment_release(c);
 	hipFree(c->ident.d_rec); hipFree(c->ident.d_list); hipFree(c->ident.d_cnt); hipFree(c->ident.d_arena); hipFree(c->ident.d_tab);
 	c->ident = DsbIdent();
 }
@@ -274,6 +430,25 @@ extern "C" int dsb_ctx_enable_identity(dsb_ctx *c, int on, uint32_t band, uint32
 	return dsb_ctx_reset_identity(c);
 }
 
+extern "C" int dsb_ctx_enable_alignment(dsb_ctx *c, int on, uint32_t trace_kib, uint64_t ops_cap)
+{
+	if (!c) return DSB_EINVAL;
+	if (on && !c->ident.d_tab) return DSB_EINVAL;
+	if (on && trace_kib == 0) trace_kib = DSB_ALN_TRACE_KIB_DEFAULT;
+	if (on && trace_kib > DSB_ALN_TRACE_KIB_MAX) return DSB_EINVAL;
+	HIPCHK(hipSetDevice(c->device));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	alignment_release(c);
+	if (!on) return DSB_OK;
+	DsbIdent &d = c->ident;
+	if (hipMalloc((void **)&d.d_trace, (size_t)d.n_waves * trace_kib * 1024u) != hipSuccess || hipMalloc((void **)&d.d_ops_used, sizeof(unsigned long long)) != hipSuccess ||
+	    grow(&d.d_aln, &d.cap_aln, c->cap_hout)) {
+		alignment_release(c); (void)hipGetLastError(); return DSB_ENOMEM;
+	}
+	d.trace_kib = trace_kib; d.ops_fixed = ops_cap;
+	return DSB_OK;
+}
+
 int identity_run(dsb_ctx *c, const DsbBatchView &b)
 {
 	DsbIdent &d = c->ident;
@@ -282,6 +457,17 @@ int identity_run(dsb_ctx *c, const DsbBatchView &b)
 	HIPCHK(hipMemsetAsync(d.d_rec, 0, b.cap_hout * sizeof(dsb_hit_identity), b.st));
 	HIPCHK(hipMemsetAsync(d.d_cnt, 0, 2 * sizeof(unsigned int), b.st));
 	hipLaunchKernelGGL(k_ident_list, dim3((b.n + 255) / 256), dim3(256), 0, b.st, b.rout, b.hout, b.counters, (uint32_t)b.cap_hout, b.n, d.d_list, d.d_cnt);
+	if (d.d_trace) {
+		// alignment on: the records' room and the batch's operation array (automatic: an operation per base and four per hit place)
+		d.ops_room = d.ops_fixed ? d.ops_fixed : c->in[c->cur].total_bases + 4ull * b.cap_hout;
+		if (grow(&d.d_aln, &d.cap_aln, b.cap_hout) || grow(&d.d_ops, &d.cap_ops, (size_t)d.ops_room)) return DSB_ENOMEM;
+		HIPCHK(hipMemsetAsync(d.d_aln, 0, b.cap_hout * sizeof(dsb_hit_alignment), b.st));
+		HIPCHK(hipMemsetAsync(d.d_ops_used, 0, sizeof(unsigned long long), b.st));
+		IdentAlnOut A; A.trace = d.d_trace; A.room = (uint64_t)d.trace_kib * 1024u; A.aln = d.d_aln; A.ops = d.d_ops; A.ops_cap = d.ops_room; A.ops_used = d.d_ops_used;
+		hipLaunchKernelGGL(k_hit_align, dim3(d.n_waves / 4), dim3(256), 0, b.st, b.hout, b.rd, b.pk, c->dx.refbin, c->dx.refinfo, (uint32_t)dsb_index_n_ref(c->idx),
+		                   (const uint2 *)d.d_list, d.d_cnt, d.band, d.permille, d.d_arena, d.stride, d.d_rec, A);
+		d.aln_run = true;
+	} else
 	hipLaunchKernelGGL(k_hit_edits, dim3(d.n_waves / 4), dim3(256), 0, b.st, b.hout, b.rd, b.pk, c->dx.refbin, c->dx.refinfo, (uint32_t)dsb_index_n_ref(c->idx),
 	                   (const uint2 *)d.d_list, d.d_cnt, d.band, d.permille, d.d_arena, d.stride, d.d_rec);
 	const size_t ref_blocks = std::min<size_t>((b.cap_hout + 255) / 256, 1024);
@@ -295,6 +481,27 @@ int identity_fetch_queue(dsb_ctx *c, size_t n_hits)
 {
 	c->ident.h_rec.resize(n_hits);
 	if (n_hits) HIPCHK(hipMemcpyAsync(c->ident.h_rec.data(), c->ident.d_rec, n_hits * sizeof(dsb_hit_identity), hipMemcpyDeviceToHost, c->stream));
+	if (!c->ident.aln_run) return DSB_OK;
+	// alignment: the records, and the used part of the operation array alone -- its length has to be known before the copy is
+	// queued, so it is read first (8 bytes, one wait on the stream that the batch's counters have already been waited for on)
+	DsbIdent &d = c->ident;
+	d.h_aln.resize(n_hits); d.h_ops.clear();
+	if (!n_hits) return DSB_OK;
+	unsigned long long used = 0;
+	HIPCHK(hipMemcpyAsync(d.h_aln.data(), d.d_aln, n_hits * sizeof(dsb_hit_alignment), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipMemcpyAsync(&used, d.d_ops_used, sizeof used, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	if (used > d.ops_room) used = d.ops_room;                // (reservations that did not fit moved the counter too)
+	d.h_ops.resize((size_t)used);
+	if (used) HIPCHK(hipMemcpyAsync(d.h_ops.data(), d.d_ops, (size_t)used * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+	return DSB_OK;
+}
+
+extern "C" int dsb_batch_alignment(dsb_ctx *c, const dsb_hit_alignment **recs, const uint32_t **ops, uint64_t *n_ops)
+{
+	if (!c || !recs || !ops || !n_ops || !c->ident.d_trace || !c->ident.aln_run) return DSB_EINVAL;
+	if (!c->ident.done) { dsb_result r; int rc = dsb_batch_fetch(c, &r); if (rc && rc != DSB_ECAP) return rc; }
+	*recs = c->ident.h_aln.data(); *ops = c->ident.h_ops.data(); *n_ops = c->ident.h_ops.size();
 	return DSB_OK;
 }
 
@@ -325,6 +532,27 @@ extern "C" int dsb_multi_enable_identity(dsb_multi *m, int on, uint32_t band, ui
 		if (rc) { for (dsb_ctx *d : m->ctx) dsb_ctx_enable_identity(d, 0, 0, 0); return rc; }
 	}
 	m->ident_on = on != 0;
+	for (dsb_ctx *c : m->ctx) if (!c->ident.d_trace) m->aln_on = false;      // (identity off, or on with another band: alignment went with it)
+	m->aln_ok = false;
+	return DSB_OK;
+}
+
+extern "C" int dsb_multi_enable_alignment(dsb_multi *m, int on, uint32_t trace_kib, uint64_t ops_cap)
+{
+	if (!m) return DSB_EINVAL;
+	m->aln_on = m->aln_ok = false;
+	for (dsb_ctx *c : m->ctx) {
+		int rc = dsb_ctx_enable_alignment(c, on, trace_kib, ops_cap);
+		if (rc) { for (dsb_ctx *d : m->ctx) dsb_ctx_enable_alignment(d, 0, 0, 0); return rc; }
+	}
+	m->aln_on = on != 0;
+	return DSB_OK;
+}
+
+extern "C" int dsb_multi_alignment(dsb_multi *m, const dsb_hit_alignment **recs, const uint32_t **ops, uint64_t *n_ops)
+{
+	if (!m || !recs || !ops || !n_ops || !m->aln_on || !m->aln_ok) return DSB_EINVAL;
+	*recs = m->aln.data(); *ops = m->aln_ops.data(); *n_ops = m->aln_ops.size();
 	return DSB_OK;
 }
 
@@ -352,15 +580,20 @@ extern "C" int dsb_multi_ref_identity(dsb_multi *m, dsb_ref_identity *out)
 	return DSB_OK;
 }
 
-extern "C" int dsb_ctx_edit_pairs(dsb_ctx *c, const uint8_t *q_codes, const uint64_t *q_off, const uint32_t *q_len, const uint8_t *t_codes, const uint64_t *t_off,
-                                  const uint32_t *t_len, size_t n_pairs, uint32_t band, uint32_t max_permille, dsb_hit_identity *out)
+// dsb_ctx_edit_pairs, and with al dsb_ctx_align_pairs: the same packing and the same phases, k_pair_edits or its tracing twin
+struct IdentPairsAln { uint32_t trace_kib; dsb_hit_alignment *aln_out; uint32_t *ops_out; uint64_t ops_cap; uint64_t *ops_used; };
+static int ident_pairs(dsb_ctx *c, const uint8_t *q_codes, const uint64_t *q_off, const uint32_t *q_len, const uint8_t *t_codes, const uint64_t *t_off,
+                       const uint32_t *t_len, size_t n_pairs, uint32_t band, uint32_t max_permille, dsb_hit_identity *out, const IdentPairsAln *al)
 {
 	if (!c || band > DSB_IDENT_MAX_BAND || max_permille < 1 || max_permille > 1000 || n_pairs > 0xffffffffu) return DSB_EINVAL;
+	if (al && (!al->ops_used || al->trace_kib < 1 || al->trace_kib > DSB_ALN_TRACE_KIB_MAX)) return DSB_EINVAL;
+	if (al) *al->ops_used = 0;
 	if (!n_pairs) return DSB_OK;
-	if (!q_codes || !q_off || !q_len || !t_codes || !t_off || !t_len || !out) return DSB_EINVAL;
+	if (!q_codes || !q_off || !q_len || !t_codes || !t_off || !t_len || !out || (al && (!al->aln_out || (!al->ops_out && al->ops_cap)))) return DSB_EINVAL;
+	const uint32_t max_len = al ? IDENT_MAX_RUN - 1u : IDENT_MAX_LEN;
 	uint64_t nq = 0, nt = 0;
 	for (size_t p = 0; p < n_pairs; p++) {
-		if (q_len[p] > IDENT_MAX_LEN || t_len[p] > IDENT_MAX_LEN || q_off[p] > IDENT_MAX_OFF || t_off[p] > IDENT_MAX_OFF) return DSB_EINVAL;   // (the sums below cannot wrap)
+		if (q_len[p] > max_len || t_len[p] > max_len || q_off[p] > IDENT_MAX_OFF || t_off[p] > IDENT_MAX_OFF) return DSB_EINVAL;   // (the sums below cannot wrap)
 		nq = std::max(nq, q_off[p] + q_len[p]); nt = std::max(nt, t_off[p] + t_len[p]);
 	}
 	HIPCHK(hipSetDevice(c->device));
@@ -378,6 +611,13 @@ extern "C" int dsb_ctx_edit_pairs(dsb_ctx *c, const uint8_t *q_codes, const uint
 	int *d_arena = (int *)T.get((size_t)n_waves * stride * sizeof(int));
 	dsb_hit_identity *d_out = (dsb_hit_identity *)T.get(n_pairs * sizeof(dsb_hit_identity));
 	if (!d_qc || !d_tc || !d_tb || !d_qw || !d_qo || !d_to || !d_ql || !d_tl || !d_work || !d_arena || !d_out) return DSB_ENOMEM;
+	IdentAlnOut A; memset(&A, 0, sizeof A);
+	if (al) {
+		A.room = (uint64_t)al->trace_kib * 1024u; A.ops_cap = al->ops_cap;
+		A.trace = (uint64_t *)T.get((size_t)n_waves * A.room); A.aln = (dsb_hit_alignment *)T.get(n_pairs * sizeof(dsb_hit_alignment));
+		A.ops = (uint32_t *)T.get((size_t)al->ops_cap * sizeof(uint32_t)); A.ops_used = (unsigned long long *)T.get(sizeof(unsigned long long));
+		if (!A.trace || !A.aln || !A.ops || !A.ops_used) return DSB_ENOMEM;
+	}
 	hipStream_t st = c->stream;
 	if (nq) HIPCHK(hipMemcpyAsync(d_qc, q_codes, nq, hipMemcpyHostToDevice, st));
 	if (nt) HIPCHK(hipMemcpyAsync(d_tc, t_codes, nt, hipMemcpyHostToDevice, st));
@@ -388,10 +628,39 @@ extern "C" int dsb_ctx_edit_pairs(dsb_ctx *c, const uint8_t *q_codes, const uint
 	HIPCHK(hipMemsetAsync(d_work, 0, sizeof(unsigned int), st));
 	hipLaunchKernelGGL(k_ident_pack_q, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, st, (const uint8_t *)d_qc, nq, d_qw, n_words);
 	hipLaunchKernelGGL(k_ident_pack_t, dim3((unsigned)((n_bytes + 255) / 256)), dim3(256), 0, st, (const uint8_t *)d_tc, nt, d_tb, n_bytes);
+	if (al) {
+		HIPCHK(hipMemsetAsync(A.ops_used, 0, sizeof(unsigned long long), st));
+		hipLaunchKernelGGL(k_pair_align, dim3(n_waves / 4), dim3(256), 0, st, (const uint64_t *)d_qw, (const uint8_t *)d_tb, (const uint64_t *)d_qo, (const uint32_t *)d_ql,
+		                   (const uint64_t *)d_to, (const uint32_t *)d_tl, (uint32_t)n_pairs, d_work, band, max_permille, d_arena, stride, d_out, A);
+	} else
 	hipLaunchKernelGGL(k_pair_edits, dim3(n_waves / 4), dim3(256), 0, st, (const uint64_t *)d_qw, (const uint8_t *)d_tb, (const uint64_t *)d_qo, (const uint32_t *)d_ql,
 	                   (const uint64_t *)d_to, (const uint32_t *)d_tl, (uint32_t)n_pairs, d_work, band, max_permille, d_arena, stride, d_out);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipMemcpyAsync(out, d_out, n_pairs * sizeof(dsb_hit_identity), hipMemcpyDeviceToHost, st));
+	if (al) {
+		unsigned long long used = 0;
+		HIPCHK(hipMemcpyAsync(al->aln_out, A.aln, n_pairs * sizeof(dsb_hit_alignment), hipMemcpyDeviceToHost, st));
+		HIPCHK(hipMemcpyAsync(&used, A.ops_used, sizeof used, hipMemcpyDeviceToHost, st));
+		HIPCHK(hipStreamSynchronize(st));
+		if (used > al->ops_cap) used = al->ops_cap;           // (reservations that did not fit moved the counter too)
+		if (used) HIPCHK(hipMemcpyAsync(al->ops_out, A.ops, (size_t)used * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+		*al->ops_used = used;
+	}
 	HIPCHK(hipStreamSynchronize(st));
 	return DSB_OK;
+}
+
+extern "C" int dsb_ctx_edit_pairs(dsb_ctx *c, const uint8_t *q_codes, const uint64_t *q_off, const uint32_t *q_len, const uint8_t *t_codes, const uint64_t *t_off,
+                                  const uint32_t *t_len, size_t n_pairs, uint32_t band, uint32_t max_permille, dsb_hit_identity *out)
+{
+	return ident_pairs(c, q_codes, q_off, q_len, t_codes, t_off, t_len, n_pairs, band, max_permille, out, nullptr);
+}
+
+extern "C" int dsb_ctx_align_pairs(dsb_ctx *c, const uint8_t *q_codes, const uint64_t *q_off, const uint32_t *q_len, const uint8_t *t_codes, const uint64_t *t_off,
+                                   const uint32_t *t_len, size_t n_pairs, uint32_t band, uint32_t max_permille, uint32_t trace_kib,
+                                   dsb_hit_identity *ident_out, dsb_hit_alignment *aln_out, uint32_t *ops_out, uint64_t ops_cap, uint64_t *ops_used)
+{
+	if (trace_kib == 0) trace_kib = DSB_ALN_TRACE_KIB_DEFAULT;
+	IdentPairsAln al; al.trace_kib = trace_kib; al.aln_out = aln_out; al.ops_out = ops_out; al.ops_cap = ops_cap; al.ops_used = ops_used;
+	return ident_pairs(c, q_codes, q_off, q_len, t_codes, t_off, t_len, n_pairs, band, max_permille, ident_out, &al);
 }

@@ -384,6 +384,85 @@ extern "C" long dsb_format_identity(const dsb_index *x, const dsb_read *rd_, con
 	return (long)o;
 }
 
+// ---- SAM with base-level CIGARs: the text of dsb_batch_alignment's records ----
+extern "C" long dsb_aligned_sam_header(const dsb_index *x, char *buf, size_t cap)
+{
+	if (!x || (!buf && cap)) return -1;
+	size_t o = 0; int w;
+#define EMIT(...) do { w = snprintf(buf + o, cap > o ? cap - o : 0, __VA_ARGS__); if (w < 0 || (size_t)w >= (cap > o ? cap - o : 0)) return -1; o += (size_t)w; } while (0)
+	EMIT("@HD\tVN:1.6\tSO:unknown\n");
+	const uint64_t n_ref = dsb_index_n_ref(x);
+	for (uint64_t r = 0; r < n_ref; r++) EMIT("@SQ\tSN:%s\tLN:%llu\n", dsb_index_ref_name(x, (uint32_t)r), (unsigned long long)dsb_index_ref_len(x, (uint32_t)r));
+	EMIT("@PG\tID:desamba_amd\n");
+#undef EMIT
+	return (long)o;
+}
+
+// bases [a, b) of the strand a chain was built on, and their qualities: direction 1 the read as given, 0 its reverse complement
+// (upper case, what is not ACGT as N) with the qualities reversed; an empty interval or a read without qualities prints *
+static bool aligned_sam_seq(const dsb_read *rd, int forward, uint64_t a, uint64_t b, bool qual, char *buf, size_t cap, size_t *o)
+{
+	const uint64_t L = rd->len, len = b > a ? b - a : 0;
+	if (!len || (qual && !rd->qual)) { if (*o + 1 >= cap) return false; buf[(*o)++] = '*'; return true; }
+	if (*o + len >= cap) return false;
+	for (uint64_t i = a; i < b; i++) {
+		char c;
+		if (qual) c = forward ? rd->qual[i] : rd->qual[L - 1 - i];
+		else {
+			c = forward ? rd->seq[i] : rd->seq[L - 1 - i];
+			if (c >= 'a' && c <= 'z') c = (char)(c - 'a' + 'A');
+			if (!forward) c = c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : 'N';
+			else if (c != 'A' && c != 'C' && c != 'G' && c != 'T') c = 'N';
+		}
+		buf[(*o)++] = c;
+	}
+	return true;
+}
+
+extern "C" long dsb_format_aligned_sam(const dsb_index *x, const dsb_read *rd_, const dsb_read_result *rr, const dsb_hit *h, const dsb_hit_identity *id,
+                                       const dsb_hit_alignment *al, const uint32_t *ops, char *buf, size_t cap)
+{
+	if (!x || !rd_ || !rr || (rr->n && (!h || !id || !al)) || (!buf && cap)) return -1;
+	size_t o = 0; int w;
+#define EMIT(...) do { w = snprintf(buf + o, cap > o ? cap - o : 0, __VA_ARGS__); if (w < 0 || (size_t)w >= (cap > o ? cap - o : 0)) return -1; o += (size_t)w; } while (0)
+#define SEQ(fw, a, b, q) do { if (!aligned_sam_seq(rd_, fw, a, b, q, buf, cap, &o)) return -1; } while (0)
+	const uint64_t L = rd_->len;
+	if (rr->n == 0) {
+		EMIT("%s\t4\t*\t0\t0\t*\t*\t0\t0\t", rd_->name); SEQ(1, 0, L, false); EMIT("\t"); SEQ(1, 0, L, true); EMIT("\n");
+		return (long)o;
+	}
+	const int mapq_pri = dsb_sam_mapq_pri(h, rr->n);
+	for (uint32_t i = 0; i < rr->n; i++) {
+		const dsb_hit *c = h + i;
+		if (!dsb_sam_counted(c, i)) continue;
+		const bool known = c->ref_ID < dsb_index_n_ref(x), sup = i > 0, has = (al[i].flags & DSB_ALN_OPS) != 0;
+		if (has && al[i].n_ops && !ops) return -1;
+		const uint64_t LN = known ? dsb_index_ref_len(x, c->ref_ID) : 0;
+		uint64_t qs = c->q_st < L ? c->q_st : L, qe = c->q_ed < L ? c->q_ed : L;
+		const uint64_t ts = c->t_st < LN ? c->t_st : LN;
+		if (qe < qs) qe = qs;
+		const int fw = c->direction ? 1 : 0;
+		EMIT("%s\t%d\t%s\t%llu\t%d\t", rd_->name, (fw ? 0 : 0x10) + (sup ? 0x800 : 0), known ? dsb_index_ref_name(x, c->ref_ID) : "*",
+		     known ? (unsigned long long)ts + 1 : 0ull, sup ? dsb_sam_mapq_sup(mapq_pri) : mapq_pri);
+		if (has) {
+			const char clip = sup ? 'H' : 'S';
+			if (qs) EMIT("%llu%c", (unsigned long long)qs, clip);
+			for (uint32_t k = 0; k < al[i].n_ops; k++) {
+				const uint32_t v = ops[al[i].ops_off + k], op = v & 15u;
+				EMIT("%u%c", v >> 4, op == DSB_ALN_OP_EQ ? '=' : op == DSB_ALN_OP_X ? 'X' : op == DSB_ALN_OP_I ? 'I' : op == DSB_ALN_OP_D ? 'D' : '?');
+			}
+			if (L - qe) EMIT("%llu%c", (unsigned long long)(L - qe), clip);
+		} else EMIT("*");
+		EMIT("\t*\t0\t0\t");
+		SEQ(fw, sup ? qs : 0, sup ? qe : L, false); EMIT("\t"); SEQ(fw, sup ? qs : 0, sup ? qe : L, true);
+		if (has) EMIT("\tNM:i:%u", id[i].edits); else EMIT("\txa:i:%u", al[i].flags);
+		EMIT("\tAS:i:%u\n", c->sum_score);
+	}
+#undef SEQ
+#undef EMIT
+	return (long)o;
+}
+
 extern "C" long dsb_identity_format(const dsb_index *x, const dsb_ref_identity *tab, char *buf, size_t cap)
 {
 	if (!x || !tab || (!buf && cap)) return -1;

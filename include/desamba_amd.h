@@ -511,6 +511,74 @@ int  dsb_ctx_edit_pairs(dsb_ctx *ctx, const uint8_t *q_codes, const uint64_t *q_
                         const uint8_t *t_codes, const uint64_t *t_off, const uint32_t *t_len, size_t n_pairs,
                         uint32_t band, uint32_t max_permille, dsb_hit_identity *out);
 
+/* ---- base-level alignment of every counted record on the GPU: CIGAR operations and NM.
+ * Everything of the identity records above stands: which records are counted, qs, qe, ts, te, n, m, Q, T, the band [lo, hi] =
+ * [min(0, d) - band, max(0, d) + band], W = hi - lo + 1, E_cap and the flags EMPTY / SKEW / OVER / EXACT.  The intervals are taken as
+ * they come, so the one-base offset of a chain end that is still its anchor's (above) shows as a leading or trailing 1I / 1D / 1X;
+ * classify is not changed.
+ * The alignment of a record is the path that the distance's own recurrence takes.  FR_e[k] is the furthest i on diagonal k (cells
+ * (i, i + k)) after e edits; generation e holds the diagonals [max(lo, -e), min(hi, e)].  On diagonal k of generation e the candidate
+ * chosen is: the mismatch from FR_{e-1}[k] (+1, if the cell lies in the rectangle) -- it wins ties; then a base of T alone from
+ * FR_{e-1}[k - 1], if strictly further; then a base of Q alone from FR_{e-1}[k + 1] (+1), if strictly further.  Move codes: 0 mismatch,
+ * 1 T alone, 2 Q alone, 3 no candidate moved (unreached, or the value carried).  The path runs back from generation `edits` on diagonal
+ * d = m - n to generation 0 on diagonal 0 by the moves alone (0 keeps k, 1 goes to k - 1, 2 goes to k + 1) and is then replayed from
+ * (0, 0): slide while Q[i] == T[i + k] (=), apply the move (X: i + 1; D: j + 1, k + 1; I: i + 1, k - 1), slide, and so on; the last slide
+ * ends on (n, m).  X + I + D == edits.
+ * An operation is len << 4 | op with BAM's codes (len below 2^28, as in BAM); adjacent equal operations are merged, none has length
+ * 0, and a record has at most 2 edits + 1 of them.  Equality is equality of the 2-bit codes the device holds: a letter of a read
+ * that is not A, G or T is C, a letter of the reference that is not C, G or T is A -- so an N can stand under =.
+ * Trace room: a wavefront's trace place holds trace_kib x 1024 bytes and a generation takes R = 16 x ceil(W / 64) of them (two bit
+ * planes of the move codes, 64 diagonals per 16 bytes).  A record has a path iff it is aligned (not EMPTY / SKEW / OVER) and
+ * edits x R <= trace_kib x 1024: a rule of (n, m, band, edits, trace_kib) alone, whatever wavefront takes the record.  Where the room
+ * ends the forward pass goes on without tracing: edits and the identity record are what they are without alignment, and the record
+ * gets DSB_ALN_NOTRACE. */
+typedef struct { uint64_t ops_off; uint32_t n_ops, n_x, n_ins, n_del, flags, pad; } dsb_hit_alignment;   /* n_x, n_ins, n_del: bases */
+#define DSB_ALN_OPS       1    /* n_ops operations at ops_off of the batch's operation array */
+#define DSB_ALN_NOTRACE   2    /* aligned, but edits x R is above the trace room: no path */
+#define DSB_ALN_NOROOM    4    /* the batch's operation array was full: n_ops = 0.  Records take their room in the order their wavefronts
+                                  finish, so WHICH records lose is not deterministic (that none loses is: see ops_cap) */
+#define DSB_ALN_UNALIGNED 8    /* the identity record is EMPTY, SKEW or OVER */
+#define DSB_ALN_OP_I 1
+#define DSB_ALN_OP_D 2
+#define DSB_ALN_OP_EQ 7
+#define DSB_ALN_OP_X 8
+#define DSB_ALN_TRACE_KIB_DEFAULT 2048
+#define DSB_ALN_TRACE_KIB_MAX 65536
+/* on: needs identity on (DSB_EINVAL otherwise) and uses its band and cap; from the next batch on k_hit_align runs in place of
+ * k_hit_edits -- one forward pass, so the identity records and the per-reference table are what they are without it.  Allocates the
+ * trace arena, trace_kib KiB for each wavefront of the grid (8 per compute unit: 2048 wavefronts x 2048 KiB = 4 GiB on an MI355X at the
+ * default), 32 bytes per place of the hit buffer and, per batch, the operation array.  trace_kib 0: the default; 1 .. 65536 else
+ * DSB_EINVAL.  ops_cap 0: the array is sized per batch, one operation per base of the batch's reads plus 4 per place of the hit buffer
+ * (a record reserves its bound 2 edits + 1, so this is enough whenever 2 edits + 1 <= n for every record); otherwise it holds ops_cap
+ * operations.  An allocation that fails: DSB_ENOMEM, and alignment stays off.  off: freed; nothing is allocated or launched while off.
+ * Turning identity off, or on again with another band, turns alignment off too. */
+int  dsb_ctx_enable_alignment(dsb_ctx *ctx, int on, uint32_t trace_kib, uint64_t ops_cap);
+/* the last batch: one record per hit of dsb_batch_fetch's hits (all zero for a hit that is not counted) and the operation array they
+ * index (records lie there in any order, with gaps); valid until the next batch.  DSB_EINVAL before a batch ran with alignment on. */
+int  dsb_batch_alignment(dsb_ctx *ctx, const dsb_hit_alignment **recs, const uint32_t **ops, uint64_t *n_ops);
+int  dsb_multi_enable_alignment(dsb_multi *m, int on, uint32_t trace_kib, uint64_t ops_cap);
+/* the last dsb_multi_classify_batch: records concatenated as dsb_multi_identity's, ops_off rebased into the one array */
+int  dsb_multi_alignment(dsb_multi *m, const dsb_hit_alignment **recs, const uint32_t **ops, uint64_t *n_ops);
+/* n_pairs bare alignments by the device functions of k_hit_align, beside dsb_ctx_edit_pairs: same packing, same phases, lengths
+ * below 2^28 here.  ident_out and aln_out: n_pairs records each; ops_out: room for ops_cap operations (no automatic size here), of
+ * which *ops_used were taken -- the sum of the bounds 2 edits + 1 of the records that have a path and found room. */
+int  dsb_ctx_align_pairs(dsb_ctx *ctx, const uint8_t *q_codes, const uint64_t *q_off, const uint32_t *q_len,
+                         const uint8_t *t_codes, const uint64_t *t_off, const uint32_t *t_len, size_t n_pairs,
+                         uint32_t band, uint32_t max_permille, uint32_t trace_kib,
+                         dsb_hit_identity *ident_out, dsb_hit_alignment *aln_out, uint32_t *ops_out, uint64_t ops_cap, uint64_t *ops_used);
+/* SAM with base-level CIGARs.  Header: @HD VN:1.6 SO:unknown, one @SQ SN LN per reference in ref_ID order, @PG ID:desamba_amd.
+ * A read: one line per counted record, in record order (secondaries are not printed; hits, ident and aln: the read's own, rr->n of
+ * each; ops: the batch's array):  QNAME FLAG RNAME POS MAPQ CIGAR * 0 0 SEQ QUAL NM:i:edits AS:i:sum_score  -- FLAG and MAPQ as
+ * dsb_format_sam prints them, POS = ts + 1, CIGAR = clip, operations, clip with the clips qs and L - qe (left out when 0; S on the
+ * primary, H on a supplementary record).  SEQ of the primary is the whole read on the strand the chain was built on (direction 0:
+ * the reverse complement, any letter that is not ACGT as N, upper case; QUAL reversed; QUAL * without qualities); of a supplementary
+ * record that strand's bases [qs, qe) and their QUAL.  A record without DSB_ALN_OPS: CIGAR *, and xa:i:<alignment flags> where NM
+ * stands.  A record whose ref_ID the index does not have: RNAME *, POS 0.  A read without hits:
+ * QNAME 4 * 0 0 * * 0 0 SEQ QUAL.  Tabs between the fields, none trailing.  Return as dsb_format_sam. */
+long dsb_format_aligned_sam(const dsb_index *idx, const dsb_read *read, const dsb_read_result *rr, const dsb_hit *hits, const dsb_hit_identity *ident,
+                            const dsb_hit_alignment *aln, const uint32_t *ops, char *buf, size_t cap);
+long dsb_aligned_sam_header(const dsb_index *idx, char *buf, size_t cap);
+
 const char *dsb_strerror(int code);
 const char *dsb_version(void);
 
