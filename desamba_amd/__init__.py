@@ -133,6 +133,7 @@ class DsbHitAlignment(C.Structure):
 DSB_ALN_OPS, DSB_ALN_NOTRACE, DSB_ALN_NOROOM, DSB_ALN_UNALIGNED = 1, 2, 4, 8
 DSB_ALN_OP_I, DSB_ALN_OP_D, DSB_ALN_OP_EQ, DSB_ALN_OP_X = 1, 2, 7, 8
 DSB_ALN_TRACE_KIB_DEFAULT, DSB_ALN_TRACE_KIB_MAX = 2048, 65536
+DSB_ALN_MODE_FULL, DSB_ALN_MODE_CHECKPOINT = 0, 1
 HIT_ALIGNMENT_DTYPE = [("ops_off", "<u8"), ("n_ops", "<u4"), ("n_x", "<u4"), ("n_ins", "<u4"), ("n_del", "<u4"), ("flags", "<u4"), ("pad", "<u4")]
 
 
@@ -159,6 +160,7 @@ EXPORTS = ["dsb_index_open", "dsb_index_close", "dsb_index_n_ref", "dsb_index_re
            "dsb_ctx_enable_identity", "dsb_ctx_reset_identity", "dsb_batch_identity", "dsb_ctx_identity", "dsb_multi_enable_identity",
            "dsb_multi_identity", "dsb_multi_ref_identity", "dsb_format_identity", "dsb_identity_format", "dsb_index_ref_bases", "dsb_ctx_edit_pairs",
            "dsb_ctx_enable_alignment", "dsb_batch_alignment", "dsb_multi_enable_alignment", "dsb_multi_alignment", "dsb_ctx_align_pairs",
+           "dsb_aln_plan", "dsb_ctx_alignment_mode", "dsb_multi_alignment_mode", "dsb_ctx_align_pairs_mode",
            "dsb_format_aligned_sam", "dsb_aligned_sam_header"]
 
 _lib = None
@@ -278,6 +280,11 @@ def lib():
     L.dsb_multi_alignment.argtypes = [C.c_void_p, C.POINTER(C.POINTER(DsbHitAlignment)), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint64)]
     L.dsb_ctx_align_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.dsb_aln_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.dsb_ctx_alignment_mode.argtypes = [C.c_void_p, C.c_uint32]
+    L.dsb_multi_alignment_mode.argtypes = [C.c_void_p, C.c_uint32]
+    L.dsb_ctx_align_pairs_mode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
+                                           C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.dsb_format_aligned_sam.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]; L.dsb_format_aligned_sam.restype = C.c_long
     L.dsb_aligned_sam_header.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]; L.dsb_aligned_sam_header.restype = C.c_long
     L.dsb_strerror.argtypes = [C.c_int]; L.dsb_strerror.restype = C.c_char_p
@@ -628,14 +635,22 @@ class Ctx:
         if rc != 0:
             raise DsbError(rc, "dsb_ctx_enable_alignment")
 
+    def alignment_mode(self, mode):
+        """dsb_ctx_alignment_mode: DSB_ALN_MODE_FULL or DSB_ALN_MODE_CHECKPOINT from the next batch on (needs enable_alignment, which
+        always leaves the mode at FULL)"""
+        rc = lib().dsb_ctx_alignment_mode(self.h, int(mode))
+        if rc != 0:
+            raise DsbError(rc, "dsb_ctx_alignment_mode")
+
     def alignment(self, n_hits):
         """(records, ops) of the last batch: one record per hit (HIT_ALIGNMENT_DTYPE) and the uint32 operation array they index"""
         return _alignment(lib().dsb_batch_alignment, self.h, int(n_hits), "dsb_batch_alignment")
 
     def align_pairs(self, q_codes, q_off, q_len, t_codes, t_off, t_len, band=DSB_IDENT_BAND_DEFAULT, max_permille=DSB_IDENT_PERMILLE_DEFAULT,
-                    trace_kib=DSB_ALN_TRACE_KIB_DEFAULT, ops_cap=None):
-        """dsb_ctx_align_pairs: edit_pairs with the path kept; returns (identity records, alignment records, ops).  ops_cap: room of
-        the operation array [None: an operation per base of Q and T plus one per pair -- never short]"""
+                    trace_kib=DSB_ALN_TRACE_KIB_DEFAULT, ops_cap=None, mode=DSB_ALN_MODE_FULL):
+        """dsb_ctx_align_pairs_mode: edit_pairs with the path kept; returns (identity records, alignment records, ops).  ops_cap: room
+        of the operation array [None: an operation per base of Q and T plus one per pair -- never short]; mode: DSB_ALN_MODE_FULL, or
+        DSB_ALN_MODE_CHECKPOINT for the checkpointed traceback"""
         import numpy as np
         qc = np.ascontiguousarray(q_codes, dtype=np.uint8); tc = np.ascontiguousarray(t_codes, dtype=np.uint8)
         qo = np.ascontiguousarray(q_off, dtype=np.uint64); to = np.ascontiguousarray(t_off, dtype=np.uint64)
@@ -650,8 +665,8 @@ class Ctx:
         ident = np.zeros(n, dtype=HIT_IDENTITY_DTYPE); aln = np.zeros(n, dtype=HIT_ALIGNMENT_DTYPE); ops = np.zeros(max(int(ops_cap), 1), dtype=np.uint32)
         used = C.c_uint64(0)
         p = lambda a: a.ctypes.data_as(C.c_void_p)
-        rc = lib().dsb_ctx_align_pairs(self.h, p(qc), p(qo), p(ql), p(tc), p(to), p(tl), n, int(band), int(max_permille), int(trace_kib),
-                                       p(ident), p(aln), p(ops), int(ops_cap), C.byref(used))
+        rc = lib().dsb_ctx_align_pairs_mode(self.h, p(qc), p(qo), p(ql), p(tc), p(to), p(tl), n, int(band), int(max_permille), int(trace_kib), int(mode),
+                                            p(ident), p(aln), p(ops), int(ops_cap), C.byref(used))
         if rc != 0:
             raise DsbError(rc, "dsb_ctx_align_pairs")
         return ident, aln, ops[:used.value]
@@ -804,6 +819,12 @@ class Multi:
         rc = lib().dsb_multi_enable_alignment(self.h, 1 if on else 0, int(trace_kib) if on else 0, int(ops_cap) if on else 0)
         if rc != 0:
             raise DsbError(rc, "dsb_multi_enable_alignment")
+
+    def alignment_mode(self, mode):
+        """Ctx.alignment_mode on every context"""
+        rc = lib().dsb_multi_alignment_mode(self.h, int(mode))
+        if rc != 0:
+            raise DsbError(rc, "dsb_multi_alignment_mode")
 
     def alignment(self, n_hits):
         """Ctx.alignment for the last classify(): one record per hit of its result, ops_off rebased into the one array"""
@@ -1016,6 +1037,15 @@ def _alignment(fn, h, n_hits, what):
     if n.value:
         C.memmove(ops.ctypes.data, po, n.value * 4)
     return recs, ops
+
+
+def aln_plan(n, m, band=DSB_IDENT_BAND_DEFAULT, max_permille=DSB_IDENT_PERMILLE_DEFAULT, trace_kib=DSB_ALN_TRACE_KIB_DEFAULT):
+    """dsb_aln_plan: the plan of an n x m pair in checkpoint mode, (K, n_ckpt), or None where it has none"""
+    K, n_ck = C.c_uint32(0), C.c_uint32(0)
+    rc = lib().dsb_aln_plan(int(n), int(m), int(band), int(max_permille), int(trace_kib), C.byref(K), C.byref(n_ck))
+    if rc < 0:
+        raise DsbError(rc, "dsb_aln_plan")
+    return (K.value, n_ck.value) if rc else None
 
 
 def aligned_sam_header(index):

@@ -955,7 +955,8 @@ static void usage(void)
 	fprintf(stderr, "    --cigar-sam FILE  keep the path of those alignments and write FILE as SAM with a header: one line per primary and supplementary\n");
 	fprintf(stderr, "                     record with a base-level CIGAR (= X I D), 1-based POS, SEQ on the aligned strand and NM:i (--identity-band and\n");
 	fprintf(stderr, "                     --identity-max-frac apply; a record without a path has CIGAR * and xa:i:<flags>)\n");
-	fprintf(stderr, "    --cigar-trace-kib N  KiB of trace per wavefront, 1 <= N <= 65536 [2048]; a record whose edits need more gets no path\n\n");
+	fprintf(stderr, "    --cigar-trace-kib N  KiB of trace per wavefront, 1 <= N <= 65536 [2048]; a record whose edits need more gets no path\n");
+	fprintf(stderr, "    --cigar-checkpoint  keep every K-th generation and recompute the path in segments: long reads get a path in the same trace room\n\n");
 }
 
 static double now(void) { struct timeval tv; gettimeofday(&tv, NULL); return tv.tv_sec + tv.tv_usec * 1e-6; }
@@ -1030,11 +1031,12 @@ static int classify_main(int argc, char **argv)
 	                                              {"identity", required_argument, NULL, 14}, {"identity-refs", required_argument, NULL, 15},
 	                                              {"identity-band", required_argument, NULL, 16}, {"identity-max-frac", required_argument, NULL, 17},
 	                                              {"cigar-sam", required_argument, NULL, 18}, {"cigar-trace-kib", required_argument, NULL, 19},
+	                                              {"cigar-checkpoint", no_argument, NULL, 20},
 	                                              {NULL, 0, NULL, 0}};
 	const char *tax_path = NULL, *rep_path[2] = {NULL, NULL}, *cov_path = NULL, *ab_path = NULL, *kr_path = NULL, *krep_path = NULL, *names_path = NULL, *abr_path = NULL, *covw_path = NULL;
 	uint32_t ab_permille = 950, lca_permille = 950, cov_window = 1000; int lca_frac_set = 0, cov_window_set = 0;
 	const char *id_path = NULL, *idr_path = NULL; uint32_t id_band = DSB_IDENT_BAND_DEFAULT, id_permille = DSB_IDENT_PERMILLE_DEFAULT; int id_opt_set = 0;
-	const char *cig_path = NULL; uint32_t cig_trace_kib = DSB_ALN_TRACE_KIB_DEFAULT; int cig_opt_set = 0;
+	const char *cig_path = NULL; uint32_t cig_trace_kib = DSB_ALN_TRACE_KIB_DEFAULT; int cig_opt_set = 0, cig_ckpt = 0;
 	while ((c = getopt_long(argc, argv, "ht:l:r:f:o:s:g:", long_opts, NULL)) >= 0) {
 		if (c == 'h') { usage(); return 0; }
 		else if (c == 1) tax_path = optarg;
@@ -1079,6 +1081,7 @@ static int classify_main(int argc, char **argv)
 			if (e == optarg || *e || v < 1 || v > DSB_ALN_TRACE_KIB_MAX) die("[classify] --cigar-trace-kib takes a number of KiB N with 1 <= N <= 65536");
 			cig_trace_kib = (uint32_t)v; cig_opt_set = 1;
 		}
+		else if (c == 20) cig_ckpt = 1;
 		else if (c == '?' && optopt == 11) die("[classify] --abundance-reads takes a file name");   /* (last on the line: getopt_long found no argument) */
 		else if (c == 't') { /* thread count: accepted for compatibility, unused */ }
 		else if (c == 'l') a.o.L_min_matching = atoi(optarg);
@@ -1117,6 +1120,7 @@ static int classify_main(int argc, char **argv)
 	if (cov_window_set && !covw_path) die("[classify] --coverage-window-size needs --coverage-windows FILE");
 	if (id_opt_set && !id_path && !idr_path && !cig_path) die("[classify] --identity-band and --identity-max-frac need --identity FILE, --identity-refs FILE or --cigar-sam FILE");
 	if (cig_opt_set && !cig_path) die("[classify] --cigar-trace-kib needs --cigar-sam FILE");
+	if (cig_ckpt && !cig_path) die("[classify] --cigar-checkpoint needs --cigar-sam FILE");
 	a.lca_on = kr_path || krep_path;
 	a.ident_on = id_path || idr_path || cig_path;
 	dsb_taxnames *names = NULL;
@@ -1167,6 +1171,7 @@ static int classify_main(int argc, char **argv)
 	if (a.ident_on && (rc = dsb_multi_enable_identity(a.multi, 1, id_band, id_permille))) { fprintf(stderr, "\n[dsb_ctx_enable_identity] %s\n", dsb_strerror(rc)); exit(1); }
 	if (a.cg_out) {
 		if ((rc = dsb_multi_enable_alignment(a.multi, 1, cig_trace_kib, 0))) { fprintf(stderr, "\n[dsb_ctx_enable_alignment] %s\n", dsb_strerror(rc)); exit(1); }
+		if (cig_ckpt && (rc = dsb_multi_alignment_mode(a.multi, DSB_ALN_MODE_CHECKPOINT))) { fprintf(stderr, "\n[dsb_ctx_alignment_mode] %s\n", dsb_strerror(rc)); exit(1); }
 		size_t cap = 1 << 14; char *buf = NULL; long w;
 		do { cap *= 4; buf = xrealloc(buf, cap); w = dsb_aligned_sam_header(a.idx, buf, cap); } while (w < 0);
 		if (fwrite(buf, 1, (size_t)w, a.cg_out) != (size_t)w) die("[classify] cannot write the aligned SAM");

@@ -24,7 +24,8 @@ struct DsbIdent {
 	// (identity_release frees both).  d_trace: trace_kib KiB per wavefront of the grid, the bit planes of k_hit_align's move codes;
 	// d_aln: one record per entry of the hit buffer; d_ops: the batch's operation array (ops_room operations: ops_fixed, or sized
 	// per batch); d_ops_used: the operations the batch's records reserved.  aln_run: the last batch ran with alignment on.
-	uint64_t *d_trace = nullptr; uint32_t trace_kib = 0;
+	// aln_mode (dsb_ctx_alignment_mode): k_hit_align, or k_hit_align_ck dividing the same trace place by the record's plan.
+	uint64_t *d_trace = nullptr; uint32_t trace_kib = 0, aln_mode = DSB_ALN_MODE_FULL;
 	dsb_hit_alignment *d_aln = nullptr; size_t cap_aln = 0;
 	uint32_t *d_ops = nullptr; size_t cap_ops = 0; uint64_t ops_fixed = 0, ops_room = 0;
 	unsigned long long *d_ops_used = nullptr;

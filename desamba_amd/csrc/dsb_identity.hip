@@ -1,7 +1,9 @@
 // Per-hit edit distance and per-reference identity (dsb_identity.h): the banded alignment of every counted record of a
 // batch, one wavefront per record, after the batch's last classify launch; the run's per-reference table; the bare-pair entry
 // dsb_ctx_edit_pairs, which runs the same device function on sequences of the caller's.  With dsb_ctx_enable_alignment the
-// same pass also keeps the path: k_hit_align in place of k_hit_edits, ident_path behind ident_wave<true>, dsb_ctx_align_pairs.
+// same pass also keeps the path: k_hit_align in place of k_hit_edits, ident_path behind the tracing form of ident_wave,
+// dsb_ctx_align_pairs.  In checkpoint mode (dsb_ctx_alignment_mode) k_hit_align_ck runs instead: the trace of one segment
+// of K generations, a checkpoint of every K-th generation, and a walk back that recomputes the earlier segments (ident_path_ck).
 //
 // The alignment is the diagonal-transition form of the banded unit-cost problem.  Diagonal k holds the cells (i, i + k), i bases of Q
 // against i + k bases of T; FR_e[k] is the largest i on diagonal k that e edits reach.  The band is a set of whole diagonals
@@ -55,16 +57,77 @@ DV int ident_slide(const IdentSeq &s, int i, int k)
 	return i;
 }
 
+// The plan of a record in checkpoint mode, stated once for the device and for dsb_aln_plan: how a trace place of
+// `room` bytes is divided for a pair of n x m bases.  A function of (n, m, band, permille, room) alone, never of the edits.  Sizes in
+// bytes: Rb the trace of a generation, C a checkpoint (a whole generation of FR, W + 2 ints), Mv a byte per move of the path; the
+// place holds the segment trace (K x Rb), then the checkpoints (n_ck x C), then the moves.  All three are multiples of 16.
+struct IdentPlan { uint32_t ok, K, n_ck, Rb, C, Mv; };
+DSB_HD IdentPlan ident_plan(uint32_t n, uint32_t m, uint32_t band, uint32_t permille, uint64_t room)
+{
+	IdentPlan p; p.ok = p.K = p.n_ck = 0;
+	const uint64_t skew = n > m ? n - m : m - n, W = skew + 2ull * band + 1u;
+	const uint64_t ecap = (uint64_t)(n > m ? n : m) * permille / 1000u;
+	const uint64_t Rb = 16u * ((W + 63u) / 64u), C = 16u * ((4u * (W + 2u) + 15u) / 16u), Mv = 16u * ((ecap + 15u) / 16u);
+	p.Rb = (uint32_t)Rb; p.C = (uint32_t)C; p.Mv = (uint32_t)Mv;
+	if (Mv > room) return p;
+	const uint64_t A = room - Mv;
+	if (ecap * Rb <= A) { p.K = (uint32_t)(ecap ? ecap : 1u); p.ok = 1; return p; }        // one pass, no checkpoint
+	const uint64_t K = A / 2u / Rb;
+	if (K < 1) return p;
+	const uint64_t n_ck = (ecap - 1u) / K;                      // after generations K, 2K, .. < E_cap
+	if (n_ck * C > A - K * Rb) return p;
+	p.K = (uint32_t)K; p.n_ck = (uint32_t)n_ck; p.ok = 1;
+	return p;
+}
+
+// Generation e of the recurrence, prev -> cur over the diagonals [klo, khi]: lane l takes diagonals klo + l + 64 r.  Returns whether
+// diagonal delta reached n (wave-uniform).  TR with tracing (wave-uniform): every lane also holds the 2-bit code of the candidate it
+// chose (0 mismatch, 1 a base of T alone, 2 a base of Q alone, 3 none moved; lanes beyond khi: 3), and each round's two bit planes
+// (two ballots) go as 16 bytes to gen + 2 * round by one lane.
+template <bool TR>
+DV bool ident_gen(const IdentSeq &s, int n, int m, int delta, int lo, int klo, int khi, const int *prev, int *cur, int lane, bool tracing, uint64_t *gen)
+{
+	bool mine = false;
+	for (int k0 = klo; k0 <= khi; k0 += DSB_WAVE) {
+		const int k = k0 + lane;
+		uint32_t mv = 3;
+		if (k <= khi) {
+			const int x = k - lo + 1;
+			const int p = prev[x], pl = prev[x - 1], pr = prev[x + 1];
+			int c = p;
+			if (p >= 0 && p + 1 <= n && p + 1 + k <= m) { c = p + 1; mv = 0; }
+			if (pl >= 0 && pl + k <= m && pl > c) { c = pl; mv = 1; }
+			if (pr >= 0 && pr + 1 <= n && pr + 1 > c) { c = pr + 1; mv = 2; }
+			if (c >= 0) c = ident_slide(s, c, k);
+			cur[x] = c;
+			if (k == delta && c >= n) mine = true;
+		}
+		if constexpr (TR) {
+			if (tracing) {                                         // (wave-uniform: all lanes give their bit to both planes)
+				const uint64_t b0 = dsb_ballot64((mv & 1u) != 0), b1 = dsb_ballot64((mv & 2u) != 0);
+				if (lane == 0) { ulonglong2 v; v.x = b0; v.y = b1; *reinterpret_cast<ulonglong2 *>(gen) = v; }
+				gen += 2;
+			}
+		}
+	}
+	return dsb_ballot64(mine) != 0;
+}
+
 // One wavefront, one pair (all 64 lanes, wave-uniform arguments).  fr: two generations of half ints each, entry k - lo + 1 for
 // diagonal k with an unreached entry on either side of the band; both start unreached, and generation e writes the diagonals
-// [max(lo, -e), min(hi, e)], a superset of what generation e - 2 wrote into the same half.  Lane l takes diagonals klo + l + 64 r.
-// The loops are bounded by E_cap (edits), the band width (rounds) and n, m (slides).
-// TR (the tracing form, k_hit_align / k_pair_align): every lane also holds the 2-bit code of the candidate it chose (0
-// mismatch, 1 a base of T alone, 2 a base of Q alone, 3 none moved; lanes beyond khi: 3), and each round's two bit planes (two
-// ballots) go as 16 bytes to trace + (e - 1) * R + 16 * round, R = 16 * ceil(W / 64), by one lane -- while e * R <= room, so that
-// nothing is written beyond the place; after that the pass goes on as the plain form does.  The plain form compiles to what it was.
-template <bool TR>
-DV dsb_hit_identity ident_wave(const IdentSeq &s, uint32_t band, uint32_t permille, int *fr, uint32_t half, int lane, uint64_t *trace = nullptr, uint64_t room = 0)
+// [max(lo, -e), min(hi, e)], a superset of what generation e - 2 wrote into the same half.
+// The loops are bounded by E_cap (edits), the band width (rounds) and n, m (slides).  Three compile-time forms:
+// IDENT_PLAIN (k_hit_edits / k_pair_edits): the distance alone.
+// IDENT_TRACE (k_hit_align / k_pair_align): generation e is traced at trace + (e - 1) * R, R = 16 * ceil(W / 64) bytes --
+// while e * R <= room, so that nothing is written beyond the place; after that the pass goes on as the plain form does.
+// IDENT_CKPT (k_hit_align_ck / k_pair_align_ck), with a plan: generation e is traced at slot (e - 1) mod K of the
+// segment trace, and after a generation with e mod K == 0 and e < E_cap all lanes copy the new generation's W + 2 ints into the next
+// checkpoint, between two wave_syncs and before generation e + 1 overwrites slot 0.  Without a plan it runs as the plain form does.
+// The plain and the tracing form compile to what they were.
+enum { IDENT_PLAIN = 0, IDENT_TRACE = 1, IDENT_CKPT = 2 };
+template <int F>
+DV dsb_hit_identity ident_wave(const IdentSeq &s, uint32_t band, uint32_t permille, int *fr, uint32_t half, int lane, uint64_t *trace = nullptr, uint64_t room = 0,
+                               const IdentPlan *plan = nullptr)
 {
 	dsb_hit_identity o; o.edits = 0; o.q_len = s.n; o.t_len = s.m; o.flags = 0;
 	const int n = (int)s.n, m = (int)s.m, delta = m - n;
@@ -79,37 +142,30 @@ DV dsb_hit_identity ident_wave(const IdentSeq &s, uint32_t band, uint32_t permil
 	if (lane == 0) { v0 = ident_slide(s, 0, 0); prev[1 - lo] = v0; }
 	bool hit = dsb_ballot64(lane == 0 && delta == 0 && v0 >= n) != 0;
 	uint32_t e = 0;
+	uint32_t slot = 0;                                                  // (IDENT_CKPT) (e - 1) mod K of the generation to come
+	int *ck = nullptr;                                                  // (IDENT_CKPT) the next checkpoint
+	if constexpr (F == IDENT_CKPT) ck = reinterpret_cast<int *>(trace + ((uint64_t)plan->K * plan->Rb >> 3));
 	while (!hit && e < ecap) {
 		e++;
 		wave_sync();
 		const int klo = lo > -(int)e ? lo : -(int)e, khi = hi < (int)e ? hi : (int)e;
-		bool mine = false;
-		const uint32_t R = 2u * (uint32_t)((W + 63) / 64);            // (TR) a generation's trace, in 8-byte words
-		const bool tracing = TR && (uint64_t)e * R * 8u <= room;
-		uint64_t *gen = TR ? trace + (uint64_t)(e - 1) * R : nullptr;
-		for (int k0 = klo; k0 <= khi; k0 += DSB_WAVE) {
-			const int k = k0 + lane;
-			uint32_t mv = 3;
-			if (k <= khi) {
-				const int x = k - lo + 1;
-				const int p = prev[x], pl = prev[x - 1], pr = prev[x + 1];
-				int c = p;
-				if (p >= 0 && p + 1 <= n && p + 1 + k <= m) { c = p + 1; mv = 0; }
-				if (pl >= 0 && pl + k <= m && pl > c) { c = pl; mv = 1; }
-				if (pr >= 0 && pr + 1 <= n && pr + 1 > c) { c = pr + 1; mv = 2; }
-				if (c >= 0) c = ident_slide(s, c, k);
-				cur[x] = c;
-				if (k == delta && c >= n) mine = true;
-			}
-			if constexpr (TR) {
-				if (tracing) {                                         // (wave-uniform: all lanes give their bit to both planes)
-					const uint64_t b0 = dsb_ballot64((mv & 1u) != 0), b1 = dsb_ballot64((mv & 2u) != 0);
-					if (lane == 0) { ulonglong2 v; v.x = b0; v.y = b1; *reinterpret_cast<ulonglong2 *>(gen) = v; }
-					gen += 2;
+		const uint32_t R = 2u * (uint32_t)((W + 63) / 64);            // (tracing forms) a generation's trace, in 8-byte words
+		if constexpr (F == IDENT_CKPT) {
+			const bool tracing = plan->ok != 0;
+			hit = ident_gen<true>(s, n, m, delta, lo, klo, khi, prev, cur, lane, tracing, trace + (uint64_t)slot * R);
+			if (tracing && ++slot == plan->K) {
+				slot = 0;
+				if (e < ecap) {
+					wave_sync();
+					for (int x = lane; x < W + 2; x += DSB_WAVE) ck[x] = cur[x];
+					wave_sync();
+					ck += plan->C >> 2;
 				}
 			}
+		} else {
+			const bool tracing = F == IDENT_TRACE && (uint64_t)e * R * 8u <= room;
+			hit = ident_gen<F == IDENT_TRACE>(s, n, m, delta, lo, klo, khi, prev, cur, lane, tracing, F == IDENT_TRACE ? trace + (uint64_t)(e - 1) * R : nullptr);
 		}
-		hit = dsb_ballot64(mine) != 0;
 		int *t = prev; prev = cur; cur = t;
 	}
 	if (hit) { o.edits = e; if (e <= band) o.flags = DSB_IDENT_EXACT; }
@@ -140,7 +196,41 @@ struct IdentOps {
 	DV void flush() { if (len) out[cnt++] = len << 4 | op; len = 0; }
 };
 
-// After ident_wave<true> and a wave_sync, in wave-uniform control flow: all lanes run the same steps on the same values (what
+// The replay of a walked path, in wave-uniform control flow: the move of generation e is the byte at moves + (e - 1) * step.  The room
+// of the record's operations is reserved with one atomic (its bound, 2 E + 1); a move is applied only where the rectangle has the room
+// for it, and a replay that does not end on (n, m) gives a record without operations.
+DV dsb_hit_alignment ident_replay(const IdentSeq &s, uint32_t E, const uint8_t *moves, uint64_t step, uint32_t *ops, uint64_t ops_cap, unsigned long long *ops_used, int lane)
+{
+	dsb_hit_alignment a; a.ops_off = 0; a.n_ops = a.n_x = a.n_ins = a.n_del = a.flags = a.pad = 0;
+	const int n = (int)s.n, m = (int)s.m;
+	const uint64_t need = 2ull * E + 1u;
+	uint32_t off_lo = 0, off_hi = 0;
+	if (lane == 0) { const unsigned long long at = atomicAdd(ops_used, (unsigned long long)need); off_lo = (uint32_t)at; off_hi = (uint32_t)(at >> 32); }
+	const uint64_t off = (uint64_t)dsb_shfl(off_hi, 0) << 32 | dsb_shfl(off_lo, 0);
+	if (off > ops_cap || need > ops_cap - off) { a.flags = DSB_ALN_NOROOM; return a; }
+	IdentOps w; w.out = ops + off; w.cnt = 0; w.op = 0; w.len = 0;
+	int i = 0, k = 0;
+	bool good = true;
+	for (uint32_t e = 1; e <= E && good; e++) {
+		const int i2 = (int)DSB_RFL(ident_slide(s, i, k));
+		w.put(DSB_ALN_OP_EQ, (uint32_t)(i2 - i)); i = i2;
+		const uint32_t mv = DSB_RFL(moves[(uint64_t)(e - 1) * step]);
+		if (mv == 1u && i + k < m) { w.put(DSB_ALN_OP_D, 1); k++; a.n_del++; }
+		else if (mv == 2u && i < n) { w.put(DSB_ALN_OP_I, 1); i++; k--; a.n_ins++; }
+		else if (mv == 0u && i < n && i + k < m) { w.put(DSB_ALN_OP_X, 1); i++; a.n_x++; }
+		else good = false;
+	}
+	if (good) {
+		const int i2 = (int)DSB_RFL(ident_slide(s, i, k));
+		w.put(DSB_ALN_OP_EQ, (uint32_t)(i2 - i)); i = i2;
+		w.flush();
+	}
+	if (!good || i != n || i + k != m) { a.n_x = a.n_ins = a.n_del = 0; a.flags = DSB_ALN_NOTRACE; return a; }
+	a.ops_off = off; a.n_ops = w.cnt; a.flags = DSB_ALN_OPS;
+	return a;
+}
+
+// After ident_wave<IDENT_TRACE> and a wave_sync, in wave-uniform control flow: all lanes run the same steps on the same values (what
 // comes from memory goes through DSB_RFL, so the walk and the replay are scalar branches), and the stores are the same bytes from
 // every lane.  The walk back reads generation e = edits .. 1 at diagonal k (from d to 0), two words per step, and leaves the move
 // in the first byte of that generation's own 16 bytes -- read already, and below every generation still to be read.  Index
@@ -171,31 +261,73 @@ DV dsb_hit_alignment ident_path(const IdentSeq &s, uint32_t band, const dsb_hit_
 		k = klo + x + (mv == 2u ? 1 : 0) - (mv == 1u ? 1 : 0);
 	}
 	wave_sync();
-	const uint64_t need = 2ull * E + 1u;
-	uint32_t off_lo = 0, off_hi = 0;
-	if (lane == 0) { const unsigned long long at = atomicAdd(ops_used, (unsigned long long)need); off_lo = (uint32_t)at; off_hi = (uint32_t)(at >> 32); }
-	const uint64_t off = (uint64_t)dsb_shfl(off_hi, 0) << 32 | dsb_shfl(off_lo, 0);
-	if (off > ops_cap || need > ops_cap - off) { a.flags = DSB_ALN_NOROOM; return a; }
-	IdentOps w; w.out = ops + off; w.cnt = 0; w.op = 0; w.len = 0;
-	int i = 0; k = 0;
-	bool good = true;
-	for (uint32_t e = 1; e <= E && good; e++) {
-		const int i2 = (int)DSB_RFL(ident_slide(s, i, k));
-		w.put(DSB_ALN_OP_EQ, (uint32_t)(i2 - i)); i = i2;
-		const uint32_t mv = DSB_RFL(moves[(uint64_t)(e - 1) * R * 8u]);
-		if (mv == 1u && i + k < m) { w.put(DSB_ALN_OP_D, 1); k++; a.n_del++; }
-		else if (mv == 2u && i < n) { w.put(DSB_ALN_OP_I, 1); i++; k--; a.n_ins++; }
-		else if (mv == 0u && i < n && i + k < m) { w.put(DSB_ALN_OP_X, 1); i++; a.n_x++; }
-		else good = false;
+	return ident_replay(s, E, moves, (uint64_t)R * 8u, ops, ops_cap, ops_used, lane);
+}
+
+// The moves of generations e_hi .. e_lo + 1 (one segment, traced at slot e - 1 - e_lo of the segment trace) into the move area,
+// from diagonal k on; returns the diagonal generation e_lo is left on.  ident_path's step: the diagonal clamped to the generation's own
+// [klo, khi], the move read through DSB_RFL, every lane storing the same byte.
+DV int ident_walk_seg(const uint64_t *seg, uint8_t *moves, uint32_t R, int lo, int hi, uint32_t e_lo, uint32_t e_hi, int k)
+{
+	for (uint32_t e = e_hi; e > e_lo; e--) {
+		const int klo = lo > -(int)e ? lo : -(int)e, khi = hi < (int)e ? hi : (int)e;
+		int x = k - klo;
+		if (x > khi - klo) x = khi - klo;
+		if (x < 0) x = 0;
+		const uint64_t *g = seg + (uint64_t)(e - 1u - e_lo) * R + 2u * ((uint32_t)x >> 6);
+		const uint64_t b0 = g[0], b1 = g[1];
+		const uint32_t mv = DSB_RFL((uint32_t)((b0 >> (x & 63)) & 1u) | (uint32_t)((b1 >> (x & 63)) & 1u) << 1);
+		moves[e - 1u] = (uint8_t)mv;
+		k = klo + x + (mv == 2u ? 1 : 0) - (mv == 1u ? 1 : 0);
 	}
-	if (good) {
-		const int i2 = (int)DSB_RFL(ident_slide(s, i, k));
-		w.put(DSB_ALN_OP_EQ, (uint32_t)(i2 - i)); i = i2;
-		w.flush();
+	return k;
+}
+
+// ident_path in checkpoint mode, after ident_wave<IDENT_CKPT> and a wave_sync, in wave-uniform control flow.  At the
+// hit the last segment, floor((edits - 1) / K), is still in the segment trace and is walked back as ident_path walks; each earlier
+// segment s is recomputed first: prev restored from checkpoint s - 1 (the initial state for s = 0), cur filled with IDENT_NEG -- a
+// generation reads up to two diagonals beyond what the one before wrote, which the forward pass has from the arrays' first fill and a
+// restore has not --, generations sK + 1 .. (s + 1)K traced again without a hit test, then walked from the diagonal the later segment
+// ended on.  The recurrence is deterministic, so these are the moves the forward pass chose.  Every index stays inside the place by
+// arithmetic alone: e <= edits <= E_cap <= Mv, the slot is < K, the checkpoint s - 1 < floor((edits - 1) / K) <= n_ck, the diagonal
+// is clamped.  The replay is ident_path's, the moves read at byte e - 1 of the move area.
+DV dsb_hit_alignment ident_path_ck(const IdentSeq &s, uint32_t band, const dsb_hit_identity &o, const IdentPlan &pl, int *fr, uint32_t half, uint64_t *trace,
+                                   uint32_t *ops, uint64_t ops_cap, unsigned long long *ops_used, int lane)
+{
+	dsb_hit_alignment a; a.ops_off = 0; a.n_ops = a.n_x = a.n_ins = a.n_del = a.flags = a.pad = 0;
+	if (o.flags & IDENT_BAD) { a.flags = DSB_ALN_UNALIGNED; return a; }
+	if (!pl.ok || s.n >= IDENT_MAX_RUN || s.m >= IDENT_MAX_RUN) { a.flags = DSB_ALN_NOTRACE; return a; }
+	const int n = (int)s.n, m = (int)s.m, delta = m - n;
+	const int lo = (delta < 0 ? delta : 0) - (int)band, hi = (delta > 0 ? delta : 0) + (int)band, W = hi - lo + 1;
+	const uint32_t R = 2u * (uint32_t)((W + 63) / 64), E = o.edits, K = pl.K;
+	const int *ckpt = reinterpret_cast<const int *>(trace + ((uint64_t)K * pl.Rb >> 3));
+	uint8_t *moves = reinterpret_cast<uint8_t *>(trace) + (uint64_t)K * pl.Rb + (uint64_t)pl.n_ck * pl.C;
+	int k = delta;
+	if (E) {
+		uint32_t seg = (E - 1u) / K;
+		k = ident_walk_seg(trace, moves, R, lo, hi, seg * K, E, k);
+		while (seg) {
+			seg--;
+			wave_sync();
+			int *prev = fr, *cur = fr + half;
+			const int *from = ckpt + (uint64_t)(seg ? seg - 1u : 0u) * (pl.C >> 2);
+			for (int x = lane; x < W + 2; x += DSB_WAVE) { prev[x] = seg ? from[x] : IDENT_NEG; cur[x] = IDENT_NEG; }
+			if (!seg) {
+				wave_sync();
+				if (lane == 0) prev[1 - lo] = ident_slide(s, 0, 0);
+			}
+			for (uint32_t e = seg * K + 1u; e <= (seg + 1u) * K; e++) {
+				wave_sync();
+				const int klo = lo > -(int)e ? lo : -(int)e, khi = hi < (int)e ? hi : (int)e;
+				ident_gen<true>(s, n, m, delta, lo, klo, khi, prev, cur, lane, true, trace + (uint64_t)(e - 1u - seg * K) * R);
+				int *t = prev; prev = cur; cur = t;
+			}
+			wave_sync();
+			k = ident_walk_seg(trace, moves, R, lo, hi, seg * K, (seg + 1u) * K, k);
+		}
 	}
-	if (!good || i != n || i + k != m) { a.n_x = a.n_ins = a.n_del = 0; a.flags = DSB_ALN_NOTRACE; return a; }
-	a.ops_off = off; a.n_ops = w.cnt; a.flags = DSB_ALN_OPS;
-	return a;
+	wave_sync();
+	return ident_replay(s, E, moves, 1u, ops, ops_cap, ops_used, lane);
 }
 
 // One lane per read, after the batch's last classify work: the records dsb_ref_coverage counts (dsb_sam_counted, among the hits
@@ -236,7 +368,7 @@ __global__ void __launch_bounds__(256) k_hit_edits(const DsbHitOut *__restrict__
 		IdentSeq s;
 		s.qw = pk + d.pk_off + (h.direction ? 0u : (d.len + 31u) / 32u + 1u); s.qbase = qs; s.n = qe > qs ? qe - qs : 0u;
 		s.tb = refbin; s.tbase = off + ts; s.m = te > ts ? (uint32_t)(te - ts) : 0u;
-		const dsb_hit_identity o = ident_wave<false>(s, band, permille, fr, stride / 2u, lane);
+		const dsb_hit_identity o = ident_wave<IDENT_PLAIN>(s, band, permille, fr, stride / 2u, lane);
 		rec[it.x] = o;                                          // (all lanes, the same value: ident_take)
 	}
 }
@@ -269,9 +401,43 @@ __global__ void __launch_bounds__(256) k_hit_align(const DsbHitOut *__restrict__
 		IdentSeq s;
 		s.qw = pk + d.pk_off + (h.direction ? 0u : (d.len + 31u) / 32u + 1u); s.qbase = qs; s.n = qe > qs ? qe - qs : 0u;
 		s.tb = refbin; s.tbase = off + ts; s.m = te > ts ? (uint32_t)(te - ts) : 0u;
-		const dsb_hit_identity o = ident_wave<true>(s, band, permille, fr, stride / 2u, lane, trace, A.room);
+		const dsb_hit_identity o = ident_wave<IDENT_TRACE>(s, band, permille, fr, stride / 2u, lane, trace, A.room);
 		wave_sync();
 		const dsb_hit_alignment a = ident_path(s, band, o, trace, A.room, A.ops, A.ops_cap, A.ops_used, lane);
+		rec[it.x] = o; A.aln[it.x] = a;                         // (all lanes, the same values)
+	}
+}
+
+// k_hit_align in checkpoint mode (dsb_ctx_alignment_mode): the same shell; the record's plan divides the wavefront's
+// trace place, the forward pass keeps one segment's trace and the checkpoints, ident_path_ck recomputes the earlier segments in the
+// wavefront's own arena place.  A record without a plan runs as k_hit_edits runs it.
+__global__ void __launch_bounds__(256) k_hit_align_ck(const DsbHitOut *__restrict__ hout, const DsbReadDesc *__restrict__ rd, const uint64_t *__restrict__ pk,
+                                                      const uint8_t *__restrict__ refbin, const DsbRefInfo *__restrict__ refinfo, uint32_t n_ref,
+                                                      const uint2 *__restrict__ list, unsigned int *cnt, uint32_t band, uint32_t permille, int *arena, uint32_t stride,
+                                                      dsb_hit_identity *__restrict__ rec, IdentAlnOut A)
+{
+	const int lane = (int)(threadIdx.x & 63u);
+	const size_t wave = blockIdx.x * 4u + (threadIdx.x >> 6);
+	int *fr = arena + wave * stride;
+	uint64_t *trace = A.trace + wave * (A.room / 8u);
+	const uint32_t total = cnt[0];
+	for (;;) {
+		const uint32_t w = ident_take(cnt + 1, lane);
+		if (w >= total) break;
+		const uint2 it = list[w];
+		const DsbHitOut h = hout[it.x];
+		const DsbReadDesc d = rd[it.y];
+		uint64_t ln = 0, off = 0;
+		if (h.ref_ID < n_ref) { const DsbRefInfo ri = refinfo[h.ref_ID]; ln = ri.seq_l; off = ri.seq_offset; }
+		const uint32_t qs = h.q_st < d.len ? h.q_st : d.len, qe = h.q_ed < d.len ? h.q_ed : d.len;
+		const uint64_t ts = h.t_st < ln ? h.t_st : ln, te = h.t_ed < ln ? h.t_ed : ln;
+		IdentSeq s;
+		s.qw = pk + d.pk_off + (h.direction ? 0u : (d.len + 31u) / 32u + 1u); s.qbase = qs; s.n = qe > qs ? qe - qs : 0u;
+		s.tb = refbin; s.tbase = off + ts; s.m = te > ts ? (uint32_t)(te - ts) : 0u;
+		const IdentPlan pl = ident_plan(s.n, s.m, band, permille, A.room);
+		const dsb_hit_identity o = ident_wave<IDENT_CKPT>(s, band, permille, fr, stride / 2u, lane, trace, A.room, &pl);
+		wave_sync();
+		const dsb_hit_alignment a = ident_path_ck(s, band, o, pl, fr, stride / 2u, trace, A.ops, A.ops_cap, A.ops_used, lane);
 		rec[it.x] = o; A.aln[it.x] = a;                         // (all lanes, the same values)
 	}
 }
@@ -343,7 +509,7 @@ __global__ void __launch_bounds__(256) k_pair_edits(const uint64_t *__restrict__
 		if (w >= n_pairs) break;
 		IdentSeq s;
 		s.qw = qw; s.qbase = q_off[w]; s.n = q_len[w]; s.tb = tb; s.tbase = t_off[w]; s.m = t_len[w];
-		const dsb_hit_identity o = ident_wave<false>(s, band, permille, fr, stride / 2u, lane);
+		const dsb_hit_identity o = ident_wave<IDENT_PLAIN>(s, band, permille, fr, stride / 2u, lane);
 		out[w] = o;                                             // (all lanes, the same value: ident_take)
 	}
 }
@@ -362,9 +528,31 @@ __global__ void __launch_bounds__(256) k_pair_align(const uint64_t *__restrict__
 		if (w >= n_pairs) break;
 		IdentSeq s;
 		s.qw = qw; s.qbase = q_off[w]; s.n = q_len[w]; s.tb = tb; s.tbase = t_off[w]; s.m = t_len[w];
-		const dsb_hit_identity o = ident_wave<true>(s, band, permille, fr, stride / 2u, lane, trace, A.room);
+		const dsb_hit_identity o = ident_wave<IDENT_TRACE>(s, band, permille, fr, stride / 2u, lane, trace, A.room);
 		wave_sync();
 		const dsb_hit_alignment a = ident_path(s, band, o, trace, A.room, A.ops, A.ops_cap, A.ops_used, lane);
+		out[w] = o; A.aln[w] = a;                               // (all lanes, the same values)
+	}
+}
+// and in checkpoint mode (dsb_ctx_align_pairs_mode): what k_hit_align_ck does to a record, on pair w
+__global__ void __launch_bounds__(256) k_pair_align_ck(const uint64_t *__restrict__ qw, const uint8_t *__restrict__ tb, const uint64_t *__restrict__ q_off,
+                                                       const uint32_t *__restrict__ q_len, const uint64_t *__restrict__ t_off, const uint32_t *__restrict__ t_len,
+                                                       uint32_t n_pairs, unsigned int *work, uint32_t band, uint32_t permille, int *arena, uint32_t stride,
+                                                       dsb_hit_identity *__restrict__ out, IdentAlnOut A)
+{
+	const int lane = (int)(threadIdx.x & 63u);
+	const size_t wave = blockIdx.x * 4u + (threadIdx.x >> 6);
+	int *fr = arena + wave * stride;
+	uint64_t *trace = A.trace + wave * (A.room / 8u);
+	for (;;) {
+		const uint32_t w = ident_take(work, lane);
+		if (w >= n_pairs) break;
+		IdentSeq s;
+		s.qw = qw; s.qbase = q_off[w]; s.n = q_len[w]; s.tb = tb; s.tbase = t_off[w]; s.m = t_len[w];
+		const IdentPlan pl = ident_plan(s.n, s.m, band, permille, A.room);
+		const dsb_hit_identity o = ident_wave<IDENT_CKPT>(s, band, permille, fr, stride / 2u, lane, trace, A.room, &pl);
+		wave_sync();
+		const dsb_hit_alignment a = ident_path_ck(s, band, o, pl, fr, stride / 2u, trace, A.ops, A.ops_cap, A.ops_used, lane);
 		out[w] = o; A.aln[w] = a;                               // (all lanes, the same values)
 	}
 }
@@ -387,7 +575,7 @@ static void alignment_release(dsb_ctx *c)
 	DsbIdent &d = c->ident;
 	hipFree(d.d_trace); hipFree(d.d_aln); hipFree(d.d_ops); hipFree(d.d_ops_used);
 	d.d_trace = nullptr; d.d_aln = nullptr; d.d_ops = nullptr; d.d_ops_used = nullptr;
-	d.cap_aln = d.cap_ops = 0; d.trace_kib = 0; d.ops_fixed = d.ops_room = 0; d.aln_run = false;
+	d.cap_aln = d.cap_ops = 0; d.trace_kib = 0; d.aln_mode = DSB_ALN_MODE_FULL; d.ops_fixed = d.ops_room = 0; d.aln_run = false;
 	std::vector<dsb_hit_alignment>().swap(d.h_aln); std::vector<uint32_t>().swap(d.h_ops);
 }
 
@@ -445,8 +633,24 @@ extern "C" int dsb_ctx_enable_alignment(dsb_ctx *c, int on, uint32_t trace_kib, 
 	    grow(&d.d_aln, &d.cap_aln, c->cap_hout)) {
 		alignment_release(c); (void)hipGetLastError(); return DSB_ENOMEM;
 	}
-	d.trace_kib = trace_kib; d.ops_fixed = ops_cap;
+	d.trace_kib = trace_kib; d.ops_fixed = ops_cap;               // (the mode: alignment_release left it at FULL)
 	return DSB_OK;
+}
+
+extern "C" int dsb_ctx_alignment_mode(dsb_ctx *c, uint32_t mode)
+{
+	if (!c || !c->ident.d_trace || (mode != DSB_ALN_MODE_FULL && mode != DSB_ALN_MODE_CHECKPOINT)) return DSB_EINVAL;
+	c->ident.aln_mode = mode;                                    // (host state alone: the next batch's launch reads it)
+	return DSB_OK;
+}
+
+extern "C" int dsb_aln_plan(uint32_t n, uint32_t m, uint32_t band, uint32_t max_permille, uint32_t trace_kib, uint32_t *K, uint32_t *n_ckpt)
+{
+	if (!K || !n_ckpt || n >= IDENT_MAX_RUN || m >= IDENT_MAX_RUN || band > DSB_IDENT_MAX_BAND || max_permille < 1 || max_permille > 1000 ||
+	    trace_kib < 1 || trace_kib > DSB_ALN_TRACE_KIB_MAX) return DSB_EINVAL;
+	const IdentPlan p = ident_plan(n, m, band, max_permille, (uint64_t)trace_kib * 1024u);
+	*K = p.K; *n_ckpt = p.n_ck;
+	return p.ok ? 1 : 0;
 }
 
 int identity_run(dsb_ctx *c, const DsbBatchView &b)
@@ -464,8 +668,8 @@ int identity_run(dsb_ctx *c, const DsbBatchView &b)
 		HIPCHK(hipMemsetAsync(d.d_aln, 0, b.cap_hout * sizeof(dsb_hit_alignment), b.st));
 		HIPCHK(hipMemsetAsync(d.d_ops_used, 0, sizeof(unsigned long long), b.st));
 		IdentAlnOut A; A.trace = d.d_trace; A.room = (uint64_t)d.trace_kib * 1024u; A.aln = d.d_aln; A.ops = d.d_ops; A.ops_cap = d.ops_room; A.ops_used = d.d_ops_used;
-		hipLaunchKernelGGL(k_hit_align, dim3(d.n_waves / 4), dim3(256), 0, b.st, b.hout, b.rd, b.pk, c->dx.refbin, c->dx.refinfo, (uint32_t)dsb_index_n_ref(c->idx),
-		                   (const uint2 *)d.d_list, d.d_cnt, d.band, d.permille, d.d_arena, d.stride, d.d_rec, A);
+		hipLaunchKernelGGL(d.aln_mode == DSB_ALN_MODE_CHECKPOINT ? k_hit_align_ck : k_hit_align, dim3(d.n_waves / 4), dim3(256), 0, b.st, b.hout, b.rd, b.pk, c->dx.refbin,
+		                   c->dx.refinfo, (uint32_t)dsb_index_n_ref(c->idx), (const uint2 *)d.d_list, d.d_cnt, d.band, d.permille, d.d_arena, d.stride, d.d_rec, A);
 		d.aln_run = true;
 	} else
 	hipLaunchKernelGGL(k_hit_edits, dim3(d.n_waves / 4), dim3(256), 0, b.st, b.hout, b.rd, b.pk, c->dx.refbin, c->dx.refinfo, (uint32_t)dsb_index_n_ref(c->idx),
@@ -549,6 +753,13 @@ extern "C" int dsb_multi_enable_alignment(dsb_multi *m, int on, uint32_t trace_k
 	return DSB_OK;
 }
 
+extern "C" int dsb_multi_alignment_mode(dsb_multi *m, uint32_t mode)
+{
+	if (!m || !m->aln_on || (mode != DSB_ALN_MODE_FULL && mode != DSB_ALN_MODE_CHECKPOINT)) return DSB_EINVAL;
+	for (dsb_ctx *c : m->ctx) if (int rc = dsb_ctx_alignment_mode(c, mode)) return rc;
+	return DSB_OK;
+}
+
 extern "C" int dsb_multi_alignment(dsb_multi *m, const dsb_hit_alignment **recs, const uint32_t **ops, uint64_t *n_ops)
 {
 	if (!m || !recs || !ops || !n_ops || !m->aln_on || !m->aln_ok) return DSB_EINVAL;
@@ -580,13 +791,13 @@ extern "C" int dsb_multi_ref_identity(dsb_multi *m, dsb_ref_identity *out)
 	return DSB_OK;
 }
 
-// dsb_ctx_edit_pairs, and with al dsb_ctx_align_pairs: the same packing and the same phases, k_pair_edits or its tracing twin
-struct IdentPairsAln { uint32_t trace_kib; dsb_hit_alignment *aln_out; uint32_t *ops_out; uint64_t ops_cap; uint64_t *ops_used; };
+// dsb_ctx_edit_pairs, and with al dsb_ctx_align_pairs(_mode): the same packing and the same phases, k_pair_edits or a tracing twin
+struct IdentPairsAln { uint32_t trace_kib, mode; dsb_hit_alignment *aln_out; uint32_t *ops_out; uint64_t ops_cap; uint64_t *ops_used; };
 static int ident_pairs(dsb_ctx *c, const uint8_t *q_codes, const uint64_t *q_off, const uint32_t *q_len, const uint8_t *t_codes, const uint64_t *t_off,
                        const uint32_t *t_len, size_t n_pairs, uint32_t band, uint32_t max_permille, dsb_hit_identity *out, const IdentPairsAln *al)
 {
 	if (!c || band > DSB_IDENT_MAX_BAND || max_permille < 1 || max_permille > 1000 || n_pairs > 0xffffffffu) return DSB_EINVAL;
-	if (al && (!al->ops_used || al->trace_kib < 1 || al->trace_kib > DSB_ALN_TRACE_KIB_MAX)) return DSB_EINVAL;
+	if (al && (!al->ops_used || al->trace_kib < 1 || al->trace_kib > DSB_ALN_TRACE_KIB_MAX || (al->mode != DSB_ALN_MODE_FULL && al->mode != DSB_ALN_MODE_CHECKPOINT))) return DSB_EINVAL;
 	if (al) *al->ops_used = 0;
 	if (!n_pairs) return DSB_OK;
 	if (!q_codes || !q_off || !q_len || !t_codes || !t_off || !t_len || !out || (al && (!al->aln_out || (!al->ops_out && al->ops_cap)))) return DSB_EINVAL;
@@ -630,7 +841,7 @@ static int ident_pairs(dsb_ctx *c, const uint8_t *q_codes, const uint64_t *q_off
 	hipLaunchKernelGGL(k_ident_pack_t, dim3((unsigned)((n_bytes + 255) / 256)), dim3(256), 0, st, (const uint8_t *)d_tc, nt, d_tb, n_bytes);
 	if (al) {
 		HIPCHK(hipMemsetAsync(A.ops_used, 0, sizeof(unsigned long long), st));
-		hipLaunchKernelGGL(k_pair_align, dim3(n_waves / 4), dim3(256), 0, st, (const uint64_t *)d_qw, (const uint8_t *)d_tb, (const uint64_t *)d_qo, (const uint32_t *)d_ql,
+		hipLaunchKernelGGL(al->mode == DSB_ALN_MODE_CHECKPOINT ? k_pair_align_ck : k_pair_align, dim3(n_waves / 4), dim3(256), 0, st, (const uint64_t *)d_qw, (const uint8_t *)d_tb, (const uint64_t *)d_qo, (const uint32_t *)d_ql,
 		                   (const uint64_t *)d_to, (const uint32_t *)d_tl, (uint32_t)n_pairs, d_work, band, max_permille, d_arena, stride, d_out, A);
 	} else
 	hipLaunchKernelGGL(k_pair_edits, dim3(n_waves / 4), dim3(256), 0, st, (const uint64_t *)d_qw, (const uint8_t *)d_tb, (const uint64_t *)d_qo, (const uint32_t *)d_ql,
@@ -660,7 +871,15 @@ extern "C" int dsb_ctx_align_pairs(dsb_ctx *c, const uint8_t *q_codes, const uin
                                    const uint32_t *t_len, size_t n_pairs, uint32_t band, uint32_t max_permille, uint32_t trace_kib,
                                    dsb_hit_identity *ident_out, dsb_hit_alignment *aln_out, uint32_t *ops_out, uint64_t ops_cap, uint64_t *ops_used)
 {
+	return dsb_ctx_align_pairs_mode(c, q_codes, q_off, q_len, t_codes, t_off, t_len, n_pairs, band, max_permille, trace_kib, DSB_ALN_MODE_FULL, ident_out, aln_out, ops_out,
+	                                ops_cap, ops_used);
+}
+
+extern "C" int dsb_ctx_align_pairs_mode(dsb_ctx *c, const uint8_t *q_codes, const uint64_t *q_off, const uint32_t *q_len, const uint8_t *t_codes, const uint64_t *t_off,
+                                        const uint32_t *t_len, size_t n_pairs, uint32_t band, uint32_t max_permille, uint32_t trace_kib, uint32_t mode,
+                                        dsb_hit_identity *ident_out, dsb_hit_alignment *aln_out, uint32_t *ops_out, uint64_t ops_cap, uint64_t *ops_used)
+{
 	if (trace_kib == 0) trace_kib = DSB_ALN_TRACE_KIB_DEFAULT;
-	IdentPairsAln al; al.trace_kib = trace_kib; al.aln_out = aln_out; al.ops_out = ops_out; al.ops_cap = ops_cap; al.ops_used = ops_used;
+	IdentPairsAln al; al.trace_kib = trace_kib; al.mode = mode; al.aln_out = aln_out; al.ops_out = ops_out; al.ops_cap = ops_cap; al.ops_used = ops_used;
 	return ident_pairs(c, q_codes, q_off, q_len, t_codes, t_off, t_len, n_pairs, band, max_permille, ident_out, &al);
 }

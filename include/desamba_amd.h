@@ -534,7 +534,7 @@ int  dsb_ctx_edit_pairs(dsb_ctx *ctx, const uint8_t *q_codes, const uint64_t *q_
  * gets DSB_ALN_NOTRACE. */
 typedef struct { uint64_t ops_off; uint32_t n_ops, n_x, n_ins, n_del, flags, pad; } dsb_hit_alignment;   /* n_x, n_ins, n_del: bases */
 #define DSB_ALN_OPS       1    /* n_ops operations at ops_off of the batch's operation array */
-#define DSB_ALN_NOTRACE   2    /* aligned, but edits x R is above the trace room: no path */
+#define DSB_ALN_NOTRACE   2    /* aligned, but edits x R is above the trace room, or, in checkpoint mode, no plan: no path */
 #define DSB_ALN_NOROOM    4    /* the batch's operation array was full: n_ops = 0.  Records take their room in the order their wavefronts
                                   finish, so WHICH records lose is not deterministic (that none loses is: see ops_cap) */
 #define DSB_ALN_UNALIGNED 8    /* the identity record is EMPTY, SKEW or OVER */
@@ -553,10 +553,35 @@ typedef struct { uint64_t ops_off; uint32_t n_ops, n_x, n_ins, n_del, flags, pad
  * operations.  An allocation that fails: DSB_ENOMEM, and alignment stays off.  off: freed; nothing is allocated or launched while off.
  * Turning identity off, or on again with another band, turns alignment off too. */
 int  dsb_ctx_enable_alignment(dsb_ctx *ctx, int on, uint32_t trace_kib, uint64_t ops_cap);
+/* Checkpoint mode: the same alignment -- every record that gets a path gets exactly the operations defined above --
+ * held in a fixed trace room.  The forward pass keeps the trace of one segment of K generations and the furthest-reaching values of
+ * every K-th generation (a checkpoint); after the hit the earlier segments are computed again from their checkpoints, one at a time,
+ * and walked back.  The price is a second forward pass.  WHICH records get a path follows the record's plan, known before the pass and
+ * a function of (n, m, band, max_permille, trace_kib) alone, never of the edits.  With W, E_cap as above, in bytes:
+ *   Rb = 16 ceil(W / 64) a generation's trace, C = 16 ceil(4 (W + 2) / 16) a checkpoint, Mv = 16 ceil(E_cap / 16) a byte per move,
+ *   room = trace_kib x 1024, A = room - Mv.
+ *   1. A < 0: no plan.  2. E_cap x Rb <= A: K = max(E_cap, 1), no checkpoint (one pass).  3. Otherwise K = floor(A / 2 / Rb); K < 1: no
+ *   plan.  4. n_ckpt = floor((E_cap - 1) / K) checkpoints, after generations K, 2K, .. < E_cap.  5. A plan iff n_ckpt x C <= A - K x Rb.
+ * An aligned record with a plan always gets a path (DSB_ALN_NOROOM and the 2^28 limit apply as ever); one without a plan gets
+ * DSB_ALN_NOTRACE, its forward pass running as it does without alignment.  The two modes are NOT nested: the full mode's rule looks at
+ * edits, the plan at E_cap, so a short record whose E_cap is far above its edits can have a path in full mode and no plan here (at
+ * trace_kib 1 and band 32, a 200 x 200 pair with 3 edits under a cap of 310 permille).  There is no fallback from one to the other.
+ * 50000 x 50750 bases at band 256 and 300 permille: K = 3253 with 4 checkpoints in the default 2048 KiB, where the full mode needs
+ * edits x 336 bytes. */
+#define DSB_ALN_MODE_FULL       0
+#define DSB_ALN_MODE_CHECKPOINT 1
+/* the plan of a pair of n x m bases: 1 with *K and *n_ckpt set, 0 for no plan; DSB_EINVAL for a length of 2^28 or more, band above
+ * DSB_IDENT_MAX_BAND, max_permille outside 1 .. 1000, trace_kib outside 1 .. DSB_ALN_TRACE_KIB_MAX or a null pointer.  Host only, no
+ * context: the function the kernels call. */
+int  dsb_aln_plan(uint32_t n, uint32_t m, uint32_t band, uint32_t max_permille, uint32_t trace_kib, uint32_t *K, uint32_t *n_ckpt);
+/* from the next batch on k_hit_align_ck (checkpoint) or k_hit_align (full) runs, in the trace arena dsb_ctx_enable_alignment made.
+ * DSB_EINVAL unless alignment is on and mode is one of the two.  dsb_ctx_enable_alignment always leaves the mode at FULL. */
+int  dsb_ctx_alignment_mode(dsb_ctx *ctx, uint32_t mode);
 /* the last batch: one record per hit of dsb_batch_fetch's hits (all zero for a hit that is not counted) and the operation array they
  * index (records lie there in any order, with gaps); valid until the next batch.  DSB_EINVAL before a batch ran with alignment on. */
 int  dsb_batch_alignment(dsb_ctx *ctx, const dsb_hit_alignment **recs, const uint32_t **ops, uint64_t *n_ops);
 int  dsb_multi_enable_alignment(dsb_multi *m, int on, uint32_t trace_kib, uint64_t ops_cap);
+int  dsb_multi_alignment_mode(dsb_multi *m, uint32_t mode);
 /* the last dsb_multi_classify_batch: records concatenated as dsb_multi_identity's, ops_off rebased into the one array */
 int  dsb_multi_alignment(dsb_multi *m, const dsb_hit_alignment **recs, const uint32_t **ops, uint64_t *n_ops);
 /* n_pairs bare alignments by the device functions of k_hit_align, beside dsb_ctx_edit_pairs: same packing, same phases, lengths
@@ -566,6 +591,11 @@ int  dsb_ctx_align_pairs(dsb_ctx *ctx, const uint8_t *q_codes, const uint64_t *q
                          const uint8_t *t_codes, const uint64_t *t_off, const uint32_t *t_len, size_t n_pairs,
                          uint32_t band, uint32_t max_permille, uint32_t trace_kib,
                          dsb_hit_identity *ident_out, dsb_hit_alignment *aln_out, uint32_t *ops_out, uint64_t ops_cap, uint64_t *ops_used);
+/* dsb_ctx_align_pairs (which means DSB_ALN_MODE_FULL) with the mode: DSB_ALN_MODE_CHECKPOINT runs k_pair_align_ck */
+int  dsb_ctx_align_pairs_mode(dsb_ctx *ctx, const uint8_t *q_codes, const uint64_t *q_off, const uint32_t *q_len,
+                              const uint8_t *t_codes, const uint64_t *t_off, const uint32_t *t_len, size_t n_pairs,
+                              uint32_t band, uint32_t max_permille, uint32_t trace_kib, uint32_t mode,
+                              dsb_hit_identity *ident_out, dsb_hit_alignment *aln_out, uint32_t *ops_out, uint64_t ops_cap, uint64_t *ops_used);
 /* SAM with base-level CIGARs.  Header: @HD VN:1.6 SO:unknown, one @SQ SN LN per reference in ref_ID order, @PG ID:desamba_amd.
  * A read: one line per counted record, in record order (secondaries are not printed; hits, ident and aln: the read's own, rr->n of
  * each; ops: the batch's array):  QNAME FLAG RNAME POS MAPQ CIGAR * 0 0 SEQ QUAL NM:i:edits AS:i:sum_score  -- FLAG and MAPQ as

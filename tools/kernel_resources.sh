@@ -1,7 +1,8 @@
 #!/bin/bash
 # Register / scratch / LDS use of every kernel (compiler remarks; device-only compile, nothing is written into the tree).
 # dsb_gpu.hip is compiled as its six units side by side (DSB_KUNIT), as the library is, and dsb_reductions.hip and dsb_identity.hip
-# (k_ident_list, k_hit_edits, k_ident_ref, k_pair_edits, their tracing twins k_hit_align and k_pair_align, and the two pack kernels)
+# (k_ident_list, k_hit_edits, k_ident_ref, k_pair_edits, their tracing twins k_hit_align and k_pair_align, the checkpointed
+# k_hit_align_ck and k_pair_align_ck, and the two pack kernels)
 # beside them.
 # usage: tools/kernel_resources.sh [csrc-dir] [hipcc flags...]
 src=${1:-$(dirname "$0")/../desamba_amd/csrc}; shift
