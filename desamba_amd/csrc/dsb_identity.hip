@@ -57,17 +57,38 @@ DV int ident_slide(const IdentSeq &s, int i, int k)
 	return i;
 }
 
+// The band of a pair of n x m bases, stated once for the forward pass, the walk back, the recomputation and ident_plan: d = m - n,
+// the diagonals [lo, hi], W of them, and R, the 8-byte words of a generation's trace (two bit planes per round of 64 diagonals:
+// 16 * ceil(W / 64) bytes, the R of DESIGN 2.13, are 8 * R).  Generation e writes the diagonals [klo(e), khi(e)] = [max(lo, -e),
+// min(hi, e)].  All of it is wave-uniform.  (ints, as the furthest-reaching points are: right for n, m <= 2^30, which dsb_aln_plan
+// and the pair entries check.)  Passed by value: behind a reference the loops that store ints would have to read its fields again,
+// which costs two vector registers in every kernel.
+struct IdentBand {
+	int delta, lo, hi, W; uint32_t R;
+	DSB_HD int klo(uint32_t e) const { return lo > -(int)e ? lo : -(int)e; }
+	DSB_HD int khi(uint32_t e) const { return hi < (int)e ? hi : (int)e; }
+};
+DSB_HD IdentBand ident_band(uint32_t n, uint32_t m, uint32_t band)
+{
+	IdentBand b; const int delta = (int)m - (int)n;
+	b.delta = delta; b.lo = (delta < 0 ? delta : 0) - (int)band; b.hi = (delta > 0 ? delta : 0) + (int)band; b.W = b.hi - b.lo + 1;
+	b.R = 2u * (uint32_t)((b.W + 63) / 64);
+	return b;
+}
+
 // The plan of a record in checkpoint mode, stated once for the device and for dsb_aln_plan: how a trace place of
 // `room` bytes is divided for a pair of n x m bases.  A function of (n, m, band, permille, room) alone, never of the edits.  Sizes in
-// bytes: Rb the trace of a generation, C a checkpoint (a whole generation of FR, W + 2 ints), Mv a byte per move of the path; the
-// place holds the segment trace (K x Rb), then the checkpoints (n_ck x C), then the moves.  All three are multiples of 16.
+// bytes: Rb the trace of a generation (the band's 8 * R), C a checkpoint (a whole generation of FR, W + 2 ints), Mv a byte per move
+// of the path; the place holds the segment trace (K x Rb), then the checkpoints (n_ck x C), then the moves.  All three are multiples
+// of 16.
 struct IdentPlan { uint32_t ok, K, n_ck, Rb, C, Mv; };
 DSB_HD IdentPlan ident_plan(uint32_t n, uint32_t m, uint32_t band, uint32_t permille, uint64_t room)
 {
 	IdentPlan p; p.ok = p.K = p.n_ck = 0;
-	const uint64_t skew = n > m ? n - m : m - n, W = skew + 2ull * band + 1u;
+	const IdentBand b = ident_band(n, m, band);
+	const uint64_t W = (uint64_t)b.W, Rb = 8ull * b.R;
 	const uint64_t ecap = (uint64_t)(n > m ? n : m) * permille / 1000u;
-	const uint64_t Rb = 16u * ((W + 63u) / 64u), C = 16u * ((4u * (W + 2u) + 15u) / 16u), Mv = 16u * ((ecap + 15u) / 16u);
+	const uint64_t C = 16u * ((4u * (W + 2u) + 15u) / 16u), Mv = 16u * ((ecap + 15u) / 16u);
 	p.Rb = (uint32_t)Rb; p.C = (uint32_t)C; p.Mv = (uint32_t)Mv;
 	if (Mv > room) return p;
 	const uint64_t A = room - Mv;
@@ -80,19 +101,20 @@ DSB_HD IdentPlan ident_plan(uint32_t n, uint32_t m, uint32_t band, uint32_t perm
 	return p;
 }
 
-// Generation e of the recurrence, prev -> cur over the diagonals [klo, khi]: lane l takes diagonals klo + l + 64 r.  Returns whether
-// diagonal delta reached n (wave-uniform).  TR with tracing (wave-uniform): every lane also holds the 2-bit code of the candidate it
-// chose (0 mismatch, 1 a base of T alone, 2 a base of Q alone, 3 none moved; lanes beyond khi: 3), and each round's two bit planes
-// (two ballots) go as 16 bytes to gen + 2 * round by one lane.
+// Generation e of the recurrence, prev -> cur over the diagonals [klo, khi] of e: lane l takes diagonals klo + l + 64 r.  Returns
+// whether diagonal delta reached n (wave-uniform).  TR with tracing (wave-uniform): every lane also holds the 2-bit code of the
+// candidate it chose (0 mismatch, 1 a base of T alone, 2 a base of Q alone, 3 none moved; lanes beyond khi: 3), and each round's two
+// bit planes (two ballots) go as 16 bytes to gen + 2 * round by one lane.
 template <bool TR>
-DV bool ident_gen(const IdentSeq &s, int n, int m, int delta, int lo, int klo, int khi, const int *prev, int *cur, int lane, bool tracing, uint64_t *gen)
+DV bool ident_gen(const IdentSeq &s, const IdentBand b, uint32_t e, const int *prev, int *cur, int lane, bool tracing, uint64_t *gen)
 {
+	const int n = (int)s.n, m = (int)s.m, delta = b.delta, klo = b.klo(e), khi = b.khi(e);
 	bool mine = false;
 	for (int k0 = klo; k0 <= khi; k0 += DSB_WAVE) {
 		const int k = k0 + lane;
 		uint32_t mv = 3;
 		if (k <= khi) {
-			const int x = k - lo + 1;
+			const int x = k - b.lo + 1;
 			const int p = prev[x], pl = prev[x - 1], pr = prev[x + 1];
 			int c = p;
 			if (p >= 0 && p + 1 <= n && p + 1 + k <= m) { c = p + 1; mv = 0; }
@@ -113,6 +135,17 @@ DV bool ident_gen(const IdentSeq &s, int n, int m, int delta, int lo, int klo, i
 	return dsb_ballot64(mine) != 0;
 }
 
+// The initial state, of the forward pass and of a recomputed segment 0: both generations unreached (each with its unreached entry on
+// either side of the band), then lane 0 slides on diagonal 0.  Returns what that slide reached, in lane 0 alone.
+DV int ident_start(const IdentSeq &s, const IdentBand b, int *prev, int *cur, int lane)
+{
+	for (int x = lane; x < b.W + 2; x += DSB_WAVE) { prev[x] = IDENT_NEG; cur[x] = IDENT_NEG; }
+	wave_sync();
+	int v0 = IDENT_NEG;
+	if (lane == 0) { v0 = ident_slide(s, 0, 0); prev[1 - b.lo] = v0; }
+	return v0;
+}
+
 // One wavefront, one pair (all 64 lanes, wave-uniform arguments).  fr: two generations of half ints each, entry k - lo + 1 for
 // diagonal k with an unreached entry on either side of the band; both start unreached, and generation e writes the diagonals
 // [max(lo, -e), min(hi, e)], a superset of what generation e - 2 wrote into the same half.
@@ -126,21 +159,17 @@ DV bool ident_gen(const IdentSeq &s, int n, int m, int delta, int lo, int klo, i
 // The plain and the tracing form compile to what they were.
 enum { IDENT_PLAIN = 0, IDENT_TRACE = 1, IDENT_CKPT = 2 };
 template <int F>
-DV dsb_hit_identity ident_wave(const IdentSeq &s, uint32_t band, uint32_t permille, int *fr, uint32_t half, int lane, uint64_t *trace = nullptr, uint64_t room = 0,
-                               const IdentPlan *plan = nullptr)
+DV dsb_hit_identity ident_wave(const IdentSeq &s, const IdentBand b, uint32_t band, uint32_t permille, int *fr, uint32_t half, int lane, uint64_t *trace, uint64_t room,
+                               const IdentPlan *plan)
 {
 	dsb_hit_identity o; o.edits = 0; o.q_len = s.n; o.t_len = s.m; o.flags = 0;
-	const int n = (int)s.n, m = (int)s.m, delta = m - n;
+	const int n = (int)s.n, m = (int)s.m;
 	if (!n || !m) { o.flags = DSB_IDENT_EMPTY; return o; }
-	if (delta > DSB_IDENT_MAX_SKEW || delta < -DSB_IDENT_MAX_SKEW) { o.flags = DSB_IDENT_SKEW; return o; }
-	const int lo = (delta < 0 ? delta : 0) - (int)band, hi = (delta > 0 ? delta : 0) + (int)band, W = hi - lo + 1;
+	if (b.delta > DSB_IDENT_MAX_SKEW || b.delta < -DSB_IDENT_MAX_SKEW) { o.flags = DSB_IDENT_SKEW; return o; }
 	const uint32_t ecap = (uint32_t)((uint64_t)(n > m ? n : m) * permille / 1000u);
 	int *prev = fr, *cur = fr + half;
-	for (int x = lane; x < W + 2; x += DSB_WAVE) { prev[x] = IDENT_NEG; cur[x] = IDENT_NEG; }
-	wave_sync();
-	int v0 = IDENT_NEG;
-	if (lane == 0) { v0 = ident_slide(s, 0, 0); prev[1 - lo] = v0; }
-	bool hit = dsb_ballot64(lane == 0 && delta == 0 && v0 >= n) != 0;
+	const int v0 = ident_start(s, b, prev, cur, lane);
+	bool hit = dsb_ballot64(lane == 0 && b.delta == 0 && v0 >= n) != 0;
 	uint32_t e = 0;
 	uint32_t slot = 0;                                                  // (IDENT_CKPT) (e - 1) mod K of the generation to come
 	int *ck = nullptr;                                                  // (IDENT_CKPT) the next checkpoint
@@ -148,23 +177,21 @@ DV dsb_hit_identity ident_wave(const IdentSeq &s, uint32_t band, uint32_t permil
 	while (!hit && e < ecap) {
 		e++;
 		wave_sync();
-		const int klo = lo > -(int)e ? lo : -(int)e, khi = hi < (int)e ? hi : (int)e;
-		const uint32_t R = 2u * (uint32_t)((W + 63) / 64);            // (tracing forms) a generation's trace, in 8-byte words
 		if constexpr (F == IDENT_CKPT) {
 			const bool tracing = plan->ok != 0;
-			hit = ident_gen<true>(s, n, m, delta, lo, klo, khi, prev, cur, lane, tracing, trace + (uint64_t)slot * R);
+			hit = ident_gen<true>(s, b, e, prev, cur, lane, tracing, trace + (uint64_t)slot * b.R);
 			if (tracing && ++slot == plan->K) {
 				slot = 0;
 				if (e < ecap) {
 					wave_sync();
-					for (int x = lane; x < W + 2; x += DSB_WAVE) ck[x] = cur[x];
+					for (int x = lane; x < b.W + 2; x += DSB_WAVE) ck[x] = cur[x];
 					wave_sync();
 					ck += plan->C >> 2;
 				}
 			}
 		} else {
-			const bool tracing = F == IDENT_TRACE && (uint64_t)e * R * 8u <= room;
-			hit = ident_gen<F == IDENT_TRACE>(s, n, m, delta, lo, klo, khi, prev, cur, lane, tracing, F == IDENT_TRACE ? trace + (uint64_t)(e - 1) * R : nullptr);
+			const bool tracing = F == IDENT_TRACE && (uint64_t)e * b.R * 8u <= room;
+			hit = ident_gen<F == IDENT_TRACE>(s, b, e, prev, cur, lane, tracing, F == IDENT_TRACE ? trace + (uint64_t)(e - 1) * b.R : nullptr);
 		}
 		int *t = prev; prev = cur; cur = t;
 	}
@@ -184,6 +211,16 @@ DV uint32_t ident_take(unsigned int *work, int lane)
 }
 
 // ---- the path of a record: walk back through the traced moves, replay forward, emit run-length operations ----
+// Where a trace arena lies and where operations go (the tracing kernels): wavefront w owns trace[w * room / 8 .. + room / 8)
+struct IdentAlnOut { uint64_t *trace; uint64_t room; dsb_hit_alignment *aln; uint32_t *ops; uint64_t ops_cap; unsigned long long *ops_used; };
+
+// the record of a hit without operations, with the flag that says why
+DV dsb_hit_alignment ident_no_path(uint32_t flags)
+{
+	dsb_hit_alignment a; a.ops_off = 0; a.n_ops = a.n_x = a.n_ins = a.n_del = a.pad = 0; a.flags = flags;
+	return a;
+}
+
 // Appends to a record's operations, merging equal neighbours.  Every lane holds the same state and stores the same word.
 struct IdentOps {
 	uint32_t *out; uint32_t cnt, op, len;
@@ -199,16 +236,16 @@ struct IdentOps {
 // The replay of a walked path, in wave-uniform control flow: the move of generation e is the byte at moves + (e - 1) * step.  The room
 // of the record's operations is reserved with one atomic (its bound, 2 E + 1); a move is applied only where the rectangle has the room
 // for it, and a replay that does not end on (n, m) gives a record without operations.
-DV dsb_hit_alignment ident_replay(const IdentSeq &s, uint32_t E, const uint8_t *moves, uint64_t step, uint32_t *ops, uint64_t ops_cap, unsigned long long *ops_used, int lane)
+DV dsb_hit_alignment ident_replay(const IdentSeq &s, uint32_t E, const uint8_t *moves, uint64_t step, const IdentAlnOut &A, int lane)
 {
-	dsb_hit_alignment a; a.ops_off = 0; a.n_ops = a.n_x = a.n_ins = a.n_del = a.flags = a.pad = 0;
+	dsb_hit_alignment a = ident_no_path(0);
 	const int n = (int)s.n, m = (int)s.m;
 	const uint64_t need = 2ull * E + 1u;
 	uint32_t off_lo = 0, off_hi = 0;
-	if (lane == 0) { const unsigned long long at = atomicAdd(ops_used, (unsigned long long)need); off_lo = (uint32_t)at; off_hi = (uint32_t)(at >> 32); }
+	if (lane == 0) { const unsigned long long at = atomicAdd(A.ops_used, (unsigned long long)need); off_lo = (uint32_t)at; off_hi = (uint32_t)(at >> 32); }
 	const uint64_t off = (uint64_t)dsb_shfl(off_hi, 0) << 32 | dsb_shfl(off_lo, 0);
-	if (off > ops_cap || need > ops_cap - off) { a.flags = DSB_ALN_NOROOM; return a; }
-	IdentOps w; w.out = ops + off; w.cnt = 0; w.op = 0; w.len = 0;
+	if (off > A.ops_cap || need > A.ops_cap - off) { a.flags = DSB_ALN_NOROOM; return a; }
+	IdentOps w; w.out = A.ops + off; w.cnt = 0; w.op = 0; w.len = 0;
 	int i = 0, k = 0;
 	bool good = true;
 	for (uint32_t e = 1; e <= E && good; e++) {
@@ -230,57 +267,44 @@ DV dsb_hit_alignment ident_replay(const IdentSeq &s, uint32_t E, const uint8_t *
 	return a;
 }
 
-// After ident_wave<IDENT_TRACE> and a wave_sync, in wave-uniform control flow: all lanes run the same steps on the same values (what
-// comes from memory goes through DSB_RFL, so the walk and the replay are scalar branches), and the stores are the same bytes from
-// every lane.  The walk back reads generation e = edits .. 1 at diagonal k (from d to 0), two words per step, and leaves the move
-// in the first byte of that generation's own 16 bytes -- read already, and below every generation still to be read.  Index
-// arithmetic alone keeps every access inside the place: e <= edits with edits * R <= room, and the diagonal is clamped to
-// the generation's [klo, khi].  The replay applies a move only where the rectangle has the room for it and ends on (n, m); a trace
-// that does not (none was seen: the model of tests/align_lib.py asserts it cannot happen) gives a record without operations.
-// Loops: edits steps each, the slides bounded by n and m; at most 2 * edits + 1 operations, the room reserved with one atomic.
-DV dsb_hit_alignment ident_path(const IdentSeq &s, uint32_t band, const dsb_hit_identity &o, uint64_t *trace, uint64_t room,
-                                uint32_t *ops, uint64_t ops_cap, unsigned long long *ops_used, int lane)
-{
-	dsb_hit_alignment a; a.ops_off = 0; a.n_ops = a.n_x = a.n_ins = a.n_del = a.flags = a.pad = 0;
-	if (o.flags & IDENT_BAD) { a.flags = DSB_ALN_UNALIGNED; return a; }
-	const int n = (int)s.n, m = (int)s.m, delta = m - n;
-	const int lo = (delta < 0 ? delta : 0) - (int)band, hi = (delta > 0 ? delta : 0) + (int)band, W = hi - lo + 1;
-	const uint32_t R = 2u * (uint32_t)((W + 63) / 64), E = o.edits;
-	if ((uint64_t)E * R * 8u > room || s.n >= IDENT_MAX_RUN || s.m >= IDENT_MAX_RUN) { a.flags = DSB_ALN_NOTRACE; return a; }
-	uint8_t *moves = reinterpret_cast<uint8_t *>(trace);
-	int k = delta;
-	for (uint32_t e = E; e >= 1; e--) {
-		const int klo = lo > -(int)e ? lo : -(int)e, khi = hi < (int)e ? hi : (int)e;
-		int x = k - klo;
-		if (x > khi - klo) x = khi - klo;
-		if (x < 0) x = 0;
-		const uint64_t *g = trace + (uint64_t)(e - 1) * R + 2u * ((uint32_t)x >> 6);
-		const uint64_t b0 = g[0], b1 = g[1];
-		const uint32_t mv = DSB_RFL((uint32_t)((b0 >> (x & 63)) & 1u) | (uint32_t)((b1 >> (x & 63)) & 1u) << 1);
-		moves[(uint64_t)(e - 1) * R * 8u] = (uint8_t)mv;
-		k = klo + x + (mv == 2u ? 1 : 0) - (mv == 1u ? 1 : 0);
-	}
-	wave_sync();
-	return ident_replay(s, E, moves, (uint64_t)R * 8u, ops, ops_cap, ops_used, lane);
-}
-
-// The moves of generations e_hi .. e_lo + 1 (one segment, traced at slot e - 1 - e_lo of the segment trace) into the move area,
-// from diagonal k on; returns the diagonal generation e_lo is left on.  ident_path's step: the diagonal clamped to the generation's own
-// [klo, khi], the move read through DSB_RFL, every lane storing the same byte.
-DV int ident_walk_seg(const uint64_t *seg, uint8_t *moves, uint32_t R, int lo, int hi, uint32_t e_lo, uint32_t e_hi, int k)
+// The walk back, stated once: the moves of generations e_hi .. e_lo + 1, traced at slot e - 1 - e_lo of seg (R words each), from
+// diagonal k on; the move of generation e goes to the byte moves + (e - 1) * step.  Returns the diagonal generation e_lo is left on.
+// A step: the diagonal clamped to the generation's own [klo, khi], both planes read (two words), the move taken through DSB_RFL, then
+// the byte stored, the same from every lane -- in this order, because in the full mode the byte lands in the 16 bytes just read.
+DV int ident_walk_seg(const uint64_t *seg, uint8_t *moves, uint64_t step, const IdentBand b, uint32_t e_lo, uint32_t e_hi, int k)
 {
 	for (uint32_t e = e_hi; e > e_lo; e--) {
-		const int klo = lo > -(int)e ? lo : -(int)e, khi = hi < (int)e ? hi : (int)e;
+		const int klo = b.klo(e), khi = b.khi(e);
 		int x = k - klo;
 		if (x > khi - klo) x = khi - klo;
 		if (x < 0) x = 0;
-		const uint64_t *g = seg + (uint64_t)(e - 1u - e_lo) * R + 2u * ((uint32_t)x >> 6);
+		const uint64_t *g = seg + (uint64_t)(e - 1u - e_lo) * b.R + 2u * ((uint32_t)x >> 6);
 		const uint64_t b0 = g[0], b1 = g[1];
 		const uint32_t mv = DSB_RFL((uint32_t)((b0 >> (x & 63)) & 1u) | (uint32_t)((b1 >> (x & 63)) & 1u) << 1);
-		moves[e - 1u] = (uint8_t)mv;
+		moves[(uint64_t)(e - 1u) * step] = (uint8_t)mv;
 		k = klo + x + (mv == 2u ? 1 : 0) - (mv == 1u ? 1 : 0);
 	}
 	return k;
+}
+
+// After ident_wave<IDENT_TRACE> and a wave_sync, in wave-uniform control flow: all lanes run the same steps on the same values (what
+// comes from memory goes through DSB_RFL, so the walk and the replay are scalar branches), and the stores are the same bytes from
+// every lane.  The walk back reads generation e = edits .. 1 at diagonal k (from d to 0): the whole trace is its one segment, and
+// the move area is the trace itself at a step of 8 * R bytes, so a move lies in the first byte of that generation's own 16 bytes --
+// read already, and below every generation still to be read.  Index arithmetic alone keeps every access inside the place: e <= edits
+// with edits * R <= room, and the diagonal is clamped to the generation's [klo, khi].  The replay applies a move only where the
+// rectangle has the room for it and ends on (n, m); a trace that does not (none was seen: the model of tests/align_lib.py asserts it
+// cannot happen) gives a record without operations.
+// Loops: edits steps each, the slides bounded by n and m; at most 2 * edits + 1 operations, the room reserved with one atomic.
+DV dsb_hit_alignment ident_path(const IdentSeq &s, const IdentBand b, const dsb_hit_identity &o, uint64_t *trace, const IdentAlnOut &A, int lane)
+{
+	if (o.flags & IDENT_BAD) return ident_no_path(DSB_ALN_UNALIGNED);
+	const uint32_t E = o.edits;
+	if ((uint64_t)E * b.R * 8u > A.room || s.n >= IDENT_MAX_RUN || s.m >= IDENT_MAX_RUN) return ident_no_path(DSB_ALN_NOTRACE);
+	uint8_t *moves = reinterpret_cast<uint8_t *>(trace);
+	ident_walk_seg(trace, moves, (uint64_t)b.R * 8u, b, 0, E, b.delta);
+	wave_sync();
+	return ident_replay(s, E, moves, (uint64_t)b.R * 8u, A, lane);
 }
 
 // ident_path in checkpoint mode, after ident_wave<IDENT_CKPT> and a wave_sync, in wave-uniform control flow.  At the
@@ -291,43 +315,38 @@ DV int ident_walk_seg(const uint64_t *seg, uint8_t *moves, uint32_t R, int lo, i
 // ended on.  The recurrence is deterministic, so these are the moves the forward pass chose.  Every index stays inside the place by
 // arithmetic alone: e <= edits <= E_cap <= Mv, the slot is < K, the checkpoint s - 1 < floor((edits - 1) / K) <= n_ck, the diagonal
 // is clamped.  The replay is ident_path's, the moves read at byte e - 1 of the move area.
-DV dsb_hit_alignment ident_path_ck(const IdentSeq &s, uint32_t band, const dsb_hit_identity &o, const IdentPlan &pl, int *fr, uint32_t half, uint64_t *trace,
-                                   uint32_t *ops, uint64_t ops_cap, unsigned long long *ops_used, int lane)
+DV dsb_hit_alignment ident_path_ck(const IdentSeq &s, const IdentBand b, const dsb_hit_identity &o, const IdentPlan &pl, int *fr, uint32_t half, uint64_t *trace,
+                                   const IdentAlnOut &A, int lane)
 {
-	dsb_hit_alignment a; a.ops_off = 0; a.n_ops = a.n_x = a.n_ins = a.n_del = a.flags = a.pad = 0;
-	if (o.flags & IDENT_BAD) { a.flags = DSB_ALN_UNALIGNED; return a; }
-	if (!pl.ok || s.n >= IDENT_MAX_RUN || s.m >= IDENT_MAX_RUN) { a.flags = DSB_ALN_NOTRACE; return a; }
-	const int n = (int)s.n, m = (int)s.m, delta = m - n;
-	const int lo = (delta < 0 ? delta : 0) - (int)band, hi = (delta > 0 ? delta : 0) + (int)band, W = hi - lo + 1;
-	const uint32_t R = 2u * (uint32_t)((W + 63) / 64), E = o.edits, K = pl.K;
+	if (o.flags & IDENT_BAD) return ident_no_path(DSB_ALN_UNALIGNED);
+	if (!pl.ok || s.n >= IDENT_MAX_RUN || s.m >= IDENT_MAX_RUN) return ident_no_path(DSB_ALN_NOTRACE);
+	const uint32_t E = o.edits, K = pl.K;
 	const int *ckpt = reinterpret_cast<const int *>(trace + ((uint64_t)K * pl.Rb >> 3));
 	uint8_t *moves = reinterpret_cast<uint8_t *>(trace) + (uint64_t)K * pl.Rb + (uint64_t)pl.n_ck * pl.C;
-	int k = delta;
+	int k = b.delta;
 	if (E) {
 		uint32_t seg = (E - 1u) / K;
-		k = ident_walk_seg(trace, moves, R, lo, hi, seg * K, E, k);
+		k = ident_walk_seg(trace, moves, 1u, b, seg * K, E, k);
 		while (seg) {
 			seg--;
 			wave_sync();
 			int *prev = fr, *cur = fr + half;
-			const int *from = ckpt + (uint64_t)(seg ? seg - 1u : 0u) * (pl.C >> 2);
-			for (int x = lane; x < W + 2; x += DSB_WAVE) { prev[x] = seg ? from[x] : IDENT_NEG; cur[x] = IDENT_NEG; }
-			if (!seg) {
-				wave_sync();
-				if (lane == 0) prev[1 - lo] = ident_slide(s, 0, 0);
-			}
+			if (seg) {
+				const int *from = ckpt + (uint64_t)(seg - 1u) * (pl.C >> 2);
+				for (int x = lane; x < b.W + 2; x += DSB_WAVE) { prev[x] = from[x]; cur[x] = IDENT_NEG; }
+			} else
+				ident_start(s, b, prev, cur, lane);
 			for (uint32_t e = seg * K + 1u; e <= (seg + 1u) * K; e++) {
 				wave_sync();
-				const int klo = lo > -(int)e ? lo : -(int)e, khi = hi < (int)e ? hi : (int)e;
-				ident_gen<true>(s, n, m, delta, lo, klo, khi, prev, cur, lane, true, trace + (uint64_t)(e - 1u - seg * K) * R);
+				ident_gen<true>(s, b, e, prev, cur, lane, true, trace + (uint64_t)(e - 1u - seg * K) * b.R);
 				int *t = prev; prev = cur; cur = t;
 			}
 			wave_sync();
-			k = ident_walk_seg(trace, moves, R, lo, hi, seg * K, (seg + 1u) * K, k);
+			k = ident_walk_seg(trace, moves, 1u, b, seg * K, (seg + 1u) * K, k);
 		}
 	}
 	wave_sync();
-	return ident_replay(s, E, moves, 1u, ops, ops_cap, ops_used, lane);
+	return ident_replay(s, E, moves, 1u, A, lane);
 }
 
 // One lane per read, after the batch's last classify work: the records dsb_ref_coverage counts (dsb_sam_counted, among the hits
@@ -345,19 +364,20 @@ __global__ void __launch_bounds__(256) k_ident_list(const DsbReadOut *__restrict
 		if (dsb_sam_counted(h + k, k)) { uint2 w; w.x = r.first + k; w.y = i; list[atomicAdd(cnt, 1u)] = w; }
 }
 
-// One wavefront per listed record, taken from the list by a work counter (cnt[1]) until it is empty.  The grid is as many wavefronts
-// as the arena has places for: wavefront w owns arena[w * stride .. + stride).
-__global__ void __launch_bounds__(256) k_hit_edits(const DsbHitOut *__restrict__ hout, const DsbReadDesc *__restrict__ rd, const uint64_t *__restrict__ pk,
-                                                   const uint8_t *__restrict__ refbin, const DsbRefInfo *__restrict__ refinfo, uint32_t n_ref,
-                                                   const uint2 *__restrict__ list, unsigned int *cnt, uint32_t band, uint32_t permille, int *arena, uint32_t stride,
-                                                   dsb_hit_identity *__restrict__ rec)
-{
-	const int lane = (int)(threadIdx.x & 63u);
-	int *fr = arena + (size_t)(blockIdx.x * 4u + (threadIdx.x >> 6)) * stride;
-	const uint32_t total = cnt[0];
-	for (;;) {
-		const uint32_t w = ident_take(cnt + 1, lane);
-		if (w >= total) break;
+// ---- the record loop, stated once: three forms x two sources ----
+// Where the wavefronts work, and with what: wavefront w owns arena[w * stride .. + stride), two generations of stride / 2 ints
+struct IdentRun { uint32_t band, permille; int *arena; uint32_t stride; };
+
+// A source says how many entries there are (total), where the work counter is (work), how entry w becomes an IdentSeq and which
+// output slot it writes (seq).  The batch's hit list: cnt[0] entries {hit, read} of k_ident_list, the counter in cnt[1]; the interval
+// of the hit clamped to its read and its reference, Q on the hit's strand (the reverse strand of a read lies one pad word behind the
+// forward one in pk), T in refbin; the slot is the hit's.
+struct IdentHits {
+	const DsbHitOut *hout; const DsbReadDesc *rd; const uint64_t *pk; const uint8_t *refbin; const DsbRefInfo *refinfo; uint32_t n_ref; const uint2 *list; unsigned int *cnt;
+	DV uint32_t total() const { return cnt[0]; }
+	DV unsigned int *work() const { return cnt + 1; }
+	DV uint32_t seq(uint32_t w, IdentSeq &s) const
+	{
 		const uint2 it = list[w];
 		const DsbHitOut h = hout[it.x];
 		const DsbReadDesc d = rd[it.y];
@@ -365,82 +385,70 @@ __global__ void __launch_bounds__(256) k_hit_edits(const DsbHitOut *__restrict__
 		if (h.ref_ID < n_ref) { const DsbRefInfo ri = refinfo[h.ref_ID]; ln = ri.seq_l; off = ri.seq_offset; }
 		const uint32_t qs = h.q_st < d.len ? h.q_st : d.len, qe = h.q_ed < d.len ? h.q_ed : d.len;
 		const uint64_t ts = h.t_st < ln ? h.t_st : ln, te = h.t_ed < ln ? h.t_ed : ln;
-		IdentSeq s;
 		s.qw = pk + d.pk_off + (h.direction ? 0u : (d.len + 31u) / 32u + 1u); s.qbase = qs; s.n = qe > qs ? qe - qs : 0u;
 		s.tb = refbin; s.tbase = off + ts; s.m = te > ts ? (uint32_t)(te - ts) : 0u;
-		const dsb_hit_identity o = ident_wave<IDENT_PLAIN>(s, band, permille, fr, stride / 2u, lane);
-		rec[it.x] = o;                                          // (all lanes, the same value: ident_take)
+		return it.x;
 	}
-}
-
-// Where a trace arena lies and where operations go (k_hit_align, k_pair_align): wavefront w owns trace[w * room / 8 .. + room / 8)
-struct IdentAlnOut { uint64_t *trace; uint64_t room; dsb_hit_alignment *aln; uint32_t *ops; uint64_t ops_cap; unsigned long long *ops_used; };
-
-// k_hit_edits with the path kept (dsb_ctx_enable_alignment): the same list, work counter and loop; one forward pass in the tracing
-// form, then the same wavefront walks back and replays (ident_path).  The identity record is the one k_hit_edits gives.
-__global__ void __launch_bounds__(256) k_hit_align(const DsbHitOut *__restrict__ hout, const DsbReadDesc *__restrict__ rd, const uint64_t *__restrict__ pk,
-                                                   const uint8_t *__restrict__ refbin, const DsbRefInfo *__restrict__ refinfo, uint32_t n_ref,
-                                                   const uint2 *__restrict__ list, unsigned int *cnt, uint32_t band, uint32_t permille, int *arena, uint32_t stride,
-                                                   dsb_hit_identity *__restrict__ rec, IdentAlnOut A)
-{
-	const int lane = (int)(threadIdx.x & 63u);
-	const size_t wave = blockIdx.x * 4u + (threadIdx.x >> 6);
-	int *fr = arena + wave * stride;
-	uint64_t *trace = A.trace + wave * (A.room / 8u);
-	const uint32_t total = cnt[0];
-	for (;;) {
-		const uint32_t w = ident_take(cnt + 1, lane);
-		if (w >= total) break;
-		const uint2 it = list[w];
-		const DsbHitOut h = hout[it.x];
-		const DsbReadDesc d = rd[it.y];
-		uint64_t ln = 0, off = 0;
-		if (h.ref_ID < n_ref) { const DsbRefInfo ri = refinfo[h.ref_ID]; ln = ri.seq_l; off = ri.seq_offset; }
-		const uint32_t qs = h.q_st < d.len ? h.q_st : d.len, qe = h.q_ed < d.len ? h.q_ed : d.len;
-		const uint64_t ts = h.t_st < ln ? h.t_st : ln, te = h.t_ed < ln ? h.t_ed : ln;
-		IdentSeq s;
-		s.qw = pk + d.pk_off + (h.direction ? 0u : (d.len + 31u) / 32u + 1u); s.qbase = qs; s.n = qe > qs ? qe - qs : 0u;
-		s.tb = refbin; s.tbase = off + ts; s.m = te > ts ? (uint32_t)(te - ts) : 0u;
-		const dsb_hit_identity o = ident_wave<IDENT_TRACE>(s, band, permille, fr, stride / 2u, lane, trace, A.room);
-		wave_sync();
-		const dsb_hit_alignment a = ident_path(s, band, o, trace, A.room, A.ops, A.ops_cap, A.ops_used, lane);
-		rec[it.x] = o; A.aln[it.x] = a;                         // (all lanes, the same values)
+};
+// The caller's pairs (dsb_ctx_edit_pairs, dsb_ctx_align_pairs): pair w as it was given, into slot w
+struct IdentPairs {
+	const uint64_t *qw; const uint8_t *tb; const uint64_t *q_off; const uint32_t *q_len; const uint64_t *t_off; const uint32_t *t_len; uint32_t n_pairs; unsigned int *cnt;
+	DV uint32_t total() const { return n_pairs; }
+	DV unsigned int *work() const { return cnt; }
+	DV uint32_t seq(uint32_t w, IdentSeq &s) const
+	{
+		s.qw = qw; s.qbase = q_off[w]; s.n = q_len[w]; s.tb = tb; s.tbase = t_off[w]; s.m = t_len[w];
+		return w;
 	}
-}
+};
 
-// k_hit_align in checkpoint mode (dsb_ctx_alignment_mode): the same shell; the record's plan divides the wavefront's
-// trace place, the forward pass keeps one segment's trace and the checkpoints, ident_path_ck recomputes the earlier segments in the
-// wavefront's own arena place.  A record without a plan runs as k_hit_edits runs it.
-__global__ void __launch_bounds__(256) k_hit_align_ck(const DsbHitOut *__restrict__ hout, const DsbReadDesc *__restrict__ rd, const uint64_t *__restrict__ pk,
-                                                      const uint8_t *__restrict__ refbin, const DsbRefInfo *__restrict__ refinfo, uint32_t n_ref,
-                                                      const uint2 *__restrict__ list, unsigned int *cnt, uint32_t band, uint32_t permille, int *arena, uint32_t stride,
-                                                      dsb_hit_identity *__restrict__ rec, IdentAlnOut A)
+// One wavefront per entry of the source, taken by the work counter until the source is empty.  The grid is as many wavefronts as
+// the arena (and with a tracing form the trace arena) has places for.  IDENT_PLAIN: one forward pass, the identity record.
+// IDENT_TRACE: the forward pass in the tracing form, then the same wavefront walks back and replays (ident_path); IDENT_CKPT: the
+// record's plan divides the wavefront's trace place, the forward pass keeps one segment's trace and the checkpoints, ident_path_ck
+// recomputes the earlier segments in the wavefront's own arena place, and a record without a plan runs as the plain form runs it.
+// The identity record is the same in all three.  Control flow is wave-uniform from end to start (ident_take): the records are
+// stored by every lane, the same bytes.
+template <int F, class Src>
+DV void ident_records(const Src &src, const IdentRun &r, dsb_hit_identity *rec, const IdentAlnOut &A)
 {
 	const int lane = (int)(threadIdx.x & 63u);
 	const size_t wave = blockIdx.x * 4u + (threadIdx.x >> 6);
-	int *fr = arena + wave * stride;
-	uint64_t *trace = A.trace + wave * (A.room / 8u);
-	const uint32_t total = cnt[0];
+	int *fr = r.arena + wave * r.stride;
+	uint64_t *trace = nullptr;
+	if constexpr (F != IDENT_PLAIN) trace = A.trace + wave * (A.room / 8u);
+	const uint32_t total = src.total();
 	for (;;) {
-		const uint32_t w = ident_take(cnt + 1, lane);
+		const uint32_t w = ident_take(src.work(), lane);
 		if (w >= total) break;
-		const uint2 it = list[w];
-		const DsbHitOut h = hout[it.x];
-		const DsbReadDesc d = rd[it.y];
-		uint64_t ln = 0, off = 0;
-		if (h.ref_ID < n_ref) { const DsbRefInfo ri = refinfo[h.ref_ID]; ln = ri.seq_l; off = ri.seq_offset; }
-		const uint32_t qs = h.q_st < d.len ? h.q_st : d.len, qe = h.q_ed < d.len ? h.q_ed : d.len;
-		const uint64_t ts = h.t_st < ln ? h.t_st : ln, te = h.t_ed < ln ? h.t_ed : ln;
 		IdentSeq s;
-		s.qw = pk + d.pk_off + (h.direction ? 0u : (d.len + 31u) / 32u + 1u); s.qbase = qs; s.n = qe > qs ? qe - qs : 0u;
-		s.tb = refbin; s.tbase = off + ts; s.m = te > ts ? (uint32_t)(te - ts) : 0u;
-		const IdentPlan pl = ident_plan(s.n, s.m, band, permille, A.room);
-		const dsb_hit_identity o = ident_wave<IDENT_CKPT>(s, band, permille, fr, stride / 2u, lane, trace, A.room, &pl);
-		wave_sync();
-		const dsb_hit_alignment a = ident_path_ck(s, band, o, pl, fr, stride / 2u, trace, A.ops, A.ops_cap, A.ops_used, lane);
-		rec[it.x] = o; A.aln[it.x] = a;                         // (all lanes, the same values)
+		const uint32_t at = src.seq(w, s);
+		const IdentBand b = ident_band(s.n, s.m, r.band);
+		if constexpr (F == IDENT_PLAIN) {
+			rec[at] = ident_wave<F>(s, b, r.band, r.permille, fr, r.stride / 2u, lane, nullptr, 0, nullptr);
+		} else {
+			IdentPlan pl = {};                                      // (IDENT_CKPT alone reads it)
+			if constexpr (F == IDENT_CKPT) pl = ident_plan(s.n, s.m, r.band, r.permille, A.room);
+			const dsb_hit_identity o = ident_wave<F>(s, b, r.band, r.permille, fr, r.stride / 2u, lane, trace, A.room, &pl);
+			wave_sync();
+			dsb_hit_alignment a;
+			if constexpr (F == IDENT_CKPT) a = ident_path_ck(s, b, o, pl, fr, r.stride / 2u, trace, A, lane);
+			else a = ident_path(s, b, o, trace, A, lane);
+			rec[at] = o; A.aln[at] = a;
+		}
 	}
 }
+
+// The three kernels of a batch's records (identity_run): --identity alone, with the path kept (dsb_ctx_enable_alignment), and that in
+// checkpoint mode (dsb_ctx_alignment_mode).  One parameter list, so that they launch alike; k_hit_edits does not read A.
+// The source's pointers are parameters of the kernel, not an IdentHits by value: as members they lose __restrict__, and without it
+// the hit kernels take four more vector registers each (32 / 38 / 50).
+#define IDENT_HIT_PARAMS const DsbHitOut *__restrict__ hout, const DsbReadDesc *__restrict__ rd, const uint64_t *__restrict__ pk, const uint8_t *__restrict__ refbin, \
+	const DsbRefInfo *__restrict__ refinfo, uint32_t n_ref, const uint2 *__restrict__ list, unsigned int *cnt, IdentRun r, dsb_hit_identity *__restrict__ rec, IdentAlnOut A
+#define IDENT_HIT_SRC IdentHits{hout, rd, pk, refbin, refinfo, n_ref, list, cnt}
+__global__ void __launch_bounds__(256) k_hit_edits(IDENT_HIT_PARAMS) { ident_records<IDENT_PLAIN>(IDENT_HIT_SRC, r, rec, A); }
+__global__ void __launch_bounds__(256) k_hit_align(IDENT_HIT_PARAMS) { ident_records<IDENT_TRACE>(IDENT_HIT_SRC, r, rec, A); }
+__global__ void __launch_bounds__(256) k_hit_align_ck(IDENT_HIT_PARAMS) { ident_records<IDENT_CKPT>(IDENT_HIT_SRC, r, rec, A); }
 
 // The batch's records into the run's table, behind k_hit_edits on the same stream: one lane per listed record, equal ref_IDs grouped
 // inside the wavefront first (as k_lca_count groups taxids), the first lane of a group adding the group's sums.  Integer adds only.
@@ -497,65 +505,13 @@ __global__ void __launch_bounds__(256) k_ident_pack_t(const uint8_t *__restrict_
 	for (uint32_t b = 0; b < 4; b++) { const uint64_t p = w * 4 + b; v = (v << 2) | (p < n_bases ? codes[p] & 3u : 0u); }
 	bytes[w] = (uint8_t)v;
 }
-__global__ void __launch_bounds__(256) k_pair_edits(const uint64_t *__restrict__ qw, const uint8_t *__restrict__ tb, const uint64_t *__restrict__ q_off,
-                                                    const uint32_t *__restrict__ q_len, const uint64_t *__restrict__ t_off, const uint32_t *__restrict__ t_len,
-                                                    uint32_t n_pairs, unsigned int *work, uint32_t band, uint32_t permille, int *arena, uint32_t stride,
-                                                    dsb_hit_identity *__restrict__ out)
-{
-	const int lane = (int)(threadIdx.x & 63u);
-	int *fr = arena + (size_t)(blockIdx.x * 4u + (threadIdx.x >> 6)) * stride;
-	for (;;) {
-		const uint32_t w = ident_take(work, lane);
-		if (w >= n_pairs) break;
-		IdentSeq s;
-		s.qw = qw; s.qbase = q_off[w]; s.n = q_len[w]; s.tb = tb; s.tbase = t_off[w]; s.m = t_len[w];
-		const dsb_hit_identity o = ident_wave<IDENT_PLAIN>(s, band, permille, fr, stride / 2u, lane);
-		out[w] = o;                                             // (all lanes, the same value: ident_take)
-	}
-}
-// its tracing twin (dsb_ctx_align_pairs): what k_hit_align does to a record, on pair w
-__global__ void __launch_bounds__(256) k_pair_align(const uint64_t *__restrict__ qw, const uint8_t *__restrict__ tb, const uint64_t *__restrict__ q_off,
-                                                    const uint32_t *__restrict__ q_len, const uint64_t *__restrict__ t_off, const uint32_t *__restrict__ t_len,
-                                                    uint32_t n_pairs, unsigned int *work, uint32_t band, uint32_t permille, int *arena, uint32_t stride,
-                                                    dsb_hit_identity *__restrict__ out, IdentAlnOut A)
-{
-	const int lane = (int)(threadIdx.x & 63u);
-	const size_t wave = blockIdx.x * 4u + (threadIdx.x >> 6);
-	int *fr = arena + wave * stride;
-	uint64_t *trace = A.trace + wave * (A.room / 8u);
-	for (;;) {
-		const uint32_t w = ident_take(work, lane);
-		if (w >= n_pairs) break;
-		IdentSeq s;
-		s.qw = qw; s.qbase = q_off[w]; s.n = q_len[w]; s.tb = tb; s.tbase = t_off[w]; s.m = t_len[w];
-		const dsb_hit_identity o = ident_wave<IDENT_TRACE>(s, band, permille, fr, stride / 2u, lane, trace, A.room);
-		wave_sync();
-		const dsb_hit_alignment a = ident_path(s, band, o, trace, A.room, A.ops, A.ops_cap, A.ops_used, lane);
-		out[w] = o; A.aln[w] = a;                               // (all lanes, the same values)
-	}
-}
-// and in checkpoint mode (dsb_ctx_align_pairs_mode): what k_hit_align_ck does to a record, on pair w
-__global__ void __launch_bounds__(256) k_pair_align_ck(const uint64_t *__restrict__ qw, const uint8_t *__restrict__ tb, const uint64_t *__restrict__ q_off,
-                                                       const uint32_t *__restrict__ q_len, const uint64_t *__restrict__ t_off, const uint32_t *__restrict__ t_len,
-                                                       uint32_t n_pairs, unsigned int *work, uint32_t band, uint32_t permille, int *arena, uint32_t stride,
-                                                       dsb_hit_identity *__restrict__ out, IdentAlnOut A)
-{
-	const int lane = (int)(threadIdx.x & 63u);
-	const size_t wave = blockIdx.x * 4u + (threadIdx.x >> 6);
-	int *fr = arena + wave * stride;
-	uint64_t *trace = A.trace + wave * (A.room / 8u);
-	for (;;) {
-		const uint32_t w = ident_take(work, lane);
-		if (w >= n_pairs) break;
-		IdentSeq s;
-		s.qw = qw; s.qbase = q_off[w]; s.n = q_len[w]; s.tb = tb; s.tbase = t_off[w]; s.m = t_len[w];
-		const IdentPlan pl = ident_plan(s.n, s.m, band, permille, A.room);
-		const dsb_hit_identity o = ident_wave<IDENT_CKPT>(s, band, permille, fr, stride / 2u, lane, trace, A.room, &pl);
-		wave_sync();
-		const dsb_hit_alignment a = ident_path_ck(s, band, o, pl, fr, stride / 2u, trace, A.ops, A.ops_cap, A.ops_used, lane);
-		out[w] = o; A.aln[w] = a;                               // (all lanes, the same values)
-	}
-}
+// the three kernels of the caller's pairs (ident_pairs): what k_hit_edits, k_hit_align and k_hit_align_ck do to a record, on pair w
+#define IDENT_PAIR_PARAMS const uint64_t *__restrict__ qw, const uint8_t *__restrict__ tb, const uint64_t *__restrict__ q_off, const uint32_t *__restrict__ q_len, \
+	const uint64_t *__restrict__ t_off, const uint32_t *__restrict__ t_len, uint32_t n_pairs, unsigned int *work, IdentRun r, dsb_hit_identity *__restrict__ out, IdentAlnOut A
+#define IDENT_PAIR_SRC IdentPairs{qw, tb, q_off, q_len, t_off, t_len, n_pairs, work}
+__global__ void __launch_bounds__(256) k_pair_edits(IDENT_PAIR_PARAMS) { ident_records<IDENT_PLAIN>(IDENT_PAIR_SRC, r, out, A); }
+__global__ void __launch_bounds__(256) k_pair_align(IDENT_PAIR_PARAMS) { ident_records<IDENT_TRACE>(IDENT_PAIR_SRC, r, out, A); }
+__global__ void __launch_bounds__(256) k_pair_align_ck(IDENT_PAIR_PARAMS) { ident_records<IDENT_CKPT>(IDENT_PAIR_SRC, r, out, A); }
 
 // ================================== host side ====================================================
 // ints of a wavefront's arena place: two generations of the widest band (|d| <= DSB_IDENT_MAX_SKEW) with its two unreached ends
@@ -568,6 +524,12 @@ static int ident_waves(int device, uint32_t *n_waves)
 	*n_waves = (uint32_t)(cus > 0 ? cus : 1) * 8u;
 	return DSB_OK;
 }
+// the kernel of a launch site: the plain form, with alignment on the tracing form, and in checkpoint mode the checkpointed one
+template <class K> static K ident_kernel(K plain, K trace, K ckpt, bool aln, uint32_t mode) { return !aln ? plain : mode == DSB_ALN_MODE_CHECKPOINT ? ckpt : trace; }
+// the ranges of the options, wherever a caller gives them
+static bool ident_opts_ok(uint32_t band, uint32_t max_permille) { return band <= DSB_IDENT_MAX_BAND && max_permille >= 1 && max_permille <= 1000; }
+static bool trace_kib_ok(uint32_t trace_kib) { return trace_kib >= 1 && trace_kib <= DSB_ALN_TRACE_KIB_MAX; }
+static bool aln_mode_ok(uint32_t mode) { return mode == DSB_ALN_MODE_FULL || mode == DSB_ALN_MODE_CHECKPOINT; }
 
 // alignment off: the trace arena, the records and the operation array freed (identity stays as it is)
 static void alignment_release(dsb_ctx *c)
@@ -599,7 +561,7 @@ extern "C" int dsb_ctx_enable_identity(dsb_ctx *c, int on, uint32_t band, uint32
 {
 	if (!c) return DSB_EINVAL;
 	if (on && band == 0 && max_permille == 0) { band = DSB_IDENT_BAND_DEFAULT; max_permille = DSB_IDENT_PERMILLE_DEFAULT; }
-	if (on && (band > DSB_IDENT_MAX_BAND || max_permille < 1 || max_permille > 1000)) return DSB_EINVAL;
+	if (on && !ident_opts_ok(band, max_permille)) return DSB_EINVAL;
 	HIPCHK(hipSetDevice(c->device));
 	HIPCHK(hipStreamSynchronize(c->stream));
 	if (on && c->ident.d_tab && c->ident.band == band) { c->ident.permille = max_permille; return dsb_ctx_reset_identity(c); }
@@ -623,7 +585,7 @@ extern "C" int dsb_ctx_enable_alignment(dsb_ctx *c, int on, uint32_t trace_kib, 
 	if (!c) return DSB_EINVAL;
 	if (on && !c->ident.d_tab) return DSB_EINVAL;
 	if (on && trace_kib == 0) trace_kib = DSB_ALN_TRACE_KIB_DEFAULT;
-	if (on && trace_kib > DSB_ALN_TRACE_KIB_MAX) return DSB_EINVAL;
+	if (on && !trace_kib_ok(trace_kib)) return DSB_EINVAL;
 	HIPCHK(hipSetDevice(c->device));
 	HIPCHK(hipStreamSynchronize(c->stream));
 	alignment_release(c);
@@ -639,15 +601,14 @@ extern "C" int dsb_ctx_enable_alignment(dsb_ctx *c, int on, uint32_t trace_kib, 
 
 extern "C" int dsb_ctx_alignment_mode(dsb_ctx *c, uint32_t mode)
 {
-	if (!c || !c->ident.d_trace || (mode != DSB_ALN_MODE_FULL && mode != DSB_ALN_MODE_CHECKPOINT)) return DSB_EINVAL;
+	if (!c || !c->ident.d_trace || !aln_mode_ok(mode)) return DSB_EINVAL;
 	c->ident.aln_mode = mode;                                    // (host state alone: the next batch's launch reads it)
 	return DSB_OK;
 }
 
 extern "C" int dsb_aln_plan(uint32_t n, uint32_t m, uint32_t band, uint32_t max_permille, uint32_t trace_kib, uint32_t *K, uint32_t *n_ckpt)
 {
-	if (!K || !n_ckpt || n >= IDENT_MAX_RUN || m >= IDENT_MAX_RUN || band > DSB_IDENT_MAX_BAND || max_permille < 1 || max_permille > 1000 ||
-	    trace_kib < 1 || trace_kib > DSB_ALN_TRACE_KIB_MAX) return DSB_EINVAL;
+	if (!K || !n_ckpt || n >= IDENT_MAX_RUN || m >= IDENT_MAX_RUN || !ident_opts_ok(band, max_permille) || !trace_kib_ok(trace_kib)) return DSB_EINVAL;
 	const IdentPlan p = ident_plan(n, m, band, max_permille, (uint64_t)trace_kib * 1024u);
 	*K = p.K; *n_ckpt = p.n_ck;
 	return p.ok ? 1 : 0;
@@ -661,23 +622,38 @@ int identity_run(dsb_ctx *c, const DsbBatchView &b)
 	HIPCHK(hipMemsetAsync(d.d_rec, 0, b.cap_hout * sizeof(dsb_hit_identity), b.st));
 	HIPCHK(hipMemsetAsync(d.d_cnt, 0, 2 * sizeof(unsigned int), b.st));
 	hipLaunchKernelGGL(k_ident_list, dim3((b.n + 255) / 256), dim3(256), 0, b.st, b.rout, b.hout, b.counters, (uint32_t)b.cap_hout, b.n, d.d_list, d.d_cnt);
+	IdentAlnOut A = {};
 	if (d.d_trace) {
 		// alignment on: the records' room and the batch's operation array (automatic: an operation per base and four per hit place)
 		d.ops_room = d.ops_fixed ? d.ops_fixed : c->in[c->cur].total_bases + 4ull * b.cap_hout;
 		if (grow(&d.d_aln, &d.cap_aln, b.cap_hout) || grow(&d.d_ops, &d.cap_ops, (size_t)d.ops_room)) return DSB_ENOMEM;
 		HIPCHK(hipMemsetAsync(d.d_aln, 0, b.cap_hout * sizeof(dsb_hit_alignment), b.st));
 		HIPCHK(hipMemsetAsync(d.d_ops_used, 0, sizeof(unsigned long long), b.st));
-		IdentAlnOut A; A.trace = d.d_trace; A.room = (uint64_t)d.trace_kib * 1024u; A.aln = d.d_aln; A.ops = d.d_ops; A.ops_cap = d.ops_room; A.ops_used = d.d_ops_used;
-		hipLaunchKernelGGL(d.aln_mode == DSB_ALN_MODE_CHECKPOINT ? k_hit_align_ck : k_hit_align, dim3(d.n_waves / 4), dim3(256), 0, b.st, b.hout, b.rd, b.pk, c->dx.refbin,
-		                   c->dx.refinfo, (uint32_t)dsb_index_n_ref(c->idx), (const uint2 *)d.d_list, d.d_cnt, d.band, d.permille, d.d_arena, d.stride, d.d_rec, A);
+		A.trace = d.d_trace; A.room = (uint64_t)d.trace_kib * 1024u; A.aln = d.d_aln; A.ops = d.d_ops; A.ops_cap = d.ops_room; A.ops_used = d.d_ops_used;
 		d.aln_run = true;
-	} else
-	hipLaunchKernelGGL(k_hit_edits, dim3(d.n_waves / 4), dim3(256), 0, b.st, b.hout, b.rd, b.pk, c->dx.refbin, c->dx.refinfo, (uint32_t)dsb_index_n_ref(c->idx),
-	                   (const uint2 *)d.d_list, d.d_cnt, d.band, d.permille, d.d_arena, d.stride, d.d_rec);
+	}
+	const IdentRun r = {d.band, d.permille, d.d_arena, d.stride};
+	hipLaunchKernelGGL(ident_kernel(k_hit_edits, k_hit_align, k_hit_align_ck, d.d_trace != nullptr, d.aln_mode), dim3(d.n_waves / 4), dim3(256), 0, b.st, b.hout, b.rd, b.pk,
+	                   c->dx.refbin, c->dx.refinfo, (uint32_t)dsb_index_n_ref(c->idx), (const uint2 *)d.d_list, d.d_cnt, r, d.d_rec, A);
 	const size_t ref_blocks = std::min<size_t>((b.cap_hout + 255) / 256, 1024);
 	hipLaunchKernelGGL(k_ident_ref, dim3((unsigned)(ref_blocks ? ref_blocks : 1)), dim3(256), 0, b.st, b.hout, (const uint2 *)d.d_list, (const unsigned int *)d.d_cnt,
 	                   (const dsb_hit_identity *)d.d_rec, (uint32_t)dsb_index_n_ref(c->idx), d.d_tab);
 	d.run = true;
+	return DSB_OK;
+}
+
+// The used part of an operation array of `room` operations, queued on st: its length has to be known before the copy is queued, so
+// it is read first (8 bytes and one wait on the stream).  to(used) gives the place the operations go to.
+template <class To>
+static int ident_fetch_ops(hipStream_t st, const uint32_t *d_ops, const unsigned long long *d_used, uint64_t room, uint64_t *n_used, To to)
+{
+	unsigned long long used = 0;
+	HIPCHK(hipMemcpyAsync(&used, d_used, sizeof used, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	if (used > room) used = room;                            // (reservations that did not fit moved the counter too)
+	uint32_t *h_ops = to((size_t)used);
+	if (used) HIPCHK(hipMemcpyAsync(h_ops, d_ops, (size_t)used * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+	*n_used = used;
 	return DSB_OK;
 }
 
@@ -686,19 +662,14 @@ int identity_fetch_queue(dsb_ctx *c, size_t n_hits)
 	c->ident.h_rec.resize(n_hits);
 	if (n_hits) HIPCHK(hipMemcpyAsync(c->ident.h_rec.data(), c->ident.d_rec, n_hits * sizeof(dsb_hit_identity), hipMemcpyDeviceToHost, c->stream));
 	if (!c->ident.aln_run) return DSB_OK;
-	// alignment: the records, and the used part of the operation array alone -- its length has to be known before the copy is
-	// queued, so it is read first (8 bytes, one wait on the stream that the batch's counters have already been waited for on)
+	// alignment: the records, and the used part of the operation array alone (the stream's one more wait comes after the batch's
+	// counters have already been waited for on it)
 	DsbIdent &d = c->ident;
 	d.h_aln.resize(n_hits); d.h_ops.clear();
 	if (!n_hits) return DSB_OK;
-	unsigned long long used = 0;
+	uint64_t used = 0;
 	HIPCHK(hipMemcpyAsync(d.h_aln.data(), d.d_aln, n_hits * sizeof(dsb_hit_alignment), hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipMemcpyAsync(&used, d.d_ops_used, sizeof used, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipStreamSynchronize(c->stream));
-	if (used > d.ops_room) used = d.ops_room;                // (reservations that did not fit moved the counter too)
-	d.h_ops.resize((size_t)used);
-	if (used) HIPCHK(hipMemcpyAsync(d.h_ops.data(), d.d_ops, (size_t)used * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-	return DSB_OK;
+	return ident_fetch_ops(c->stream, d.d_ops, d.d_ops_used, d.ops_room, &used, [&d](size_t n) { d.h_ops.resize(n); return d.h_ops.data(); });
 }
 
 extern "C" int dsb_batch_alignment(dsb_ctx *c, const dsb_hit_alignment **recs, const uint32_t **ops, uint64_t *n_ops)
@@ -755,7 +726,7 @@ extern "C" int dsb_multi_enable_alignment(dsb_multi *m, int on, uint32_t trace_k
 
 extern "C" int dsb_multi_alignment_mode(dsb_multi *m, uint32_t mode)
 {
-	if (!m || !m->aln_on || (mode != DSB_ALN_MODE_FULL && mode != DSB_ALN_MODE_CHECKPOINT)) return DSB_EINVAL;
+	if (!m || !m->aln_on || !aln_mode_ok(mode)) return DSB_EINVAL;
 	for (dsb_ctx *c : m->ctx) if (int rc = dsb_ctx_alignment_mode(c, mode)) return rc;
 	return DSB_OK;
 }
@@ -796,8 +767,8 @@ struct IdentPairsAln { uint32_t trace_kib, mode; dsb_hit_alignment *aln_out; uin
 static int ident_pairs(dsb_ctx *c, const uint8_t *q_codes, const uint64_t *q_off, const uint32_t *q_len, const uint8_t *t_codes, const uint64_t *t_off,
                        const uint32_t *t_len, size_t n_pairs, uint32_t band, uint32_t max_permille, dsb_hit_identity *out, const IdentPairsAln *al)
 {
-	if (!c || band > DSB_IDENT_MAX_BAND || max_permille < 1 || max_permille > 1000 || n_pairs > 0xffffffffu) return DSB_EINVAL;
-	if (al && (!al->ops_used || al->trace_kib < 1 || al->trace_kib > DSB_ALN_TRACE_KIB_MAX || (al->mode != DSB_ALN_MODE_FULL && al->mode != DSB_ALN_MODE_CHECKPOINT))) return DSB_EINVAL;
+	if (!c || !ident_opts_ok(band, max_permille) || n_pairs > 0xffffffffu) return DSB_EINVAL;
+	if (al && (!al->ops_used || !trace_kib_ok(al->trace_kib) || !aln_mode_ok(al->mode))) return DSB_EINVAL;
 	if (al) *al->ops_used = 0;
 	if (!n_pairs) return DSB_OK;
 	if (!q_codes || !q_off || !q_len || !t_codes || !t_off || !t_len || !out || (al && (!al->aln_out || (!al->ops_out && al->ops_cap)))) return DSB_EINVAL;
@@ -839,23 +810,15 @@ static int ident_pairs(dsb_ctx *c, const uint8_t *q_codes, const uint64_t *q_off
 	HIPCHK(hipMemsetAsync(d_work, 0, sizeof(unsigned int), st));
 	hipLaunchKernelGGL(k_ident_pack_q, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, st, (const uint8_t *)d_qc, nq, d_qw, n_words);
 	hipLaunchKernelGGL(k_ident_pack_t, dim3((unsigned)((n_bytes + 255) / 256)), dim3(256), 0, st, (const uint8_t *)d_tc, nt, d_tb, n_bytes);
-	if (al) {
-		HIPCHK(hipMemsetAsync(A.ops_used, 0, sizeof(unsigned long long), st));
-		hipLaunchKernelGGL(al->mode == DSB_ALN_MODE_CHECKPOINT ? k_pair_align_ck : k_pair_align, dim3(n_waves / 4), dim3(256), 0, st, (const uint64_t *)d_qw, (const uint8_t *)d_tb, (const uint64_t *)d_qo, (const uint32_t *)d_ql,
-		                   (const uint64_t *)d_to, (const uint32_t *)d_tl, (uint32_t)n_pairs, d_work, band, max_permille, d_arena, stride, d_out, A);
-	} else
-	hipLaunchKernelGGL(k_pair_edits, dim3(n_waves / 4), dim3(256), 0, st, (const uint64_t *)d_qw, (const uint8_t *)d_tb, (const uint64_t *)d_qo, (const uint32_t *)d_ql,
-	                   (const uint64_t *)d_to, (const uint32_t *)d_tl, (uint32_t)n_pairs, d_work, band, max_permille, d_arena, stride, d_out);
+	if (al) HIPCHK(hipMemsetAsync(A.ops_used, 0, sizeof(unsigned long long), st));
+	const IdentRun r = {band, max_permille, d_arena, stride};
+	hipLaunchKernelGGL(ident_kernel(k_pair_edits, k_pair_align, k_pair_align_ck, al != nullptr, al ? al->mode : 0u), dim3(n_waves / 4), dim3(256), 0, st, (const uint64_t *)d_qw,
+	                   (const uint8_t *)d_tb, (const uint64_t *)d_qo, (const uint32_t *)d_ql, (const uint64_t *)d_to, (const uint32_t *)d_tl, (uint32_t)n_pairs, d_work, r, d_out, A);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipMemcpyAsync(out, d_out, n_pairs * sizeof(dsb_hit_identity), hipMemcpyDeviceToHost, st));
 	if (al) {
-		unsigned long long used = 0;
 		HIPCHK(hipMemcpyAsync(al->aln_out, A.aln, n_pairs * sizeof(dsb_hit_alignment), hipMemcpyDeviceToHost, st));
-		HIPCHK(hipMemcpyAsync(&used, A.ops_used, sizeof used, hipMemcpyDeviceToHost, st));
-		HIPCHK(hipStreamSynchronize(st));
-		if (used > al->ops_cap) used = al->ops_cap;           // (reservations that did not fit moved the counter too)
-		if (used) HIPCHK(hipMemcpyAsync(al->ops_out, A.ops, (size_t)used * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-		*al->ops_used = used;
+		if (int rc = ident_fetch_ops(st, A.ops, A.ops_used, al->ops_cap, al->ops_used, [al](size_t) { return al->ops_out; })) return rc;
 	}
 	HIPCHK(hipStreamSynchronize(st));
 	return DSB_OK;
